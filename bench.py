@@ -19,6 +19,20 @@ Self-launch: `python bench.py --gpus N` with N > 1 and no torch.distributed envi
 GPU) and exits with its status; under a launcher, --gpus must equal WORLD_SIZE or the run fails.
 `--workload selftest` is a CPU-only stand-in step (no GPU, no kernels) that exercises exactly
 this launch / barrier / max-over-ranks / JSON path (tests/test_distributed.py).
+
+A plain run does only what the headline figure needs: set-up, the warm-up steps, the K timed steps,
+the output dump if `--dump-outputs DIR` is given, and the result line (metric, value, unit,
+ms_per_step, dtype, config). `--full` adds everything else the result line can carry, each measured
+in passes of its own after the timed region: the roofline objects (dominant kernel, Winograd
+convolutions, split-bf16 GEMMs, the render kernel's VALU roofline), the committed PMC traffic
+digest, the launched-routes label of the workload string and the CPU baseline. The options that
+only shape those (--dominant, --no-cpu-baseline, --cpu-baseline-seconds, --cpu-baseline-1thread) are
+accepted and unused in a plain run, whose `config.workload` ends after the precision modes.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32; `color` for e2e, `color` and `radii` for raster, `out` for selftest; rank r > 0 writes
+<name>.rank<r>.npy). Inputs and weights are seeded, so two builds run with the same arguments can
+be compared output for output. Above 64 MiB on disk, a fixed seeded sample of each array is written.
 """
 from __future__ import annotations
 
@@ -53,13 +67,20 @@ def parse():
     ap.add_argument("--attn-dtype", choices=["auto", "fp32", "bf16x3", "bf16"], default="auto",
                     help="window attention: auto = bf16 under bf16 dense layers, bf16x3 (split-bf16 products, "
                          "fp32 softmax) under bf16x3 ones, else exact fp32")
-    ap.add_argument("--dominant", default=None, help="kernel timed for the roofline object")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, after the timed steps: roofline "
+                         "objects (per-kernel HIP-event passes), PMC traffic digest, launched-routes label, CPU "
+                         "baseline. Off by default: a plain run times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all: a fixed seeded sample of anything larger)")
+    ap.add_argument("--dominant", default=None, help="kernel timed for the roofline object (--full)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph per step")
     ap.add_argument("--batch", type=int, default=1, help="scenes per step per GPU")
-    ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0, help="with --full: its time budget")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-baseline-1thread", action="store_true",
-                    help="also time the e2e CPU port on ONE thread (one full scene: several minutes)")
+                    help="with --full: also time the e2e CPU port on ONE thread (one full scene: several minutes)")
     ap.add_argument("--no-conv-search", action="store_true",
                     help="MIOpen's default convolution algorithm choice instead of its measured search "
                          "(torch.backends.cudnn.benchmark, on by default: +2.4%% e2e at b = 1)")
@@ -165,7 +186,10 @@ def build_raster_workload(batch: int, device, scene_offset: int):
         "alg_bytes_per_launch": raster_bytes_per_view(g_per_scene, g["harmonics"].shape[-1], *hw) * b * v,
         "workload": "raster-only: decoder on synthetic Gaussians (G=131072/scene, 3 target views)",
     }
-    cpu_inputs = ({k: t.cpu() for k, t in g.items()}, cams.to("cpu"), hw, v)
+
+    def cpu_inputs():  # host copies for the CPU baseline (--full), made only when asked for
+        return {k: t.cpu() for k, t in g.items()}, cams.to("cpu"), hw, v
+
     return step, info, cpu_inputs
 
 
@@ -388,18 +412,32 @@ def cpu_baseline_raster(cpu_inputs, seconds: float):
     }
 
 
+def keeping_last(step):
+    """`step` wrapped to keep what its latest call returned (--dump-outputs): (wrapped, [last])."""
+    last = [None]
+
+    def timed():
+        last[0] = step()
+
+    return timed, last
+
+
 def selftest_main(args, world, rank):
     """CPU stand-in step (a small matmul, plus rank-dependent sleep so the max-over-ranks is
-    observable): the launch, barrier, timing all-reduce and JSON line of the real bench, no GPU."""
-    x = torch.randn(128, 128)
+    observable): the launch, barrier, timing all-reduce and JSON line of the real bench, no GPU.
+    --dump-outputs writes the step's product as `out`; there is nothing for --full to add."""
+    x = torch.randn(128, 128, generator=torch.Generator().manual_seed(rank))
 
     def step():
         time.sleep(0.01 * (rank + 1))
         return x @ x
 
+    timed, last = keeping_last(step) if args.dump_outputs else (step, None)
     for _ in range(args.warmup):
-        step()
-    elapsed = timed_steps(step, args.steps, world, lambda: None, torch.device("cpu"))
+        timed()
+    elapsed = timed_steps(timed, args.steps, world, lambda: None, torch.device("cpu"))
+    if args.dump_outputs:
+        dump_outputs(last[0], Path(args.dump_outputs), rank)
     if rank == 0:
         print(json.dumps({"metric": "selftest steps/s", "value": world * args.steps / elapsed, "unit": "steps/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -443,18 +481,98 @@ def main():
 
         step, info, model = build_e2e_workload(args.batch, device, scene_offset=rank * args.batch,
                                                dense_dtype=args.dense_dtype, graph=not args.no_graph,
-                                               attn_dtype=args.attn_dtype)
+                                               attn_dtype=args.attn_dtype, routes=args.full)
         info.update(e2e_roofline_info(args.dominant or "win_attn", args.batch, attn_dtype))
-        cpu_inputs = ("e2e", model)
     if args.dominant and args.workload == "raster":
         info["dominant"] = args.dominant
 
+    timed, last = keeping_last(step) if args.dump_outputs else (step, None)
     for _ in range(args.warmup):
-        step()
-    elapsed = timed_steps(step, args.steps, world, torch.cuda.synchronize, device)
+        timed()
+    elapsed = timed_steps(timed, args.steps, world, torch.cuda.synchronize, device)
     from transplat_amd.model.decoder.hip_splatting import check_status
 
     check_status(device)  # any capacity overflow during the timed steps invalidates the run
+    if args.dump_outputs:  # before anything else launches: a graphed step's outputs are static buffers
+        torch.cuda.synchronize()
+        dump_outputs(last[0], Path(args.dump_outputs), rank)
+
+    views = world * info["views_per_step"] * args.steps
+    result = {
+        "metric": "novel views/sec at 256x256, 2 ctx views; PSNR parity vs reference",
+        "value": views / elapsed,
+        "unit": "views/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": dtype_label,
+        "data": "synthetic",
+        "config": {
+            "workload": info["workload"],
+            "scenes_per_gpu_per_step": args.batch,
+            "views_per_scene": 3,
+            "image": [256, 256],
+            "parallelism": f"scene-shard x{world}",
+        },
+    }
+    if args.full:
+        result.update(full_measurements(args, step, info, elapsed, attn_dtype))
+        if rank == 0 and not args.no_cpu_baseline:
+            if args.workload == "raster":
+                result["cpu_baseline"] = cpu_baseline_raster(cpu_inputs(), args.cpu_baseline_seconds)
+            else:
+                result["cpu_baseline"] = cpu_baseline_e2e(model, args.cpu_baseline_seconds, args.cpu_baseline_1thread)
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64 * 2**20  # of the .npy files on disk, headers included
+NPY_HEADER_BYTES = 128  # numpy.save's header for a one-dimensional array (format 1.0, padded to 64)
+
+
+def dump_outputs(out, folder: Path, rank: int = 0) -> None:
+    """What one call of the timed path hands its caller, as <name>.npy in float32 (float64 for
+    64-bit values): the decoder's `color` [b, v, 3, h, w] (and `depth` when it renders one) for the
+    e2e step, `color` and the per-Gaussian `radii` for the raster-only step. Above DUMP_BUDGET_BYTES
+    on disk, each array is cut to its share of the budget: the flattened array is split into equal
+    strata and one element of each is kept, at an offset drawn from numpy's default_rng(0), so the
+    sample is sorted, free of duplicates and the same for every run of the same shapes."""
+    import numpy as np
+
+    if torch.is_tensor(out):
+        named = {"out": out}
+    elif isinstance(out, tuple):
+        named = dict(zip(("color", "radii"), out))
+    else:
+        named = {"color": out.color, "depth": out.depth}
+    arrays = {}
+    for name, t in named.items():
+        if t is None:
+            continue
+        wide = t.dtype in (torch.float64, torch.int64)
+        arrays[name] = t.detach().to("cpu", torch.float64 if wide else torch.float32).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    folder.mkdir(parents=True, exist_ok=True)
+    payload = DUMP_BUDGET_BYTES - NPY_HEADER_BYTES * len(arrays)
+    for name, a in arrays.items():
+        if total > payload:
+            keep = max(1, int(a.size * payload / total))  # a.nbytes * payload / total bytes of it
+            lo = np.arange(keep, dtype=np.int64) * a.size // keep
+            hi = np.append(lo[1:], a.size)
+            a = a.reshape(-1)[lo + np.random.default_rng(0).integers(0, hi - lo)]
+        np.save(folder / (f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
+
+
+def full_measurements(args, step, info, elapsed, attn_dtype) -> dict:
+    """--full: the roofline objects of the result line, measured after the timed region in passes
+    of their own (HIP events around one kernel family at a time)."""
+    from transplat_amd import _lib
 
     # dominant-kernel timing (HIP events on the launch stream), separate from the timed region;
     # event records cannot live inside a replayed hipGraph, so this pass launches eagerly (the
@@ -544,27 +662,7 @@ def main():
 
     render_valu = render_valu_roofline(step, n_prof) if args.workload == "raster" else None
     serial.__exit__(None, None, None)
-    views = world * info["views_per_step"] * args.steps
     result = {
-        "metric": "novel views/sec at 256x256, 2 ctx views; PSNR parity vs reference",
-        "value": views / elapsed,
-        "unit": "views/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": dtype_label,
-        "data": "synthetic",
-        "config": {
-            "workload": info["workload"],
-            "scenes_per_gpu_per_step": args.batch,
-            "views_per_scene": 3,
-            "image": [256, 256],
-            "parallelism": f"scene-shard x{world}",
-        },
         "roofline": {
             "kernel": info["dominant"],
             "bound": info.get("bound", "hbm"),
@@ -588,16 +686,7 @@ def main():
         result["roofline_gemm"] = gemm_roofline
     if render_valu is not None:
         result["roofline_render_valu"] = render_valu
-    if rank == 0 and not args.no_cpu_baseline and cpu_inputs is not None:
-        if isinstance(cpu_inputs, tuple) and cpu_inputs[0] == "e2e":
-            result["cpu_baseline"] = cpu_baseline_e2e(cpu_inputs[1], args.cpu_baseline_seconds,
-                                                      args.cpu_baseline_1thread)
-        else:
-            result["cpu_baseline"] = cpu_baseline_raster(cpu_inputs, args.cpu_baseline_seconds)
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return result
 
 
 if __name__ == "__main__":

@@ -178,3 +178,85 @@ def test_bench_gpus_must_match_world_size():
     out = _run_bench("--gpus", "2", "--workload", "selftest", "--steps", "1", "--warmup", "0",
                      env_extra={"WORLD_SIZE": "1"})
     assert out.returncode != 0 and "WORLD_SIZE=1" in (out.stderr + out.stdout)
+
+
+def test_bench_dump_outputs_names_dtype_and_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: one float32 .npy per returned array (rank r > 0 under its own name), and
+    above the byte budget the same seeded sample of each array on every call, within the budget."""
+    import sys
+
+    import numpy as np
+
+    sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+    import bench
+    from transplat_amd.model.decoder import DecoderOutput
+
+    color = torch.rand(1, 3, 3, 8, 8, generator=torch.Generator().manual_seed(3))
+    radii = torch.arange(100, dtype=torch.int32)
+    bench.dump_outputs(DecoderOutput(color, None), tmp_path / "e2e")
+    assert [p.name for p in (tmp_path / "e2e").iterdir()] == ["color.npy"]
+    got = np.load(tmp_path / "e2e" / "color.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, color.numpy())
+    bench.dump_outputs((color[0], radii), tmp_path / "r1", rank=1)
+    assert sorted(p.name for p in (tmp_path / "r1").iterdir()) == ["color.rank1.npy", "radii.rank1.npy"]
+    assert np.array_equal(np.load(tmp_path / "r1" / "radii.rank1.npy"), np.arange(100, dtype=np.float32))
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs((color[0], radii), tmp_path / d)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("color", "radii")}
+    assert 0 < a["radii"].size < 100 and 0 < a["color"].size < color.numel()
+    assert sum((tmp_path / "a" / f"{n}.npy").stat().st_size for n in a) <= 1000  # headers included
+    assert set(a["radii"]) <= set(range(100)) and np.all(np.diff(a["radii"]) > 0)  # sorted, no duplicates
+    for n, x in a.items():
+        assert np.array_equal(x, np.load(tmp_path / "b" / f"{n}.npy"))
+
+
+def test_bench_cli_dump_outputs_selftest(tmp_path):
+    """The command-line wiring of --dump-outputs on the CPU stand-in: exactly --steps timed steps, the
+    last step's product written as out.npy, identical from run to run (seeded input)."""
+    import json
+
+    import numpy as np
+
+    outs = []
+    for d in ("a", "b"):
+        out = _run_bench("--gpus", "1", "--workload", "selftest", "--steps", "3", "--warmup", "1",
+                         "--dump-outputs", str(tmp_path / d))
+        assert out.returncode == 0, out.stderr[-3000:]
+        res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert res["steps"] == 3 and res["ms_per_step"] >= 10.0  # 3 steps of >= 10 ms each were timed
+        assert [p.name for p in (tmp_path / d).iterdir()] == ["out.npy"]
+        outs.append(np.load(tmp_path / d / "out.npy"))
+    x = torch.randn(128, 128, generator=torch.Generator().manual_seed(0))
+    assert outs[0].dtype == np.float32 and np.array_equal(outs[0], (x @ x).numpy())
+    assert np.array_equal(outs[0], outs[1])
+
+
+@pytest.mark.gpu
+def test_bench_cli_dump_outputs_raster_full(device, tmp_path):
+    """`bench.py --workload raster --full --dump-outputs`: the files hold what the timed step returned,
+    not what the --full passes after it left in the buffers (the diag-5 render pass writes counters
+    into the image), and equal an in-process call on the same seeded inputs bit for bit (the blend
+    order is the stable (depth, id) sort, so the rasterizer is run-to-run deterministic). The result
+    line reports the 2 steps asked for and, under --full, the roofline objects."""
+    import json
+    import sys
+
+    import numpy as np
+
+    sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+    import bench
+
+    out = _run_bench("--gpus", "1", "--workload", "raster", "--steps", "2", "--warmup", "1", "--full",
+                     "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "d"))
+    assert out.returncode == 0, out.stderr[-3000:]
+    res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    assert "roofline" in res and "roofline_render_valu" in res and "cpu_baseline" not in res
+    step, _, _ = bench.build_raster_workload(1, device, 0)
+    color, radii = step()
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["color.npy", "radii.npy"]
+    got_c, got_r = np.load(tmp_path / "d" / "color.npy"), np.load(tmp_path / "d" / "radii.npy")
+    assert got_c.dtype == np.float32 and got_c.shape == tuple(color.shape)
+    assert np.array_equal(got_r, radii.cpu().numpy().astype(np.float32))
+    assert np.array_equal(got_c, color.cpu().numpy())

@@ -3,7 +3,7 @@
 A step is the span between consecutive dispatches of a marker kernel that runs once per step
 (default: the rasterizer's render_kernel, the last kernel of test_step). Only steps in the middle
 of the run are averaged (the first `--skip` spans hold warmup, MIOpen's algorithm search and
-graph capture; the last span holds the eager pass bench.py times the roofline kernel with), so
+graph capture; under bench.py --full the last span holds the eager pass that times the roofline kernel), so
 one-time work never lands in the per-step numbers.
 usage: prof_steps.py run_kernel_trace.csv|run_results.db [--marker render_kernel] [--skip 4] [--top 40]
        [--timeline out.txt] [--grids substring]  (one steady-state step, every dispatch in start order with its queue and the

@@ -14,7 +14,7 @@ for i in 1 2; do
       timeout -k 10 120 python -u tools/bench_winattn.py $a > $OUT/wa.log 2>&1 || { tail -3 $OUT/wa.log; exit 2; }
       echo "$lib $i $a: $(grep -v amdgpu $OUT/wa.log | tail -1 | cut -c1-120)"
     done
-    timeout -k 10 300 python -u bench.py --no-cpu-baseline > $OUT/bench_c2_${lib}_$i.log 2>&1 || { tail -5 $OUT/bench_c2_${lib}_$i.log; exit 4; }
+    timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $OUT/bench_c2_${lib}_$i.log 2>&1 || { tail -5 $OUT/bench_c2_${lib}_$i.log; exit 4; }
     echo "$lib $i c2 $(tail -1 $OUT/bench_c2_${lib}_$i.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["value"],1), round(d["roofline"]["frac"],4), d["roofline"]["avg_launch_ms"])')"
   done
 done

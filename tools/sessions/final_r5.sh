@@ -23,15 +23,15 @@ if [ "$PART" = "all" ] || [ "$PART" = "tests" ]; then
 fi
 if [ "$PART" = "all" ] || [ "$PART" = "bench" ]; then
   step bench
-  timeout -k 10 500 python bench.py > $OUT/bench_e2e_x3_b1.log 2>&1 || { tail -5 $OUT/bench_e2e_x3_b1.log; exit 1; }
+  timeout -k 10 500 python bench.py --full > $OUT/bench_e2e_x3_b1.log 2>&1 || { tail -5 $OUT/bench_e2e_x3_b1.log; exit 1; }
   tail -1 $OUT/bench_e2e_x3_b1.log | cut -c1-300
-  timeout -k 10 500 python bench.py --dense-dtype fp32 --no-cpu-baseline > $OUT/bench_e2e_fp32_b1.log 2>&1 || exit 1
+  timeout -k 10 500 python bench.py --full --dense-dtype fp32 --no-cpu-baseline > $OUT/bench_e2e_fp32_b1.log 2>&1 || exit 1
   tail -1 $OUT/bench_e2e_fp32_b1.log | cut -c1-200
-  timeout -k 10 500 python bench.py --batch 8 --dense-dtype bf16x3 --attn-dtype bf16 --no-cpu-baseline > $OUT/bench_c3_stated.log 2>&1 || exit 1
+  timeout -k 10 500 python bench.py --full --batch 8 --dense-dtype bf16x3 --attn-dtype bf16 --no-cpu-baseline > $OUT/bench_c3_stated.log 2>&1 || exit 1
   tail -1 $OUT/bench_c3_stated.log | cut -c1-200
-  timeout -k 10 500 python bench.py --batch 8 --dense-dtype bf16 --no-cpu-baseline > $OUT/bench_c3_bf16dense.log 2>&1 || exit 1
+  timeout -k 10 500 python bench.py --full --batch 8 --dense-dtype bf16 --no-cpu-baseline > $OUT/bench_c3_bf16dense.log 2>&1 || exit 1
   tail -1 $OUT/bench_c3_bf16dense.log | cut -c1-200
-  timeout -k 10 300 python bench.py --workload raster --steps 20 --warmup 3 > $OUT/bench_raster.log 2>&1 || exit 1
+  timeout -k 10 300 python bench.py --full --workload raster --steps 20 --warmup 3 > $OUT/bench_raster.log 2>&1 || exit 1
   tail -1 $OUT/bench_raster.log | cut -c1-300
 fi
 if [ "$PART" = "all" ] || [ "$PART" = "prof" ]; then

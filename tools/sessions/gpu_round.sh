@@ -18,7 +18,7 @@ if [ "${RUN_SMOKE:-1}" = 1 ]; then
   ok $rc || exit $rc
 fi
 if [ "${RUN_BENCH:-1}" = 1 ]; then
-  timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > $OUT/bench_$TAG.log 2>&1; rc=$?
+  timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench_$TAG.log 2>&1; rc=$?
   echo "bench rc=$rc"; tail -3 $OUT/bench_$TAG.log
   [ $rc -eq 0 ] || exit $rc
 fi

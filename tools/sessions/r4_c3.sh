@@ -9,9 +9,9 @@ R=$(pwd)
 OUT=$R/gpurun_out/${TAG:-r4_c3}
 mkdir -p $OUT
 export PYTHONPATH=$R
-timeout -k 10 300 python -u bench.py --batch 8 --dense-dtype bf16x3 --attn-dtype bf16 > $OUT/bench_c3_stated.log 2>&1 || { tail -5 $OUT/bench_c3_stated.log; exit 1; }
+timeout -k 10 300 python -u bench.py --full --batch 8 --dense-dtype bf16x3 --attn-dtype bf16 > $OUT/bench_c3_stated.log 2>&1 || { tail -5 $OUT/bench_c3_stated.log; exit 1; }
 echo "stated $(tail -1 $OUT/bench_c3_stated.log | cut -c1-200)"
-timeout -k 10 300 python -u bench.py --batch 8 --dense-dtype bf16 > $OUT/bench_c3_bf16dense.log 2>&1 || { tail -5 $OUT/bench_c3_bf16dense.log; exit 1; }
+timeout -k 10 300 python -u bench.py --full --batch 8 --dense-dtype bf16 > $OUT/bench_c3_bf16dense.log 2>&1 || { tail -5 $OUT/bench_c3_bf16dense.log; exit 1; }
 echo "bf16-dense $(tail -1 $OUT/bench_c3_bf16dense.log | cut -c1-200)"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_c3_stated -o run --output-format csv -- python3 $R/bench.py --batch 8 --dense-dtype bf16x3 --attn-dtype bf16 --steps 10 --warmup 2 --no-cpu-baseline --no-conv-search > $OUT/prof_c3_stated.log 2>&1 || exit 2

@@ -14,8 +14,8 @@ for a in "--batch 2" "--batch 2 --shift 0" "--batch 16 --dtype bf16" "--batch 16
   echo "$a: $(grep -v amdgpu $OUT/wa.log | tail -2 | tr '\n' ' ' | cut -c1-200)"
 done
 for i in 1 2; do
-  timeout -k 10 300 python -u bench.py --no-cpu-baseline > $OUT/bench_c2_$i.log 2>&1 || { tail -5 $OUT/bench_c2_$i.log; exit 4; }
+  timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $OUT/bench_c2_$i.log 2>&1 || { tail -5 $OUT/bench_c2_$i.log; exit 4; }
   echo "c2 $i $(tail -1 $OUT/bench_c2_$i.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["value"],1), d["roofline"]["achieved"], d["roofline"]["frac"], d["roofline"]["avg_launch_ms"])')"
 done
-timeout -k 10 300 python -u bench.py --batch 8 --dense-dtype bf16x3 --attn-dtype bf16 --no-cpu-baseline > $OUT/bench_c3_stated.log 2>&1 || { tail -5 $OUT/bench_c3_stated.log; exit 5; }
+timeout -k 10 300 python -u bench.py --full --batch 8 --dense-dtype bf16x3 --attn-dtype bf16 --no-cpu-baseline > $OUT/bench_c3_stated.log 2>&1 || { tail -5 $OUT/bench_c3_stated.log; exit 5; }
 echo "c3 stated $(tail -1 $OUT/bench_c3_stated.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["value"],1), d["roofline"]["achieved"], d["roofline"]["frac"], d["roofline"]["avg_launch_ms"])')"

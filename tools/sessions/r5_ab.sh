@@ -32,7 +32,7 @@ for i in 1 2; do
     [ $leg = env2 ] && envs="$AB_ENV2"
     [ $leg = env3 ] && envs="$AB_ENV3"
     [ $leg = env ] && [ -z "$AB_ENV" ] && continue
-    env $envs timeout -k 10 300 python -u bench.py --no-cpu-baseline ${BENCH_ARGS} > $OUT/bench_${leg}_$i.log 2>&1 || { tail -5 $OUT/bench_${leg}_$i.log; exit 4; }
+    env $envs timeout -k 10 300 python -u bench.py --full --no-cpu-baseline ${BENCH_ARGS} > $OUT/bench_${leg}_$i.log 2>&1 || { tail -5 $OUT/bench_${leg}_$i.log; exit 4; }
     echo "$leg $i c2 $(tail -1 $OUT/bench_${leg}_$i.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["value"],1), round(d["roofline"]["frac"],4), d["roofline"]["avg_launch_ms"], round(d["roofline_step_dominant"]["ms_per_step"],3))')"
   done
 done

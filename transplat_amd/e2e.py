@@ -173,7 +173,9 @@ def route_label(model, data) -> str:
 
 
 def build_e2e_workload(batch: int, device, scene_offset: int = 0, dense_dtype: str = "fp32", graph: bool = True,
-                       attn_dtype: str = "auto"):
+                       attn_dtype: str = "auto", routes: bool = True):
+    """`routes`: run one more eager step under routes.record() and append what it launched to the
+    workload string (bench.py --full); without it the string states the precision modes only."""
     from .gemm_tuning import use_tuned_gemms
 
     use_tuned_gemms(device, dense_dtype)  # recorded library GEMM solutions (replay only), before any capture
@@ -192,6 +194,8 @@ def build_e2e_workload(batch: int, device, scene_offset: int = 0, dense_dtype: s
         "eager_step": lambda: model.test_step(data),
         "views_per_step": batch * data["target"]["near"].shape[1],
         "workload": f"e2e TranSplat test_step: {batch} scene(s) x (2 ctx -> 3 tgt) 256x256; "
-                    + precision_label(dense_dtype, attn_dtype) + "; launched per step: " + route_label(model, data),
+                    + precision_label(dense_dtype, attn_dtype),
     }
+    if routes:
+        info["workload"] += "; launched per step: " + route_label(model, data)
     return step, info, model
