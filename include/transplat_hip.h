@@ -170,6 +170,22 @@ int tsplat_uv_cross_table_fwd(const float* table, const float* cams, const float
                               const float* logits, float* out, int32_t batch, int32_t height, int32_t width,
                               int32_t channels, int32_t depths, int32_t points, void* stream);
 
+/* Fine cross correlation, fused form: identical semantics to tsplat_uv_cross_fwd, products in
+ * split-bf16 precision (key_hi val_hi + key_hi val_lo + key_lo val_hi on bf16 MFMA, fp32
+ * accumulation -- what the K = 3C bf16 table GEMM computes), without the [H*W, H*W] table: each
+ * workgroup computes the slices of it that its 32 query pixels sample in LDS and gathers there.
+ * tsplat_uv_cross_pack_fwd splits value [2*batch, H*W, C] (un-flipped, as for tsplat_uv_cross_fwd)
+ * into the MFMA operand image `packed` of tsplat_uv_cross_pack_bytes(batch, H, W) bytes, which
+ * tsplat_uv_cross_fused_fwd reads in place of value. C must be 128, points <= 8; value, packed,
+ * key, offsets and logits 16-byte aligned. Deterministic (no atomics). */
+size_t tsplat_uv_cross_pack_bytes(int32_t batch, int32_t height, int32_t width);
+int tsplat_uv_cross_pack_fwd(const float* value, void* packed, int32_t batch, int32_t height, int32_t width,
+                             int32_t channels, void* stream);
+int tsplat_uv_cross_fused_fwd(const void* packed, const float* key, const float* cams, const float* disp,
+                              const float* offsets, const float* logits, float* out, int32_t batch,
+                              int32_t height, int32_t width, int32_t channels, int32_t depths, int32_t points,
+                              void* stream);
+
 /* Single-level single-head multi-scale deformable attention (mmcv ms_deform_attn_forward with
  * num_levels = num_heads = 1): out[i, q] = sum_pt weights[i, q, pt] * bilinear(value[i],
  * loc[i, q, pt] * (W, H) - 0.5). value [n, H*W, C], loc [n, queries, points, 2] in [0, 1],

@@ -96,7 +96,8 @@ def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
 
     Two steps: the correlation table G[(b v)] = key_v value_(1-v)^T [HW, HW] as one batched
     fp32 library GEMM (hipBLASLt, MFMA; autocast off so it stays fp32), then
-    tsplat_uv_cross_table_fwd gathers 4 points x 4 bilinear corners of G per (pixel, depth)."""
+    tsplat_uv_cross_table_fwd gathers 4 points x 4 bilinear corners of G per (pixel, depth). In the
+    bf16x3 dense mode the table never reaches memory (uv_cross_fused)."""
     lib = _lib.load()
     b, _, hw, c = value.shape
     d = disp.shape[1]
@@ -114,8 +115,11 @@ def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
             table = torch.bmm(k2, torch.cat((vb, vb), dim=-1).transpose(1, 2), out_dtype=torch.float32)
         value = None
         key, offsets, logits, disp = map(_f32, (key, offsets, logits, disp))
+    elif _DENSE == "bf16x3" and value.is_cuda and c == 128 and _UV_FUSED:
+        # bf16x3 dense mode: the same split-bf16 products computed and gathered on chip, no table
+        return uv_cross_fused(value, key, intr, pose, disp, offsets, logits, h, w)
     elif _DENSE == "bf16x3" and value.is_cuda and c % 4 == 0:
-        # bf16x3 dense mode: the table in split-bf16 precision as ONE hipBLASLt bf16 GEMM with K = 3C,
+        # TSPLAT_UV_FUSED=0 (or C != 128): the table in split-bf16 precision as ONE hipBLASLt bf16 GEMM with K = 3C,
         # [key_hi | key_hi | key_lo] x [val_hi | val_lo | val_hi]^T, fp32 output (47 vs 83 us for the
         # fp32 bmm at b = 1, and vs 104 us on tsplat_linear_bf16x3_fwd, profiles/r4/split_gemm2.log;
         # <= 3 * 2^-18 relative per product)
@@ -134,6 +138,28 @@ def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
     rc = lib.tsplat_uv_cross_table_fwd(_lib.ptr(table), _lib.ptr(cams), _lib.ptr(disp), _lib.ptr(offsets),
                                        _lib.ptr(logits), _lib.ptr(out), b, h, w, c, d, p, _lib.stream_ptr(table.device))
     _lib.check(rc, "tsplat_uv_cross_table_fwd")
+    return out
+
+
+def uv_cross_fused(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
+    """uv_cross in split-bf16 precision without the [HW, HW] table: tsplat_uv_cross_pack_fwd splits
+    value of both views into the MFMA operand image (one launch, in place of the flip and the two
+    splits), tsplat_uv_cross_fused_fwd computes each 32-query block's slices of the table in LDS
+    and gathers there, skipping the slices nobody samples. C = 128."""
+    lib = _lib.load()
+    b, _, hw, c = value.shape
+    d = disp.shape[1]
+    p = logits.shape[-1] // d
+    value, key, offsets, logits, disp = map(_f32, (value, key, offsets, logits, disp))
+    cams = pack_cameras(intr, pose)
+    packed = torch.empty(int(lib.tsplat_uv_cross_pack_bytes(b, h, w)), dtype=torch.uint8, device=value.device)
+    stream = _lib.stream_ptr(value.device)
+    _lib.check(lib.tsplat_uv_cross_pack_fwd(_lib.ptr(value), _lib.ptr(packed), b, h, w, c, stream),
+               "tsplat_uv_cross_pack_fwd")
+    out = torch.empty((b * 2, hw, d), dtype=torch.float32, device=value.device)
+    rc = lib.tsplat_uv_cross_fused_fwd(_lib.ptr(packed), _lib.ptr(key), _lib.ptr(cams), _lib.ptr(disp),
+                                       _lib.ptr(offsets), _lib.ptr(logits), _lib.ptr(out), b, h, w, c, d, p, stream)
+    _lib.check(rc, "tsplat_uv_cross_fused_fwd")
     return out
 
 
@@ -296,6 +322,8 @@ _BF16_NORMS = os.environ.get("TSPLAT_BF16_NORMS", "1") != "0"  # A/B knob: bf16-
 _CAT_RES = os.environ.get("TSPLAT_GN_CAT_RES", "1") != "0"  # A/B knob: concatenated residuals read in place
 BF16_NORMS = _BF16_NORMS
 _UV_TABLE_BF16 = os.environ.get("TSPLAT_UV_TABLE_BF16", "1") != "0"  # A/B knob: split-bf16 table GEMM (C3)
+# A/B knob: the fused fine cross correlation (uv_cross_fused) in the bf16x3 dense mode; 0 = the table route
+_UV_FUSED = os.environ.get("TSPLAT_UV_FUSED", "1") != "0"
 
 
 def group_norm(x, num_groups: int, weight, bias, eps: float, act: str = "none", residual=None, pre_bias=None):

@@ -74,7 +74,7 @@ class EncoderTransCfg:
     # fp32 accumulation -- the stand-in for the reference's TF32, src/main.py:15, more precise than
     # it; kernels.dense_precision) or "bf16" (autocast). The rasterizer and the correlation gathers
     # always run fp32; the fine-cross correlation TABLE is a dense GEMM and follows dense_dtype
-    # (bf16x3: one split-bf16 hipBLASLt GEMM over K' = 3K, kernels.uv_cross).
+    # (bf16x3: the same split-bf16 products computed and gathered on chip, kernels.uv_cross_fused).
     dense_dtype: str = "fp32"
     # Window attention (T2): "auto" (bf16 MFMA under bf16 dense layers, bf16x3 under bf16x3 ones,
     # else exact fp32; kernels.auto_attention), "fp32", "bf16x3" or "bf16" (config C3 as

@@ -53,6 +53,7 @@ _HIP = {
     "tsplat_uv_coarse_fwd": ("correlation (HIP)", "fp32"),
     "tsplat_uv_cross_table_fwd": ("correlation (HIP)", "fp32"),
     "tsplat_uv_cross_fwd": ("correlation (HIP)", "fp32"),
+    "tsplat_uv_cross_fused_fwd": ("correlation (HIP)", "bf16x3 products, fp32 gather"),
     "tsplat_msda_fwd": ("correlation (HIP)", "fp32"),
     "tsplat_msda_raw_fwd": ("correlation (HIP)", "fp32"),
     "tsplat_ms_deform_attn_fwd": ("correlation (HIP)", "fp32"),
