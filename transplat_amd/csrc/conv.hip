@@ -22,14 +22,13 @@
 // 8-16 pairs of a 1x1) at a time with the next batch's loads in flight; the ksplit partial tiles are
 // summed through LDS, the bias added, and the tile stored (lanes = consecutive pixels).
 #include "common.h"
+#include "mfma.h"
 #include "prof.h"
 
 namespace tsplat {
 namespace conv {
 
 constexpr int kMaxWaves = 16;
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct Args {
     const float* x1;
@@ -256,14 +255,6 @@ __global__ void __launch_bounds__(1024) conv_f32_kernel(Args p) {
 // fragments, two 16-B loads), splits the 8 values into hi / lo bf16 and issues the 3 MFMAs. Weights
 // packed on the host as [co tile][tap][group][hi, lo][64 lanes][8] bf16 (lane l: cout 32 cot + (l & 31),
 // channels 16 g + 8 (l >> 5) + j; zero past cin / cout). Epilogue as the fp32 kernel's.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((floatx2){a, b}, bf16x2));
-}
-
 template <int KS, int S, int UP, int NB>
 __global__ void __launch_bounds__(1024) conv_x3_kernel(Args p) {
     extern __shared__ float sred[];  // [ksplit][16][64]
@@ -337,12 +328,7 @@ __global__ void __launch_bounds__(1024) conv_x3_kernel(Args p) {
         for (int k = 0; k < NB; ++k) {
             uint32_t hi[4], lo[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float a = xv[k][2 * q], b = xv[k][2 * q + 1];
-                hi[q] = pack_bf16(a, b);
-                const float ah_ = __uint_as_float(hi[q] << 16), bh_ = __uint_as_float(hi[q] & 0xffff0000u);
-                lo[q] = pack_bf16(a - ah_, b - bh_);
-            }
+            for (int q = 0; q < 4; ++q) split_pair(xv[k][2 * q], xv[k][2 * q + 1], hi[q], lo[q]);
             const bf16x8 bh = __builtin_bit_cast(bf16x8, make_uint4(hi[0], hi[1], hi[2], hi[3]));
             const bf16x8 bl = __builtin_bit_cast(bf16x8, make_uint4(lo[0], lo[1], lo[2], lo[3]));
             const bf16x8 wh = __builtin_bit_cast(bf16x8, ah[k]), wl = __builtin_bit_cast(bf16x8, al[k]);

@@ -31,12 +31,10 @@
 #include <string.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace tsplat {
 namespace convbf16 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int kThreads = 256;
 constexpr int kMaxSrc = 4;
@@ -58,11 +56,9 @@ struct Args {
                     // the register-blocked form (C3 1019 -> 1062 views/s, profiles/r3/convbf16)
 };
 
+// mfma.h's activate() but for the SiLU on __expf (activate() has expf, which groupnorm.hip's bits rest on)
 __device__ __forceinline__ float act_fn(float v, int act) {
-    if (act == 1) return v / (1.0f + __expf(-v));                       // SiLU
-    if (act == 2) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));  // GELU (erf)
-    if (act == 3) return fmaxf(v, 0.0f);                                  // ReLU
-    return v;
+    return act == 1 ? v / (1.0f + __expf(-v)) : activate(v, act);
 }
 
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {

@@ -24,13 +24,11 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 #include "prof.h"
 
 namespace tsplat {
 namespace convfew {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int kMaxSrc = 6;
 constexpr int kCols = 64;            // output columns per workgroup
@@ -54,12 +52,6 @@ struct Args {
     int rb, cb;          // row / column blocks per image
     int abl;             // diagnostics only (TSPLAT_FEW_ABL): 1 no input loads, 2 no MFMAs, 4 no stores
 };
-
-__device__ __forceinline__ float act_fn(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.0f);
-    if (act == 2) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-    return v;
-}
 
 // plane of input channel c (concatenated sources), or null past the last channel; the source loop is
 // unrolled so every a.src[q] / a.cs[q] is a constant kernel-argument offset (a runtime index into the
@@ -137,8 +129,7 @@ __global__ void __launch_bounds__(256, 2) conv_kernel(Args a) {
                 const float* p = sPlane[min(c0 + j, kMaxCi - 1)] + po;
                 // global address space: a pointer read from LDS would otherwise be a flat load, which
                 // also counts against the LDS counter
-                typedef float f4v __attribute__((ext_vector_type(4)));
-                const f4v f = *(const __attribute__((address_space(1))) f4v*)p;
+                const floatx4 f = *(const __attribute__((address_space(1))) floatx4*)p;
                 v[k][j] = ok ? make_float4(f.x, f.y, f.z, f.w) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
@@ -239,8 +230,8 @@ __global__ void __launch_bounds__(256, 2) conv_kernel(Args a) {
         const size_t off = ((size_t)img * a.co + o) * hw + (size_t)yy * a.w + xx;
         float4 v = *reinterpret_cast<const float4*>(&sOut[(col * TR + i) * kCols + 4 * c4]);
         const float bb = a.bias ? a.bias[o] : 0.0f;
-        v = make_float4(act_fn(v.x + bb, a.act), act_fn(v.y + bb, a.act), act_fn(v.z + bb, a.act),
-                        act_fn(v.w + bb, a.act));
+        v = make_float4(conv_act(v.x + bb, a.act), conv_act(v.y + bb, a.act), conv_act(v.z + bb, a.act),
+                        conv_act(v.w + bb, a.act));
         if (a.res) {
             const float4 r = *reinterpret_cast<const float4*>(a.res + off);
             v = make_float4(v.x + r.x, v.y + r.y, v.z + r.z, v.w + r.w);

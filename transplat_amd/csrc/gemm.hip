@@ -29,17 +29,13 @@
 //   * XCD-aware order: the workgroups of one column block (same W slice) are dealt to one XCD;
 //   * the output tile goes through LDS and is stored as whole 512-B rows.
 #include "common.h"
+#include "mfma.h"
 #include "prof.h"
 
 namespace tsplat {
 namespace gemm3 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) f4v* gptr;  // global loads (not flat)
+typedef const __attribute__((address_space(1))) floatx4* gptr;  // global loads (not flat)
 
 #ifndef TSPLAT_GEMM_WKMAJOR
 #define TSPLAT_GEMM_WKMAJOR 1  // packed W k-step-major: a k-step's n-tiles adjacent
@@ -80,22 +76,12 @@ __device__ unsigned long long* g_gemm_stamps = nullptr;
 #define G_STAMP(slot) do {} while (0)
 #endif
 
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((floatx2){a, b}, bf16x2));
-}
-
-// hi / lo bf16 halves of (a, b), each pair packed into one dword (a in the low half)
-__device__ __forceinline__ void split_pair(float a, float b, uint32_t& hi, uint32_t& lo) {
-    hi = pack_bf16(a, b);
-    const float ah = __builtin_bit_cast(float, hi << 16), bh = __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = pack_bf16(a - ah, b - bh);
-}
-
 // GELU with erf from Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7 absolute, branch-free: one
 // reciprocal, one exp2, five FMAs): the device library's erff (ranges, branches) made fc1's epilogue
 // 4.8 of its 23.5 us (tools/gemm_stamps.py). The difference to the exact erf is below the bf16x3
-// products' own rounding (~4e-6 relative).
-__device__ __forceinline__ float gelu_erf(float v) {
+// products' own rounding (~4e-6 relative). Not mfma.h's gelu_erf (the exact erff), on purpose: hence
+// the other name.
+__device__ __forceinline__ float gelu_erf_poly(float v) {
     const float z = fabsf(v) * 0.70710678118654752f;
     const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
     float p = fmaf(1.061405429f, t, -1.453152027f);
@@ -200,7 +186,7 @@ __global__ void __launch_bounds__(kThreads, 2 / KG) gemm_x3_kernel(Args a) {
 #pragma unroll
         for (int i = 0; i < kXr; ++i) {
             const float* p = rok[i] && kok ? xrow[i] + c * kBK : reinterpret_cast<const float*>(&g_zero16);
-            const f4v v = *(gptr)p;
+            const floatx4 v = *(gptr)p;
             xr[decltype(X)::value][i] = make_float4(v.x, v.y, v.z, v.w);
         }
     };
@@ -351,7 +337,8 @@ __global__ void __launch_bounds__(kThreads, 2 / KG) gemm_x3_kernel(Args a) {
             v.z += bb.z;
             v.w += bb.w;
         }
-        if (a.act == 1) v = make_float4(gelu_erf(v.x), gelu_erf(v.y), gelu_erf(v.z), gelu_erf(v.w));
+        if (a.act == 1)
+            v = make_float4(gelu_erf_poly(v.x), gelu_erf_poly(v.y), gelu_erf_poly(v.z), gelu_erf_poly(v.w));
         if (a.act == 2) {  // hi / lo bf16 images [m][n] at out and out + m n bf16 (the x3 MHA's operands)
             uint32_t h0, l0, h1, l1;
             split_pair(v.x, v.y, h0, l0);

@@ -11,6 +11,7 @@
 // normalises its chunk with the activation and optional residual fused: x is read twice (the
 // second time mostly from L2/MALL), y written once.
 #include "common.h"
+#include "mfma.h"
 #include "prof.h"
 
 namespace tsplat {
@@ -51,19 +52,18 @@ __device__ __forceinline__ Welford wave_reduce(Welford w) {
 // activation I/O: fp32, or bf16 (config C3's bf16 dense layers: the convolutions around the norm
 // read and write bf16, so the norm takes bf16 in and gives bf16 out, computing in fp32 -- the
 // reference's GroupNorm32 normalises x.float() and casts back to x's dtype)
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const __bf16* p) { return (float)*p; }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(__bf16* p, float v) { *p = (__bf16)v; }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 ld4(const __bf16* p) {
-    const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(p);
+    const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
     return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
 }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ void st4(__bf16* p, float4 v) {
-    *reinterpret_cast<bf16x4_t*>(p) = bf16x4_t{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
+    *reinterpret_cast<bf16x4*>(p) = bf16x4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
 }
 
 // Welford over this workgroup's chunk -> partials[seg * S + chunk] = (mean, M2)
@@ -106,14 +106,6 @@ stats_kernel(const T* __restrict__ x, const float* __restrict__ pb, float2* __re
         for (int i = 1; i < kThreads / kWave; ++i) t = combine(t, sw[i]);
         partials[(int64_t)seg * S + chunk] = make_float2(t.mean, t.m2);
     }
-}
-
-template <int ACT>
-__device__ __forceinline__ float activate(float v) {
-    if (ACT == 1) return v / (1.0f + expf(-v));                     // SiLU
-    if (ACT == 2) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));  // GELU (erf)
-    if (ACT == 3) return fmaxf(v, 0.0f);                             // ReLU
-    return v;
 }
 
 // after the residual add: ACT 3 is the UniMatch ResidualBlock ending relu(x + relu(norm(y)))
@@ -173,10 +165,10 @@ apply_kernel(const T* __restrict__ x, const float* __restrict__ pb, const float2
                 v.y += b;
                 v.z += b;
                 v.w += b;
-                v.x = activate<ACT>(v.x * sc + sh);
-                v.y = activate<ACT>(v.y * sc + sh);
-                v.z = activate<ACT>(v.z * sc + sh);
-                v.w = activate<ACT>(v.w * sc + sh);
+                v.x = activate(v.x * sc + sh, ACT);
+                v.y = activate(v.y * sc + sh, ACT);
+                v.z = activate(v.z * sc + sh, ACT);
+                v.w = activate(v.w * sc + sh, ACT);
                 if (RES) {
                     const float4 r = ld4(res_at(res, res2, c1, C, base + i, seg / G, c, HW));
                     v.x = post_residual<ACT>(v.x + r.x);
@@ -191,7 +183,7 @@ apply_kernel(const T* __restrict__ x, const float* __restrict__ pb, const float2
         for (int i = tid; i < n_local; i += kThreads) {
             const int c = g * cpg + (int)((start + i) / HW);
             const float sc = rstd * gamma[c];
-            float v = activate<ACT>((ld1(x + base + i) + (pb ? pb[c] : 0.f)) * sc + (beta[c] - sc * mean));
+            float v = activate((ld1(x + base + i) + (pb ? pb[c] : 0.f)) * sc + (beta[c] - sc * mean), ACT);
             if (RES) v = post_residual<ACT>(v + ld1(res_at(res, res2, c1, C, base + i, seg / G, c, HW)));
             st1(y + base + i, v);
         }
@@ -261,10 +253,10 @@ fused_kernel(const T* __restrict__ x, const float* __restrict__ pb, const float*
             const int c = g * cpg + i / HW;
             const float sc = rstd * gamma[c], sh = beta[c] - sc * mean;
             float4 o;
-            o.x = activate<ACT>(v[k].x * sc + sh);
-            o.y = activate<ACT>(v[k].y * sc + sh);
-            o.z = activate<ACT>(v[k].z * sc + sh);
-            o.w = activate<ACT>(v[k].w * sc + sh);
+            o.x = activate(v[k].x * sc + sh, ACT);
+            o.y = activate(v[k].y * sc + sh, ACT);
+            o.z = activate(v[k].z * sc + sh, ACT);
+            o.w = activate(v[k].w * sc + sh, ACT);
             if (RES) {
                 const float4 r = ld4(res_at(res, res2, c1, cpg * G, base + i, seg / G, c, HW));
                 o.x = post_residual<ACT>(o.x + r.x);
@@ -412,10 +404,10 @@ bias_act_kernel(const float* __restrict__ x, const float* __restrict__ bias, con
     const int c = (i / hw4) % C;
     const float b = bias ? bias[c] : 0.f;
     float4 v = reinterpret_cast<const float4*>(x)[i];
-    v.x = activate<ACT>(v.x + b);
-    v.y = activate<ACT>(v.y + b);
-    v.z = activate<ACT>(v.z + b);
-    v.w = activate<ACT>(v.w + b);
+    v.x = activate(v.x + b, ACT);
+    v.y = activate(v.y + b, ACT);
+    v.z = activate(v.z + b, ACT);
+    v.w = activate(v.w + b, ACT);
     if (RES) {
         const float4 r = reinterpret_cast<const float4*>(res)[i];
         v.x = post_residual<ACT>(v.x + r.x);
@@ -475,10 +467,10 @@ bias_act_nhwc_kernel(const float* __restrict__ x, const float* __restrict__ bias
         v.z += b.z;
         v.w += b.w;
     }
-    v.x = activate<ACT>(v.x);
-    v.y = activate<ACT>(v.y);
-    v.z = activate<ACT>(v.z);
-    v.w = activate<ACT>(v.w);
+    v.x = activate(v.x, ACT);
+    v.y = activate(v.y, ACT);
+    v.z = activate(v.z, ACT);
+    v.w = activate(v.w, ACT);
     if (NRES >= 1) {
         const float4 r = reinterpret_cast<const float4*>(r1)[i];
         v.x += r.x;

@@ -19,6 +19,7 @@
 // and a 4-wave LDS exchange. K is walked in 64-wide chunks staged through LDS (rows XOR-swizzled
 // per 16-B chunk, ping-pong buffers) with two register stages in flight (see linear_f32_kernel).
 #include "common.h"
+#include "mfma.h"
 #include "prof.h"
 
 namespace tsplat {
@@ -36,11 +37,6 @@ enum Flags : int {
     kXBf16 = 512,    // x1 is bf16 (widened exactly as it is staged; no x2)
     kOutBf16 = 1024, // the output is written as bf16 (round to nearest even; no residual)
 };
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct Args {
     const float* x1;
@@ -144,13 +140,12 @@ __device__ __forceinline__ void stage_load(const Args& a, int m0, int n0, int K,
         const float* xs = first ? a.x1 : a.x2;
         const int ld = first ? a.k1 : a.k2, kk = first ? k0 : k0 - a.k1;
         if (a.flags & kXBf16) {  // x1 bf16: 4 channels = 8 B, widened exactly
-            typedef __bf16 bf16x4l __attribute__((ext_vector_type(4)));
             const __bf16* xb = reinterpret_cast<const __bf16*>(a.x1);
 #pragma unroll
             for (int i = 0; i < BM / 32; ++i) {
                 const int m = m0 + srow + 32 * i;
                 st.x[i] = m < a.M ? __builtin_convertvector(
-                                        *reinterpret_cast<const bf16x4l*>(xb + (size_t)m * a.k1 + k0 + 4 * sq), floatx4)
+                                        *reinterpret_cast<const bf16x4*>(xb + (size_t)m * a.k1 + k0 + 4 * sq), floatx4)
                                   : (floatx4)(0.f);
             }
         } else {
@@ -166,12 +161,10 @@ __device__ __forceinline__ void stage_load(const Args& a, int m0, int n0, int K,
         st.w[i] = *reinterpret_cast<const floatx4*>(a.w + (size_t)(n0 + srow + 32 * i) * K + k0 + 4 * sq);
 }
 
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // bf16x3 staging: a 256-B row holds the chunk's 64 channels as [hi: 8 units of 8 bf16 | lo: 8 units],
 // 16-B unit u at slot u ^ (row & 15) (the fp32 image's swizzle); fp32 unit sq (channels 4 sq ..
 // 4 sq + 3) is the (sq & 1) half of bf16 unit sq >> 1
+// (the split rule of mfma.h as 4-wide vector converts; not split_pair: other device code)
 __device__ __forceinline__ void store_split(char* base, int r, int sq, floatx4 v) {
     const bf16x4 hi = __builtin_convertvector(v, bf16x4);
     const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, floatx4), bf16x4);
@@ -431,34 +424,32 @@ linear_f32_kernel(Args a) {
     }
     if (!active || m >= a.M) return;
     if ((a.flags & kSplit) && a.x3_from >= 0 && nb / kBN >= a.x3_from) {
-        typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
         const size_t blk = (size_t)(nb / kBN - a.x3_from) * 2;
         __bf16* hi = a.kv_x3 + blk * a.M * kBN + (size_t)m * kBN + nb % kBN;
         __bf16* lo = hi + (size_t)a.M * kBN;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            bf16x4v vh, vl;
+            bf16x4 vh, vl;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 vh[j] = (__bf16)y[4 * u + j];
                 vl[j] = (__bf16)(y[4 * u + j] - (float)vh[j]);
             }
-            *reinterpret_cast<bf16x4v*>(hi + 8 * u) = vh;
-            *reinterpret_cast<bf16x4v*>(lo + 8 * u) = vl;
+            *reinterpret_cast<bf16x4*>(hi + 8 * u) = vh;
+            *reinterpret_cast<bf16x4*>(lo + 8 * u) = vl;
         }
         return;
     }
     if (a.flags & kOutBf16) {  // bf16 output (same layouts; split_stride in elements)
-        typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
         __bf16* ob = reinterpret_cast<__bf16*>(a.out) +
                      ((a.flags & kSplit) ? (size_t)(nb / kBN) * a.split_stride + (size_t)m * kBN + nb % kBN
                                          : (size_t)m * a.N + nb);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            bf16x4v vh;
+            bf16x4 vh;
 #pragma unroll
             for (int j = 0; j < 4; ++j) vh[j] = (__bf16)y[4 * u + j];
-            *reinterpret_cast<bf16x4v*>(ob + 8 * u) = vh;
+            *reinterpret_cast<bf16x4*>(ob + 8 * u) = vh;
         }
         return;
     }

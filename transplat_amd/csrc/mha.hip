@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "mfma.h"
 #include "prof.h"
 
 namespace tsplat {
@@ -26,9 +27,6 @@ constexpr int kQW = 32;  // queries per workgroup (one MFMA tile)
 constexpr int kKT = 32;  // keys per tile
 constexpr int kThreads = 256;
 constexpr float kLog2e = 1.4426950408889634f;
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float halves_max(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
@@ -526,10 +524,10 @@ mha16_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int N, 
 //     B = the lane's own 4 probabilities, split) x 3 terms, instead of 16 fp32 MFMAs.
 // Same operand / output maps, softmax and merge as mha16_f32_kernel; the biases live in the split
 // image (q's scaled by scale * log2 e in registers after re-joining hi + lo exactly).
+// (the split rule of mfma.h written as vector converts, here and in the kernel, as in linear.hip)
 __global__ void __launch_bounds__(256) split_qkv_kernel(const float4* __restrict__ x, const float* __restrict__ bias,
                                                         int cols4, int64_t n4, uint2* __restrict__ hi,
                                                         uint2* __restrict__ lo) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         float4 v = x[i];
         if (bias) {
@@ -546,10 +544,6 @@ __global__ void __launch_bounds__(256) split_qkv_kernel(const float4* __restrict
         lo[i] = __builtin_bit_cast(uint2, l);
     }
 }
-
-typedef __bf16 bf16x8m __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4m __attribute__((ext_vector_type(4)));
-typedef short shortx4m __attribute__((ext_vector_type(4)));
 
 template <int W>
 __global__ void __launch_bounds__(W * 64)
@@ -577,22 +571,22 @@ mha16_x3_kernel(const __bf16* __restrict__ qh_img, const __bf16* __restrict__ ql
     const int q = qblk * 16 + c;
 
     // this lane's query row, dims 16 g .. 16 g + 15: re-joined (exact), scaled, split again
-    bf16x8m qh[2], ql[2];
+    bf16x8 qh[2], ql[2];
     {
         const float qs = scale * kLog2e;
         const size_t qo = off0 + (size_t)min(q, N - 1) * tok + 16 * g;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-            const bf16x8m h = *reinterpret_cast<const bf16x8m*>(qh_img + qo + 8 * s2);
-            const bf16x8m l = *reinterpret_cast<const bf16x8m*>(ql_img + qo + 8 * s2);
+            const bf16x8 h = *reinterpret_cast<const bf16x8*>(qh_img + qo + 8 * s2);
+            const bf16x8 l = *reinterpret_cast<const bf16x8*>(ql_img + qo + 8 * s2);
             typedef float floatx8 __attribute__((ext_vector_type(8)));
             const floatx8 f = (__builtin_convertvector(h, floatx8) + __builtin_convertvector(l, floatx8)) * qs;
-            qh[s2] = __builtin_convertvector(f, bf16x8m);
-            ql[s2] = __builtin_convertvector(f - __builtin_convertvector(qh[s2], floatx8), bf16x8m);
+            qh[s2] = __builtin_convertvector(f, bf16x8);
+            ql[s2] = __builtin_convertvector(f - __builtin_convertvector(qh[s2], floatx8), bf16x8);
         }
     }
     struct TileX3 {
-        bf16x8m kh[2], kl[2];      // K[key c][16 g + 8 s .. + 7]
+        bf16x8 kh[2], kl[2];      // K[key c][16 g + 8 s .. + 7]
         __bf16 vh[16], vl[16];     // V[key 4 g + t][16 dt + c] at t * 4 + dt
     };
     auto load_tile = [&](int tile, TileX3& T) {
@@ -600,8 +594,8 @@ mha16_x3_kernel(const __bf16* __restrict__ qh_img, const __bf16* __restrict__ ql
         const size_t ko = (size_t)min(k0 + c, N - 1) * tok + 16 * g;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-            T.kh[s2] = *reinterpret_cast<const bf16x8m*>(kh_b + ko + 8 * s2);
-            T.kl[s2] = *reinterpret_cast<const bf16x8m*>(kl_b + ko + 8 * s2);
+            T.kh[s2] = *reinterpret_cast<const bf16x8*>(kh_b + ko + 8 * s2);
+            T.kl[s2] = *reinterpret_cast<const bf16x8*>(kl_b + ko + 8 * s2);
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -651,14 +645,14 @@ mha16_x3_kernel(const __bf16* __restrict__ qh_img, const __bf16* __restrict__ ql
             bsum += s[i];
         }
         l_run += halves_sum(rows_sum(bsum));
-        const bf16x4m ph = __builtin_convertvector(s, bf16x4m);
-        const bf16x4m pl = __builtin_convertvector(s - __builtin_convertvector(ph, floatx4), bf16x4m);
-        const shortx4m phs = __builtin_bit_cast(shortx4m, ph), pls = __builtin_bit_cast(shortx4m, pl);
+        const bf16x4 ph = __builtin_convertvector(s, bf16x4);
+        const bf16x4 pl = __builtin_convertvector(s - __builtin_convertvector(ph, floatx4), bf16x4);
+        const shortx4 phs = __builtin_bit_cast(shortx4, ph), pls = __builtin_bit_cast(shortx4, pl);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-            const bf16x4m vh4 = {cur.vh[dt], cur.vh[4 + dt], cur.vh[8 + dt], cur.vh[12 + dt]};
-            const bf16x4m vl4 = {cur.vl[dt], cur.vl[4 + dt], cur.vl[8 + dt], cur.vl[12 + dt]};
-            const shortx4m vhs = __builtin_bit_cast(shortx4m, vh4), vls = __builtin_bit_cast(shortx4m, vl4);
+            const bf16x4 vh4 = {cur.vh[dt], cur.vh[4 + dt], cur.vh[8 + dt], cur.vh[12 + dt]};
+            const bf16x4 vl4 = {cur.vl[dt], cur.vl[4 + dt], cur.vl[8 + dt], cur.vl[12 + dt]};
+            const shortx4 vhs = __builtin_bit_cast(shortx4, vh4), vls = __builtin_bit_cast(shortx4, vl4);
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(vls, phs, o[dt], 0, 0, 0);
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(vhs, pls, o[dt], 0, 0, 0);
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(vhs, phs, o[dt], 0, 0, 0);

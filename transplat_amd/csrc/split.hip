@@ -10,6 +10,9 @@
 namespace tsplat {
 namespace split {
 
+// the split rule of mfma.h (hi = bf16(x), lo = bf16(x - hi), low half first) in scalar converts and
+// bit arithmetic, written out in both kernels: with split_pair, or with one shared helper for the
+// two, the compiler emits other device code, so this form stays
 __device__ __forceinline__ uint32_t bits(float v) { return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)v); }
 
 // one thread = 4 consecutive elements of a row (k % 4 == 0): one float4 in, three 8-B stores out

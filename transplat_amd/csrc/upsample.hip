@@ -13,16 +13,10 @@
 // (4 consecutive output columns per thread) -- instead of the interpolation kernel plus a separate
 // GELU pass over the full-resolution map.
 #include "common.h"
+#include "mfma.h"
 
 namespace tsplat {
 namespace upsample {
-
-template <int ACT>
-__device__ __forceinline__ float act(float v) {
-    if (ACT == 2) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));  // GELU (erf)
-    if (ACT == 3) return fmaxf(v, 0.f);
-    return v;
-}
 
 template <int ACT>
 __global__ void __launch_bounds__(256) bilinear_ac_kernel(const float* __restrict__ x, const float* __restrict__ bias,
@@ -52,7 +46,7 @@ __global__ void __launch_bounds__(256) bilinear_ac_kernel(const float* __restric
         const int w1 = w0 + (w0 < w - 1 ? 1 : 0);
         const float m1 = wr - (float)w0, m0 = 1.f - m1;
         const float v = l0 * (m0 * r0[w0] + m1 * r0[w1]) + l1 * (m0 * r1[w0] + m1 * r1[w1]);
-        out[j] = act<ACT>(v + b);
+        out[j] = activate(v + b, ACT);
     }
     *reinterpret_cast<float4*>(y + (size_t)rowi * wo + ox0) = make_float4(out[0], out[1], out[2], out[3]);
 }

@@ -22,16 +22,12 @@
 // No atomics and no cross-workgroup state: a pair accumulates its bands in ascending order in its
 // own LDS slot, so the result is the same bit for bit from launch to launch.
 #include "common.h"
+#include "mfma.h"
 #include "corr_geo.h"
 #include "prof.h"
 
 namespace tsplat {
 namespace corr {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kQ = 32;                  // query pixels per workgroup: one MFMA M tile
 constexpr int kBand = 512;              // value pixels per band
@@ -54,6 +50,7 @@ __device__ int* g_uvx_bands = nullptr;
 #endif
 
 // (hi, lo) bf16 halves of 8 floats, hi = bf16(x), lo = bf16(x - hi), as two 16-B fragments
+// (the split rule of mfma.h as 4-wide vector converts; not split_pair: other device code)
 __device__ __forceinline__ void split8(floatx4 a, floatx4 b, uint4& hi, uint4& lo) {
     const bf16x4 ah = __builtin_convertvector(a, bf16x4), bh = __builtin_convertvector(b, bf16x4);
     const bf16x4 al = __builtin_convertvector(a - __builtin_convertvector(ah, floatx4), bf16x4);

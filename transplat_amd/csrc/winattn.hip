@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "mfma.h"
 #include "prof.h"
 
 namespace tsplat {
@@ -93,8 +94,6 @@ constexpr int kBQ = 64;          // queries per workgroup
 constexpr int kBK = 64;          // keys per LDS tile
 constexpr int kThreads = 256;
 constexpr int kVStride = kC + 4;  // padded V row (floats)
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct Params {
     int H, W, splits, shift, m, L;  // L = window pixels; shift != 0: shifted (masked) layer
@@ -346,7 +345,6 @@ win_attn_f32_kernel(Params p, const float* __restrict__ q, const float* __restri
 // workgroups for the 2-view map: the partials are the only HBM/MALL traffic of the split)
 __device__ __forceinline__ void store4(float* dst, float4 v) { *reinterpret_cast<float4*>(dst) = v; }
 __device__ __forceinline__ void store4(__bf16* dst, float4 v) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
     *reinterpret_cast<bf16x4*>(dst) = bf16x4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
 }
 
@@ -438,8 +436,6 @@ win_attn_combine_x32_kernel(Params p, Partials part, OutT* __restrict__ out) {
 constexpr int kQW = 32;              // queries per wave
 constexpr int kBQ3 = 4 * kQW;        // queries per workgroup
 constexpr int kVtStride = kBK + 4;   // transposed V row (floats)
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 // Staging is the T14 split of the key-pair kernel below: K(t+1) is loaded into registers during
 // QK(t) and stored after the barrier that retires K(t); the same registers then carry V(t+1)
@@ -598,15 +594,14 @@ win_attn_f32x32_kernel(Params p, const float* __restrict__ q, const float* __res
             m_run = m_new;
         }
         // s - m and the row sum on packed pairs (v_pk_add_f32: half the issue slots)
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        const f2v nm2 = {-m_run, -m_run};
-        f2v bsum2 = {0.f, 0.f};
+        const floatx2 nm2 = {-m_run, -m_run};
+        floatx2 bsum2 = {0.f, 0.f};
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
-                const f2v arg = (f2v){s[sub][r], s[sub][r + 1]} + nm2;
-                const f2v e = {fast_exp2(arg.x), fast_exp2(arg.y)};
+                const floatx2 arg = (floatx2){s[sub][r], s[sub][r + 1]} + nm2;
+                const floatx2 e = {fast_exp2(arg.x), fast_exp2(arg.y)};
                 s[sub][r] = e.x;
                 s[sub][r + 1] = e.y;
                 bsum2 += e;
@@ -671,11 +666,8 @@ win_attn_f32x32_kernel(Params p, const float* __restrict__ q, const float* __res
     WA_STAMP(13, wall_clock64());
 }
 
-
 // ============================================================================================
-// bf16 operand types (the v2 / v3 kernels below)
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+// bf16 operands (the v2 / v3 kernels below)
 constexpr int kVtStrideH = kBK + 8;  // transposed V row (bf16 elements)
 
 // ============================================================================================
@@ -707,9 +699,6 @@ constexpr float kMaskBonus = 1128.0f;    // bf16-exact; x 1/sqrt(128) = 99.7 (re
 __device__ __forceinline__ int vimg_off(int r, int ch) {
     return 256 * r + 16 * (ch ^ (((r & 3) << 2) | ((r >> 2) & 3)));
 }
-
-typedef short shortx4 __attribute__((ext_vector_type(4)));
-
 
 __global__ void __launch_bounds__(kThreads, 2)
 win_attn_bf16_v2_kernel(Params p, const __bf16* __restrict__ q, const __bf16* __restrict__ k,
@@ -870,7 +859,6 @@ win_attn_bf16_v2_kernel(Params p, const __bf16* __restrict__ q, const __bf16* __
                     (__attribute__((address_space(3))) shortx4*)(sV + vimg_off(r0, c0) + 8 * (pp & 1)));
                 const shortx4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
                     (__attribute__((address_space(3))) shortx4*)(sV + vimg_off(r0 + 8, c0) + 8 * (pp & 1)));
-                typedef short shortx8 __attribute__((ext_vector_type(8)));
                 const shortx8 vs = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 if (kAbl2 == 2) { o[dt][0] += (float)pf[0] + (float)vs[0]; continue; }
                 o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vs), pf, o[dt], 0, 0, 0);
@@ -1078,7 +1066,6 @@ win_attn_bf16_v3_kernel(Params p, const __bf16* __restrict__ q, const __bf16* __
                         (__attribute__((address_space(3))) shortx4*)(smem + aV[0][dt] + off));
                     const shortx4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
                         (__attribute__((address_space(3))) shortx4*)(smem + aV[1][dt] + off));
-                    typedef short shortx8 __attribute__((ext_vector_type(8)));
                     const shortx8 vs = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                     o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vs), pf[ksx], o[dt], 0,
                                                                     0, 0);
@@ -1184,6 +1171,7 @@ win_attn_bf16_v3_kernel(Params p, const __bf16* __restrict__ q, const __bf16* __
 // Writes the same split-key partials (lane-contiguous O, natural-log m, l) as the exact kernel, so
 // tsplat_linear_f32_attn_merge_fwd combines them in its operand staging unchanged.
 // ============================================================================================
+// the split rule of mfma.h, element by element with scalar casts (not split_pair: other device code)
 __device__ __forceinline__ void split8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -1366,7 +1354,6 @@ win_attn_x3_kernel(Params p, const float* __restrict__ q, const __bf16* __restri
                 const shortx4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(sVh[buf] + a1));
                 const shortx4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(sVl[buf] + a0));
                 const shortx4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(sVl[buf] + a1));
-                typedef short shortx8 __attribute__((ext_vector_type(8)));
                 const shortx8 vh8 = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
                 const shortx8 vl8 = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
                 o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vl8), ph, o[dt], 0, 0, 0);
@@ -1530,20 +1517,19 @@ win_attn_x3_v2_kernel(Params p, const float* __restrict__ q, const __bf16* __res
     {
         unsigned char* qh_img = smem + kX3BufB;            // group 0, buffer 1
         unsigned char* ql_img = smem + kX3GrpB + kX3BufB;  // group 1, buffer 1
-        typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int row = 16 * i + 2 * wid + h;
             const float x[4] = {qraw[i].x, qraw[i].y, qraw[i].z, qraw[i].w};
-            bf16x4v hi, lo;
+            bf16x4 hi, lo;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 hi[e] = (__bf16)x[e];
                 lo[e] = (__bf16)(x[e] - (float)hi[e]);
             }
             const int off = row * 256 + (((c4 >> 1) ^ (row & 15)) * 16) + 8 * (c4 & 1);
-            *reinterpret_cast<bf16x4v*>(qh_img + off) = hi;
-            *reinterpret_cast<bf16x4v*>(ql_img + off) = lo;
+            *reinterpret_cast<bf16x4*>(qh_img + off) = hi;
+            *reinterpret_cast<bf16x4*>(ql_img + off) = lo;
         }
     }
     lds_barrier();
@@ -1595,7 +1581,6 @@ win_attn_x3_v2_kernel(Params p, const float* __restrict__ q, const __bf16* __res
                     const shortx4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(vh + a1));
                     const shortx4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(vl + a0));
                     const shortx4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(vl + a1));
-                    typedef short shortx8 __attribute__((ext_vector_type(8)));
                     const shortx8 vh8 = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
                     const shortx8 vl8 = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
                     o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vl8), ph[ksx], o[dt], 0, 0, 0);
@@ -1747,15 +1732,14 @@ __global__ void __launch_bounds__(256) split_kv_kernel(const float4* __restrict_
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n4) return;
     const float4 x = blockIdx.y ? v[i] : k[i];
-    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-    bf16x4v hi, lo;
+    bf16x4 hi, lo;
     const float e[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         hi[j] = (__bf16)e[j];
         lo[j] = (__bf16)(e[j] - (float)hi[j]);
     }
-    bf16x4v* o = reinterpret_cast<bf16x4v*>(out + (size_t)blockIdx.y * 2 * (4 * n4));
+    bf16x4* o = reinterpret_cast<bf16x4*>(out + (size_t)blockIdx.y * 2 * (4 * n4));
     o[i] = hi;
     o[n4 + i] = lo;
 }
@@ -2015,7 +1999,6 @@ extern "C" int tsplat_win_attn_bf16_shift_fwd(const void* q, const void* k, cons
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
 }
-
 
 // bf16x3 key / value split for tsplat_win_attn_x3_*: out = [kh | kl | vh | vl], each n bf16
 extern "C" int tsplat_split_kv_bf16x3(const float* k, const float* v, void* out, int64_t n, void* stream_) {

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 #include "prof.h"
 
 namespace tsplat {
@@ -34,8 +35,6 @@ constexpr int kCoB = 32;     // output channels per workgroup
 constexpr int kTiles = 32;   // output tiles per workgroup
 constexpr int kCiB = 8;      // channels per chunk of conv_kernel (16 for conv64_kernel)
 constexpr int kGroup = 16;   // packed-filter channel group: [xi][co block][group][lane][8 slots]
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int kMaxSrc = 6;     // input sources concatenated along channels (read in place)
 constexpr int kMaxCiPad = 1024;  // input channels (padded to 16) of one launch
@@ -52,12 +51,6 @@ struct Args {
     int act;             // 0 none, 1 ReLU, 2 GELU (erf)
     int cob_base;        // first 32-channel output block of this launch (a split launch's offset)
 };
-
-__device__ __forceinline__ float act_fn(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.0f);
-    if (act == 2) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-    return v;
-}
 
 // U = G g G^T, G = [[1, 0, 0], [1/2, 1/2, 1/2], [1/2, -1/2, 1/2], [0, 0, 1]], packed as the A
 // operand of v_mfma_f32_32x32x2_f32: lane l (co = 32 b + (l & 31), k half h = l >> 5) of channel
@@ -210,7 +203,7 @@ __device__ __forceinline__ void store_tile(const Args& a, const float* zs, int c
         if (py >= a.h) continue;
         const float y0v = i == 0 ? z[0][0] + z[1][0] + z[2][0] : z[1][0] - z[2][0] - z[3][0];
         const float y1v = i == 0 ? z[0][1] + z[1][1] + z[2][1] : z[1][1] - z[2][1] - z[3][1];
-        const float r0 = act_fn(y0v + bv, a.act), r1 = act_fn(y1v + bv, a.act);
+        const float r0 = conv_act(y0v + bv, a.act), r1 = conv_act(y1v + bv, a.act);
         const int px = 2 * otx;
         float* p = dst + (size_t)py * a.w + px;
         if (px + 1 < a.w && ((reinterpret_cast<uintptr_t>(p) & 7) == 0)) {

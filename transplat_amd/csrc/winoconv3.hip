@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 #include "prof.h"
 
 #ifndef TSPLAT_W3_ABL
@@ -32,9 +33,6 @@
 
 namespace tsplat {
 namespace wino3 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int kMaxSrc = 6;
 constexpr int kMaxCiPad = 1024;
@@ -74,28 +72,6 @@ struct Args {
     const float* res2;   // a second such addend (the fusion block's skip), or null
     int cob_base;        // first 32-channel output block of this launch
 };
-
-__device__ __forceinline__ float act_fn(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.0f);
-    if (act == 2) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-    return v;
-}
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-
-// (a, b) rounded to bf16 and packed (a in the low half): one v_cvt_pk_bf16_f32
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((floatx2){a, b}, bf16x2));
-}
-
-// hi / lo halves of the channel pair (a, b) as two packed dwords (channel a in the low half):
-// cvt_pk, shift, and, two subtractions, cvt_pk
-__device__ __forceinline__ void split_pair(float a, float b, uint32_t& hi, uint32_t& lo) {
-    hi = pack_bf16(a, b);
-    const float ah = __builtin_bit_cast(float, hi << 16), bh = __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = pack_bf16(a - ah, b - bh);
-}
 
 // U = G g G^T (as winoconv.hip's weight_kernel), split into hi / lo bf16 and packed as the A operand
 // of v_mfma_f32_32x32x16_bf16: lane l (co = 32 b + (l & 31), h = l >> 5), element j <- ci = 16 k + 8 h + j
@@ -364,14 +340,13 @@ __global__ void __launch_bounds__(256 * CB * KS, (NB == 1 && CB * KS <= 2) ? 2 :
         const int c = chunk * 16 + gch;
         // global address space: a plain pointer read from LDS would make these flat loads, which
         // count against the LDS counter too and wait on it
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        typedef const __attribute__((address_space(1))) f4v* gptr;
+        typedef const __attribute__((address_space(1))) floatx4* gptr;
         const float* plane = planes[min(c, a.ci_pad - 1)];
         const bool cok = c < a.ci;
 #pragma unroll
         for (int k = 0; k < (ST ? NL : 0); ++k) {
             const float* addr = cok && g_code[k] >= 0 ? plane + g_code[k] : reinterpret_cast<const float*>(&g_zero16);
-            const f4v v = *(gptr)addr;
+            const floatx4 v = *(gptr)addr;
             gr[decltype(S)::value][k] = make_float4(v.x, v.y, v.z, v.w);
         }
     };
@@ -532,7 +507,7 @@ __global__ void __launch_bounds__(256 * CB * KS, (NB == 1 && CB * KS <= 2) ? 2 :
             if (py >= a.h) continue;
             const float y0v = i == 0 ? z[0][0] + z[1][0] + z[2][0] : z[1][0] - z[2][0] - z[3][0];
             const float y1v = i == 0 ? z[0][1] + z[1][1] + z[2][1] : z[1][1] - z[2][1] - z[3][1];
-            float r0 = act_fn(y0v + bv, a.act), r1 = act_fn(y1v + bv, a.act);
+            float r0 = conv_act(y0v + bv, a.act), r1 = conv_act(y1v + bv, a.act);
             const int px = 2 * otx;
             float* p = dst + (size_t)py * a.w + px;
             const size_t off = ((size_t)pt.img * a.co + o) * hw + (size_t)py * a.w + px;
@@ -647,14 +622,13 @@ __global__ void __launch_bounds__(256, 2) conv_persist_kernel(Args a, int nblock
         const bool cok = valid && c < a.ci;
         const int cc = min(c, a.ci_pad - 1);
         const float* plane = planes[cc] + (size_t)img * cstride[cc];
-        typedef float f4v __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int k = 0; k < NL; ++k) {
             const int code = g_pos[k];
             const int y = ry0 + ((code >> 12) & 4095), x = rx0 + 4 * (code & 4095);
             const bool ok = cok && code >= 0 && y >= 0 && y < a.h && x >= 0 && x < a.w;
             const float* addr = ok ? plane + (size_t)y * a.w + x : reinterpret_cast<const float*>(&g_zero16);
-            const f4v v = *(const __attribute__((address_space(1))) f4v*)addr;
+            const floatx4 v = *(const __attribute__((address_space(1))) floatx4*)addr;
             gr[decltype(S)::value][k] = make_float4(v.x, v.y, v.z, v.w);
         }
     };
@@ -757,7 +731,7 @@ __global__ void __launch_bounds__(256, 2) conv_persist_kernel(Args a, int nblock
                 if (py >= a.h) continue;
                 const float y0v = i == 0 ? z[0][0] + z[1][0] + z[2][0] : z[1][0] - z[2][0] - z[3][0];
                 const float y1v = i == 0 ? z[0][1] + z[1][1] + z[2][1] : z[1][1] - z[2][1] - z[3][1];
-                float r0 = act_fn(y0v + bv, a.act), r1 = act_fn(y1v + bv, a.act);
+                float r0 = conv_act(y0v + bv, a.act), r1 = conv_act(y1v + bv, a.act);
                 const int px = 2 * otx;
                 const size_t off = ((size_t)img * a.co + o) * hw + (size_t)py * a.w + px;
                 if (a.res) {

@@ -5,10 +5,13 @@ requires device tensors and the in-tree HIP library; there is no fallback path.
 """
 from __future__ import annotations
 
+import ctypes
+import functools
 import os
 import weakref
 
 import torch
+import torch.nn.functional as F
 
 from . import _lib
 
@@ -17,6 +20,36 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+# The one cache of tensors derived from a weight or bias (packed MFMA operands, split hi / lo images,
+# transformed filters): (id(tensor), tag) -> (weakref, version, value). A hit needs the same live
+# tensor (never a new tensor at a recycled address or id) at an unchanged version; several tags on one
+# tensor coexist (the fp32 direct pack and the x3 pack of one weight).
+_DERIVED: dict = {}
+_DERIVED_MAX = 512  # entries of dead tensors are pruned once the dict is larger than this
+
+
+def _derived(tensor, tag: str, make):
+    """make(tensor.detach()), cached per (tensor, tag) and tensor version (see _DERIVED)."""
+    key = (id(tensor), tag)
+    hit = _DERIVED.get(key)
+    if hit is not None and hit[0]() is tensor and hit[1] == tensor._version:
+        return hit[2]
+    val = make(tensor.detach())
+    if len(_DERIVED) > _DERIVED_MAX:
+        for k in [k for k, v in _DERIVED.items() if v[0]() is None]:
+            del _DERIVED[k]
+    _DERIVED[key] = (weakref.ref(tensor), tensor._version, val)
+    return val
+
+
+def _square(v) -> int:
+    """A Conv2d-style stride / padding / dilation / kernel size as one int: an int, or the common
+    value of an equal pair; -1 for anything else (unequal pairs, "same")."""
+    if isinstance(v, int):
+        return v
+    return v[0] if len(set(v)) == 1 else -1
 
 
 def small_inverse(x: torch.Tensor) -> torch.Tensor:
@@ -263,8 +296,6 @@ def conv_bias_act(conv, x, act: str = "none", residual=None, site: str = "", ext
     Used on the depth predictor's full-resolution conv -> GELU -> conv heads (+0.4 % e2e); on the
     DPT ResidualConvUnits the bias-free convolutions measured 3 % slower end to end (A/B with
     TSPLAT_NO_CONV_EPI=<site>), so those keep the module path."""
-    import torch.nn.functional as F
-
     if not x.is_cuda:
         raise RuntimeError("transplat HIP ops need device tensors (no CPU path)")
     if (residual is None and act in _ACTS and _NO_CONV_EPI not in ("all", site)
@@ -335,6 +366,7 @@ def group_norm(x, num_groups: int, weight, bias, eps: float, act: str = "none", 
     lib = _lib.load()
     n, c = x.shape[:2]
     hw = x[0, 0].numel()
+    bf16 = False
     if isinstance(residual, (tuple, list)):
         r1, r2 = residual
         if not (_CAT_RES and x.dtype == torch.float32 and r1.dtype == r2.dtype == torch.float32 and x.is_cuda):
@@ -343,47 +375,26 @@ def group_norm(x, num_groups: int, weight, bias, eps: float, act: str = "none", 
         if (r1.shape[0] != n or r2.shape[0] != n or r1.shape[1] + r2.shape[1] != c or r1.shape[2:] != x.shape[2:]
                 or r2.shape[2:] != x.shape[2:]):
             raise ValueError(f"residual parts {tuple(r1.shape)} + {tuple(r2.shape)} != input {tuple(x.shape)}")
-        xf = _f32(x)
-        y = torch.empty_like(xf)
-        ws = torch.empty(int(lib.tsplat_group_norm_workspace_bytes(n, c, hw, num_groups)), dtype=torch.uint8,
-                         device=x.device)
-        pb = _f32(pre_bias) if pre_bias is not None else None
-        rc = lib.tsplat_group_norm_cat_res_fwd(_lib.ptr(xf), _lib.ptr(pb), _lib.ptr(_f32(weight)),
-                                               _lib.ptr(_f32(bias)), _lib.ptr(r1), _lib.ptr(r2), r1.shape[1],
-                                               _lib.ptr(y), _lib.ptr(ws), n, c, hw, num_groups, float(eps),
-                                               _ACTS[act], _lib.stream_ptr(x.device))
-        _lib.check(rc, "tsplat_group_norm_cat_res_fwd")
-        return y
-    if x.dtype == torch.bfloat16 and x.is_cuda and _BF16_NORMS:
-        if residual is not None and residual.dtype != torch.bfloat16:
+        entry, res = "tsplat_group_norm_cat_res_fwd", (_lib.ptr(r1), _lib.ptr(r2), r1.shape[1])
+    else:
+        bf16 = x.dtype == torch.bfloat16 and x.is_cuda and _BF16_NORMS
+        if bf16 and residual is not None and residual.dtype != torch.bfloat16:
             # the module path rounds the norm's output to bf16 (GroupNorm32 casts back to x's dtype)
             # and then promotes bf16 + fp32 to fp32: keep the fp32 residual stream un-narrowed
             return group_norm(x, num_groups, weight, bias, eps, act, None, pre_bias).float() + residual
-        xb = x.contiguous()
-        res = residual.contiguous() if residual is not None else None
-        if res is not None and res.shape != x.shape:
-            raise ValueError(f"residual {tuple(res.shape)} != input {tuple(x.shape)}")
-        y = torch.empty_like(xb)
-        ws = torch.empty(int(lib.tsplat_group_norm_workspace_bytes(n, c, hw, num_groups)), dtype=torch.uint8,
-                         device=x.device)
-        pb = _f32(pre_bias) if pre_bias is not None else None
-        rc = lib.tsplat_group_norm_bf16_fwd(_lib.ptr(xb), _lib.ptr(pb), _lib.ptr(_f32(weight)), _lib.ptr(_f32(bias)),
-                                            _lib.ptr(res) if res is not None else None, _lib.ptr(y), _lib.ptr(ws),
-                                            n, c, hw, num_groups, float(eps), _ACTS[act], _lib.stream_ptr(x.device))
-        _lib.check(rc, "tsplat_group_norm_bf16_fwd")
-        return y
-    xf = _f32(x)
-    res = _f32(residual) if residual is not None else None
-    if res is not None and res.shape != x.shape:
-        raise ValueError(f"residual {tuple(res.shape)} != input {tuple(x.shape)}")
-    y = torch.empty_like(xf)
+        r = None if residual is None else (residual.contiguous() if bf16 else _f32(residual))
+        if r is not None and r.shape != x.shape:
+            raise ValueError(f"residual {tuple(r.shape)} != input {tuple(x.shape)}")
+        entry, res = "tsplat_group_norm_bf16_fwd" if bf16 else "tsplat_group_norm_fwd", (_lib.ptr(r),)
+    xc = x.contiguous() if bf16 else _f32(x)
+    y = torch.empty_like(xc)
     ws = torch.empty(int(lib.tsplat_group_norm_workspace_bytes(n, c, hw, num_groups)), dtype=torch.uint8,
                      device=x.device)
     pb = _f32(pre_bias) if pre_bias is not None else None
-    rc = lib.tsplat_group_norm_fwd(_lib.ptr(xf), _lib.ptr(pb), _lib.ptr(_f32(weight)), _lib.ptr(_f32(bias)),
-                                   _lib.ptr(res) if res is not None else None, _lib.ptr(y), _lib.ptr(ws), n, c, hw,
-                                   num_groups, float(eps), _ACTS[act], _lib.stream_ptr(x.device))
-    _lib.check(rc, "tsplat_group_norm_fwd")
+    rc = getattr(lib, entry)(_lib.ptr(xc), _lib.ptr(pb), _lib.ptr(_f32(weight)), _lib.ptr(_f32(bias)), *res,
+                             _lib.ptr(y), _lib.ptr(ws), n, c, hw, num_groups, float(eps), _ACTS[act],
+                             _lib.stream_ptr(x.device))
+    _lib.check(rc, entry)
     return y
 
 
@@ -755,9 +766,6 @@ def mha(qkv, heads: int, scale: float, bias=None, precision: str | None = None):
     return out
 
 
-# packed weights per weight tensor: id -> (weakref, version, packed); a hit needs the same live
-# tensor (never a new tensor at a recycled address or id) at an unchanged version
-_CONV_PACKED: dict = {}
 # Which convolutions go to tsplat_conv2d_f32_fwd: "auto" (the latency-bound ones, see
 # conv2d_direct_ok), "off" (always MIOpen), "all" (every shape the kernel takes; tests / A/B)
 _CONV_MODE = os.environ.get("TSPLAT_CONV", "auto")
@@ -810,34 +818,45 @@ def _zsplit_counters(device, tiles: int):
     return view
 
 
-def conv_zsplit(tiles: int, pairs: int, ksplit: int, k: int) -> int:
-    """Workgroups per output tile for tsplat_conv2d_f32_zsplit_fwd (1 = no split)."""
+def _wave_split(tiles: int, work: int, max_waves: int, per_wave: int) -> int:
+    """Waves per output tile: 16, halved while the grid exceeds `max_waves` waves or a wave would get
+    fewer than `per_wave` of the tile's `work` reduction items (ci pairs, 16-channel units)."""
+    ksplit = 16
+    while ksplit > 1 and (tiles * ksplit > max_waves or work < per_wave * ksplit):
+        ksplit //= 2
+    return ksplit
+
+
+def _zsplit_factor(tiles: int, more) -> int:
+    """Workgroups per output tile of a zsplit launch (1 = no split): doubled from z while the grid
+    stays within _ZSPLIT_WGS workgroups, the _ZSPLIT knob allows 2 z and `more(z)` (the site's rule
+    for the work every wave keeps) holds."""
     if _ZSPLIT == 0:
         return 1
-    per_batch = _ZSPLIT_MIN if k == 3 else 4 * _ZSPLIT_MIN
     z = 1
-    while (z < 64 and tiles * 2 * z <= _ZSPLIT_WGS and -(-pairs // (ksplit * z)) > per_batch
-           and (_ZSPLIT < 0 or 2 * z <= _ZSPLIT)):
+    while z < 64 and tiles * 2 * z <= _ZSPLIT_WGS and more(z) and (_ZSPLIT < 0 or 2 * z <= _ZSPLIT):
         z *= 2
     return z
+
+
+def conv_zsplit(tiles: int, pairs: int, ksplit: int, k: int) -> int:
+    """Workgroups per output tile for tsplat_conv2d_f32_zsplit_fwd (1 = no split)."""
+    per_batch = _ZSPLIT_MIN if k == 3 else 4 * _ZSPLIT_MIN
+    return _zsplit_factor(tiles, lambda z: -(-pairs // (ksplit * z)) > per_batch)
+
+
+def _pack_conv(weight):
+    co, ci, k = weight.shape[:3]  # a Conv1d weight [cout, cin, 1] packs as the 1x1 it is
+    cot = (co + 31) // 32
+    w = torch.zeros((cot * 32, ci, k * k), dtype=torch.float32, device=weight.device)
+    w[:co] = weight.float().reshape(co, ci, k * k)
+    return w.reshape(cot, 32, ci // 2, 2, k * k).permute(0, 4, 2, 3, 1).contiguous()
 
 
 def conv_pack_weight(weight):
     """[cout, cin, k, k] -> [ceil(cout / 32), k * k, cin / 2, 2, 32] (zero-padded couts), cached per
     weight tensor version: the A-operand order of tsplat_conv2d_f32_fwd."""
-    hit = _CONV_PACKED.get(id(weight))
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2]
-    co, ci, k = weight.shape[:3]  # a Conv1d weight [cout, cin, 1] packs as the 1x1 it is
-    cot = (co + 31) // 32
-    w = torch.zeros((cot * 32, ci, k * k), dtype=torch.float32, device=weight.device)
-    w[:co] = weight.detach().float().reshape(co, ci, k * k)
-    packed = w.reshape(cot, 32, ci // 2, 2, k * k).permute(0, 4, 2, 3, 1).contiguous()
-    if len(_CONV_PACKED) > 512:
-        for k in [k for k, v in _CONV_PACKED.items() if v[0]() is None]:
-            del _CONV_PACKED[k]
-    _CONV_PACKED[id(weight)] = (weakref.ref(weight), weight._version, packed)
-    return packed
+    return _derived(weight, "conv", _pack_conv)
 
 
 def conv2d_direct_ok(x, weight, stride: int = 1, padding=None, c2: int = 0, upsample: bool = False,
@@ -855,13 +874,8 @@ def conv2d_direct_ok(x, weight, stride: int = 1, padding=None, c2: int = 0, upsa
     co, ci, k, k2 = weight.shape
     if k != k2 or k not in (1, 3) or stride not in (1, 2) or (upsample and stride != 1):
         return False
-    pad = padding if padding is not None else k // 2
-    if isinstance(pad, (tuple, list)):
-        if len(set(pad)) != 1:
-            return False
-        pad = pad[0]
     c1 = x.shape[1]
-    if pad != k // 2 or ci != c1 + c2 or c1 % 2 or c2 % 2:
+    if _square(padding if padding is not None else k // 2) != k // 2 or ci != c1 + c2 or c1 % 2 or c2 % 2:
         return False
     if _CONV_MODE == "all" or force:
         return True
@@ -878,30 +892,25 @@ def conv2d_direct_ok(x, weight, stride: int = 1, padding=None, c2: int = 0, upsa
 # the direct convolutions in the bf16x3 dense mode on split-bf16 MFMA (tsplat_conv2d_bf16x3_fwd) instead of
 # exact fp32; TSPLAT_CONV_X3=0 keeps them exact (A/B knob)
 _CONV_X3 = os.environ.get("TSPLAT_CONV_X3", "1") == "1"
-_CONV_X3_PACKED: dict = {}
+
+
+def _pack_conv_x3(weight):
+    co, ci = weight.shape[:2]
+    k = weight.shape[2] if weight.dim() == 4 else 1
+    cot, ng = (co + 31) // 32, (ci + 15) // 16
+    w = torch.zeros((cot * 32, ng * 16, k * k), dtype=torch.float32, device=weight.device)
+    w[:co, :ci] = weight.float().reshape(co, ci, k * k)
+    a = w.reshape(cot, 32, ng, 2, 8, k * k).permute(0, 5, 2, 3, 1, 4)  # [cot, tap, g, h, m, j]
+    hi = a.to(torch.bfloat16)
+    lo = (a - hi.float()).to(torch.bfloat16)
+    return torch.stack((hi, lo), dim=3).contiguous()  # [cot, tap, g, hl, h, m, j]
 
 
 def conv_pack_weight_x3(weight):
     """[cout, cin, k, k] -> hi / lo bf16 fragments [ceil(cout / 32)][k * k][ceil(cin / 16)][hi, lo][64 lanes]
     [8] (lane l: cout 32 cot + (l & 31), cin 16 g + 8 (l >> 5) + j; zero-padded), cached per weight
     tensor version: the A operand of tsplat_conv2d_bf16x3_fwd."""
-    hit = _CONV_X3_PACKED.get(id(weight))
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2]
-    co, ci = weight.shape[:2]
-    k = weight.shape[2] if weight.dim() == 4 else 1
-    cot, ng = (co + 31) // 32, (ci + 15) // 16
-    w = torch.zeros((cot * 32, ng * 16, k * k), dtype=torch.float32, device=weight.device)
-    w[:co, :ci] = weight.detach().float().reshape(co, ci, k * k)
-    a = w.reshape(cot, 32, ng, 2, 8, k * k).permute(0, 5, 2, 3, 1, 4)  # [cot, tap, g, h, m, j]
-    hi = a.to(torch.bfloat16)
-    lo = (a - hi.float()).to(torch.bfloat16)
-    packed = torch.stack((hi, lo), dim=3).contiguous()  # [cot, tap, g, hl, h, m, j]
-    if len(_CONV_X3_PACKED) > 512:
-        for key in [key for key, v in _CONV_X3_PACKED.items() if v[0]() is None]:
-            del _CONV_X3_PACKED[key]
-    _CONV_X3_PACKED[id(weight)] = (weakref.ref(weight), weight._version, packed)
-    return packed
+    return _derived(weight, "conv_x3", _pack_conv_x3)
 
 
 def conv_x3_wins(npx: int, ci: int, co: int, k: int) -> bool:
@@ -915,22 +924,20 @@ def conv_x3_wins(npx: int, ci: int, co: int, k: int) -> bool:
     return ci >= 64 and 2.0 * npx * co * ci * k * k >= 0.5e9
 
 
-def _conv2d_direct_x3(lib, a, b, c1, c2, weight, bias, n, h, w, co, k, stride, upsample, y):
-    hout, wout = y.shape[2], y.shape[3]
-    tiles = ((n * hout * wout + 31) // 32) * ((co + 31) // 32)
-    units = (c1 + c2 + 15) // 16 * k * k
+def _conv_x3_shape(tiles: int, units: int):
+    """(waves per tile, workgroups per tile) of a tsplat_conv2d_bf16x3_fwd launch."""
     # waves per tile: up to 16 while the grid stays <= 8192 waves and every wave has a unit; then
     # workgroups per tile (zsplit) doubled while the grid stays within 256 workgroups and every
     # wave keeps >= 2 units (the alternative, >= 1 unit with 4-unit batches, measured slower:
     # profiles/r5/conv_x3/census_x3b.log)
-    ksplit = 16
-    while ksplit > 1 and (tiles * ksplit > _CONV3_WAVES or units < ksplit):
-        ksplit //= 2
-    z = 1
-    if _ZSPLIT != 0:
-        while (z < 64 and tiles * 2 * z <= _ZSPLIT_WGS and units >= 2 * ksplit * 2 * z
-               and (_ZSPLIT < 0 or 2 * z <= _ZSPLIT)):
-            z *= 2
+    ksplit = _wave_split(tiles, units, _CONV3_WAVES, 1)
+    return ksplit, _zsplit_factor(tiles, lambda z: units >= 2 * ksplit * 2 * z)
+
+
+def _conv2d_direct_x3(lib, a, b, c1, c2, weight, bias, n, h, w, co, k, stride, upsample, y):
+    hout, wout = y.shape[2], y.shape[3]
+    tiles = ((n * hout * wout + 31) // 32) * ((co + 31) // 32)
+    ksplit, z = _conv_x3_shape(tiles, (c1 + c2 + 15) // 16 * k * k)
     part = cnt = None
     if z > 1:
         part = torch.empty(tiles * z * 1024, dtype=torch.float32, device=y.device)
@@ -967,11 +974,8 @@ def conv2d_direct(x1, weight, bias=None, stride: int = 1, x2=None, upsample: boo
     # one or two batches of loads, so more of them in flight hide more of the latency)
     tiles = ((n * hout * wout + 31) // 32) * ((co + 31) // 32)
     pairs = ci // 2
-    ksplit = 16
     cap, min_pairs = (_CONV3_WAVES, _CONV3_PAIRS) if k == 3 else (_CONV1_WAVES, _CONV1_PAIRS)
-    while ksplit > 1 and (tiles * ksplit > cap or pairs < min_pairs * ksplit):
-        ksplit //= 2
-    ksplit = _CONV_KSPLIT or ksplit
+    ksplit = _CONV_KSPLIT or _wave_split(tiles, pairs, cap, min_pairs)
     zsplit = conv_zsplit(tiles, pairs, ksplit, k) if ksplit == 16 else 1
     pb = _f32(bias) if bias is not None else None
     part = cnt = None
@@ -985,8 +989,6 @@ def conv2d_direct(x1, weight, bias=None, stride: int = 1, x2=None, upsample: boo
     return y
 
 
-# Winograd-transformed weights per weight tensor (same caching rule as _CONV_PACKED)
-_WINO_PACKED: dict = {}
 # Which 3x3 convolutions go to tsplat_conv3x3_wino_f32_fwd: "auto" (the shapes where it beats
 # MIOpen, see conv3x3_wino_ok), "off", "all" (every 3x3 / stride 1 / pad 1 fp32 conv; tests / A/B),
 # "big" (auto with the direct kernel's FLOP floor also where MIOpen is the alternative; A/B only:
@@ -995,23 +997,20 @@ _WINO_MODE = os.environ.get("TSPLAT_WINO", "auto")
 _WINO_ACT = {"none": 0, "relu": 1, "gelu": 2}
 
 
-def wino_pack_weight(weight):
-    """[cout, cin, 3, 3] -> the transformed filters G g G^T in the A-operand order of
-    tsplat_conv3x3_wino_f32_fwd, cached per weight tensor version."""
-    hit = _WINO_PACKED.get(id(weight))
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2]
+def _pack_wino(weight):
     lib = _lib.load()
     co, ci = weight.shape[:2]
     packed = torch.empty(int(lib.tsplat_wino_weight_floats(co, ci)), dtype=torch.float32, device=weight.device)
-    w = weight.detach().float().contiguous()
+    w = _f32(weight)
     _lib.check(lib.tsplat_wino_weight_f32(_lib.ptr(w), _lib.ptr(packed), co, ci, _lib.stream_ptr(weight.device)),
                "tsplat_wino_weight_f32")
-    if len(_WINO_PACKED) > 512:
-        for k in [k for k, v in _WINO_PACKED.items() if v[0]() is None]:
-            del _WINO_PACKED[k]
-    _WINO_PACKED[id(weight)] = (weakref.ref(weight), weight._version, packed)
     return packed
+
+
+def wino_pack_weight(weight):
+    """[cout, cin, 3, 3] -> the transformed filters G g G^T in the A-operand order of
+    tsplat_conv3x3_wino_f32_fwd, cached per weight tensor version."""
+    return _derived(weight, "wino", _pack_wino)
 
 
 WINO_MAX_CI_PAD = 1024  # winoconv.hip kMaxCiPad: input channels (padded to 16) of one launch
@@ -1033,11 +1032,10 @@ def conv3x3_wino_ok(x, weight, stride=1, padding=1, dilation=1, groups=1, extra=
             return False
     if weight.dtype != torch.float32 or weight.dim() != 4:
         return False
-    as_int = lambda v: v if isinstance(v, int) else (v[0] if len(set(v)) == 1 else -1)
-    if tuple(weight.shape[2:]) != (3, 3) or as_int(stride) != 1 or as_int(padding) != 1:
+    if tuple(weight.shape[2:]) != (3, 3) or _square(stride) != 1 or _square(padding) != 1:
         return False
     ci = sum(t.shape[1] for t in (x, *extra))
-    if as_int(dilation) != 1 or groups != 1 or weight.shape[1] != ci:
+    if _square(dilation) != 1 or groups != 1 or weight.shape[1] != ci:
         return False
     if (ci + 15) // 16 * 16 > WINO_MAX_CI_PAD:  # the launch's LDS plane table (winoconv.hip kMaxCiPad)
         return False
@@ -1062,23 +1060,22 @@ def conv2d_forward(mod, x):
     the 3x3s that conv3x3_wino_ok admits on the Winograd kernel, the latency-bound 1x1 / 3x3
     (stride 1 or 2) ones that conv2d_direct_ok admits on the direct kernel (bias in the epilogue
     instead of MIOpen's separate bias launch), the rest through MIOpen."""
-    if mod.padding_mode == "zeros" and mod.groups == 1 and tuple(mod.dilation) == (1, 1):
+    if mod.padding_mode == "zeros" and mod.groups == 1 and _square(mod.dilation) == 1:
         if conv_bf16_ok(x, mod.weight, mod.stride, mod.padding, mod.dilation, mod.groups):
             return conv_bf16(x, mod.weight, mod.bias)
         if conv3x3_wino_ok(x, mod.weight, mod.stride, mod.padding, mod.dilation, mod.groups, vs_miopen=True):
             return conv3x3_wino(x, mod.weight, mod.bias)
-        st = mod.stride[0] if mod.stride[0] == mod.stride[1] else 0
-        if (_ENC_DIRECT and st and x.is_contiguous() and x.dtype == torch.float32
+        st, pad = _square(mod.stride), _square(mod.padding)
+        if (_ENC_DIRECT and st > 0 and x.is_contiguous() and x.dtype == torch.float32
                 and conv2d_direct_ok(x, mod.weight, st, mod.padding)):
             return conv2d_direct(x, mod.weight, mod.bias, st)
         y = _conv2d_x3_libfree(x, mod.weight, mod.bias, mod.stride, mod.padding)
         if y is not None:
             return y
-        k = mod.kernel_size
-        if (_LIBFREE and st and k[0] == k[1] and k[0] > 3 and mod.padding[0] == mod.padding[1] and x.is_cuda
+        if (_LIBFREE and st > 0 and _square(mod.kernel_size) > 3 and pad >= 0 and x.is_cuda
                 and x.dtype == torch.float32 and mod.weight.dtype == torch.float32
                 and not torch.is_autocast_enabled("cuda")):
-            return conv_unfold_gemm(x, mod.weight, mod.bias, st, mod.padding[0])
+            return conv_unfold_gemm(x, mod.weight, mod.bias, st, pad)
     return mod._conv_forward(x, mod.weight, mod.bias)
 
 
@@ -1090,21 +1087,6 @@ _LIBFREE = os.environ.get("TSPLAT_CONV_LIBFREE", "1") == "1"
 # bf16x3 mode: every remaining Conv2d on the split-bf16 Winograd / direct kernels (TSPLAT_CONV_LIBFREE_X3=0:
 # the shapes above the latency-bound range stay on MIOpen, the A/B knob)
 _LIBFREE_X3 = os.environ.get("TSPLAT_CONV_LIBFREE_X3", "1") == "1"
-_DERIVED: dict = {}
-
-
-def _derived(weight, tag, make):
-    """A tensor derived from `weight` (cached per weight tensor and version, like _CONV_PACKED)."""
-    key = (id(weight), tag)
-    hit = _DERIVED.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2]
-    val = make(weight.detach())
-    if len(_DERIVED) > 256:
-        for k in [k for k, v in _DERIVED.items() if v[0]() is None]:
-            del _DERIVED[k]
-    _DERIVED[key] = (weakref.ref(weight), weight._version, val)
-    return val
 
 
 def conv_unfold_gemm(x, weight, bias, stride: int, padding: int):
@@ -1114,7 +1096,7 @@ def conv_unfold_gemm(x, weight, bias, stride: int, padding: int):
     n, ci, h, w = x.shape
     co, _, kh, kw = weight.shape
     ho, wo = (h + 2 * padding - kh) // stride + 1, (w + 2 * padding - kw) // stride + 1
-    cols = torch.nn.functional.unfold(x, (kh, kw), padding=padding, stride=stride)  # [n, ci kh kw, L]
+    cols = F.unfold(x, (kh, kw), padding=padding, stride=stride)  # [n, ci kh kw, L]
     # one GEMM per image straight into its [co, L] slab, bias in the GEMM's C term (a broadcast
     # matmul over the batch transposed cols into a [n L, ci kh kw] copy first, and the bias add
     # was another pass)
@@ -1136,18 +1118,18 @@ def conv_transpose_direct(x, weight, bias, s: int):
     ci, co = weight.shape[:2]
     w1 = _derived(weight, "convT", lambda t: t.permute(1, 2, 3, 0).reshape(co * s * s, ci, 1, 1).contiguous())
     b1 = _derived(bias, "convT_b", lambda t: t.repeat_interleave(s * s).contiguous()) if bias is not None else None
-    return torch.nn.functional.pixel_shuffle(conv2d_direct(x, w1, b1, 1), s)
+    return F.pixel_shuffle(conv2d_direct(x, w1, b1, 1), s)
 
 
 def conv_transpose_forward(mod, x):
     """nn.ConvTranspose2d.forward (installed by install_conv2d_dispatch): kernel = stride, no padding
     -> conv_transpose_direct; anything else through MIOpen."""
-    k, st = mod.kernel_size, mod.stride
-    if (_LIBFREE and k[0] == k[1] == st[0] == st[1] and tuple(mod.padding) == (0, 0) and mod.groups == 1
-            and tuple(mod.output_padding) == (0, 0) and tuple(mod.dilation) == (1, 1) and x.is_cuda
+    st = _square(mod.stride)
+    if (_LIBFREE and _square(mod.kernel_size) == st > 0 and _square(mod.padding) == 0 and mod.groups == 1
+            and _square(mod.output_padding) == 0 and _square(mod.dilation) == 1 and x.is_cuda
             and x.dtype == torch.float32 and mod.weight.dtype == torch.float32 and x.shape[1] % 2 == 0
             and not torch.is_autocast_enabled("cuda")):
-        return conv_transpose_direct(x.contiguous(), mod.weight, mod.bias, st[0])
+        return conv_transpose_direct(x.contiguous(), mod.weight, mod.bias, st)
     return torch.nn.ConvTranspose2d.forward(mod, x)
 
 
@@ -1160,8 +1142,8 @@ def _conv2d_x3_libfree(x, weight, bias, stride, padding):
     if not (_LIBFREE_X3 and split_mode() and x.is_cuda and x.dim() == 4 and x.is_contiguous()
             and x.dtype == torch.float32 and weight.dim() == 4):
         return None
-    st = stride if isinstance(stride, int) else (stride[0] if stride[0] == stride[1] else 0)
-    if not st:
+    st = _square(stride)
+    if st <= 0:
         return None
     if weight.shape[1] <= 256 and conv3x3_wino_ok(x, weight, stride, padding, force=True):
         return conv3x3_wino(x, weight, bias)
@@ -1173,18 +1155,16 @@ def _conv2d_x3_libfree(x, weight, bias, stride, padding):
 def conv2d_fallback(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
     """F.conv2d for the model code's last-resort branches: in the bf16x3 mode through
     _conv2d_x3_libfree first, so no convolution of that mode reaches MIOpen."""
-    if groups == 1 and (dilation == 1 or tuple(dilation) == (1, 1)):
+    if groups == 1 and _square(dilation) == 1:
         y = _conv2d_x3_libfree(x, weight, bias, stride, padding)
         if y is not None:
             return y
-    return torch.nn.functional.conv2d(x, weight, bias, stride, padding, dilation, groups)
+    return F.conv2d(x, weight, bias, stride, padding, dilation, groups)
 
 
 def install_conv2d_dispatch(module) -> int:
     """Route every nn.Conv2d under `module` through conv2d_forward (same parameters, same state
     dict); returns the number of modules routed."""
-    import functools
-
     n = 0
     for m in module.modules():
         if type(m) is torch.nn.Conv2d:
@@ -1275,9 +1255,6 @@ class attention_precision:
         return False
 
 
-_SPLIT_W: dict = {}
-
-
 def split_bf16x3(x: torch.Tensor, weight_order: bool = False) -> torch.Tensor:
     """[..., k] fp32 -> [..., 3k] bf16: [hi | hi | lo] (activations) or [hi | lo | hi] (weights_order),
     hi = bf16(x), lo = bf16(x - hi) (tsplat_split_bf16x3)."""
@@ -1292,15 +1269,7 @@ def split_bf16x3(x: torch.Tensor, weight_order: bool = False) -> torch.Tensor:
 
 def _split_weight(weight):
     """[n, k] -> [n, 3k] bf16 [hi | lo | hi], cached per weight tensor version."""
-    hit = _SPLIT_W.get(id(weight))
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2]
-    packed = split_bf16x3(weight.detach(), weight_order=True)
-    if len(_SPLIT_W) > 512:
-        for k in [k for k, v in _SPLIT_W.items() if v[0]() is None]:
-            del _SPLIT_W[k]
-    _SPLIT_W[id(weight)] = (weakref.ref(weight), weight._version, packed)
-    return packed
+    return _derived(weight, "split", lambda w: split_bf16x3(w, weight_order=True))
 
 
 def linear_bf16x3(x, weight, bias=None, act: str = "none", cache: bool = True):
@@ -1321,7 +1290,7 @@ def linear_bf16x3(x, weight, bias=None, act: str = "none", cache: bool = True):
             y = torch.mm(x3, w3.t(), out_dtype=torch.float32)
     y = y.reshape(*x.shape[:-1], n)
     if act == "gelu":
-        y = torch.nn.functional.gelu(y)
+        y = F.gelu(y)
     return y
 
 
@@ -1380,7 +1349,6 @@ def linear_xf32(x, weight, bias=None, act: str = "none"):
 # replaces hipBLASLt's exact-fp32 / emulated-xf32 GEMMs there. TSPLAT_GEMM_X3=0: the library path.
 _GEMM_X3 = os.environ.get("TSPLAT_GEMM_X3", "1") == "1"
 _GEMM_KSPLIT = int(os.environ.get("TSPLAT_GEMM_KSPLIT", "0"))  # 0: auto
-_GEMM_W: dict = {}
 GEMM_LOG = None  # list: (m, n, k, ksplit) per launch when set (bench.py's roofline)
 
 
@@ -1394,22 +1362,19 @@ def gemm_x3_ok(x, weight) -> bool:
     return k % 4 == 0 and n % 4 == 0 and x.shape[-1] == k
 
 
-def _gemm_pack(weight):
-    """W [n, k] -> its packed hi / lo MFMA fragments, cached per weight tensor version."""
-    hit = _GEMM_W.get(id(weight))
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2]
+def _pack_gemm(weight):
     lib = _lib.load()
     n, k = weight.shape
-    wf = _f32(weight.detach())
+    wf = _f32(weight)
     wp = torch.empty(int(lib.tsplat_gemm_x3_pack_bytes(n, k)), dtype=torch.uint8, device=weight.device)
     _lib.check(lib.tsplat_gemm_x3_pack(_lib.ptr(wf), _lib.ptr(wp), n, k, _lib.stream_ptr(weight.device)),
                "tsplat_gemm_x3_pack")
-    if len(_GEMM_W) > 512:
-        for key in [key for key, v in _GEMM_W.items() if v[0]() is None]:
-            del _GEMM_W[key]
-    _GEMM_W[id(weight)] = (weakref.ref(weight), weight._version, wp)
     return wp
+
+
+def _gemm_pack(weight):
+    """W [n, k] -> its packed hi / lo MFMA fragments, cached per weight tensor version."""
+    return _derived(weight, "gemm_x3", _pack_gemm)
 
 
 def gemm_ksplit(m: int, n: int, k: int) -> int:
@@ -1456,8 +1421,6 @@ def linear_forward(mod, x):
     """nn.Linear.forward (installed by install_linear_dispatch): in dense_precision("bf16x3") the fp32
     linears run on the split-bf16 GEMM (gemm_x3; linear_xf32 instead if its A/B knob admits them, and
     F.linear below 64 rows); everything else is F.linear."""
-    import torch.nn.functional as F
-
     if linear_xf32_ok(x, mod.weight):
         return linear_xf32(x, mod.weight, mod.bias)
     if gemm_x3_ok(x, mod.weight) and x.numel() // x.shape[-1] >= 64:
@@ -1467,8 +1430,6 @@ def linear_forward(mod, x):
 
 def install_linear_dispatch(module) -> int:
     """Route every nn.Linear under `module` through linear_forward (same parameters and state dict)."""
-    import functools
-
     n = 0
     for m in module.modules():
         if type(m) is torch.nn.Linear:
@@ -1482,26 +1443,20 @@ def install_linear_dispatch(module) -> int:
 WINO_FLOP_LOG = None
 
 
-_WINO3_PACKED: dict = {}
+def _pack_wino_x3(weight):
+    lib = _lib.load()
+    co, ci = weight.shape[:2]
+    packed = torch.empty(int(lib.tsplat_wino_weight_bf16x3_bytes(co, ci)), dtype=torch.uint8, device=weight.device)
+    w = _f32(weight)
+    _lib.check(lib.tsplat_wino_weight_bf16x3(_lib.ptr(w), _lib.ptr(packed), co, ci, _lib.stream_ptr(weight.device)),
+               "tsplat_wino_weight_bf16x3")
+    return packed
 
 
 def wino_pack_weight_bf16x3(weight):
     """[cout, cin, 3, 3] -> G g G^T split into hi / lo bf16 in the A-operand order of
     tsplat_conv3x3_wino_bf16x3_fwd, cached per weight tensor version."""
-    hit = _WINO3_PACKED.get(id(weight))
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2]
-    lib = _lib.load()
-    co, ci = weight.shape[:2]
-    packed = torch.empty(int(lib.tsplat_wino_weight_bf16x3_bytes(co, ci)), dtype=torch.uint8, device=weight.device)
-    w = weight.detach().float().contiguous()
-    _lib.check(lib.tsplat_wino_weight_bf16x3(_lib.ptr(w), _lib.ptr(packed), co, ci, _lib.stream_ptr(weight.device)),
-               "tsplat_wino_weight_bf16x3")
-    if len(_WINO3_PACKED) > 512:
-        for k in [k for k, v in _WINO3_PACKED.items() if v[0]() is None]:
-            del _WINO3_PACKED[k]
-    _WINO3_PACKED[id(weight)] = (weakref.ref(weight), weight._version, packed)
-    return packed
+    return _derived(weight, "wino_x3", _pack_wino_x3)
 
 
 # bf16x3 3x3s of few-channel full-resolution maps on the direct kernel tsplat_conv3x3_few_bf16x3_fwd
@@ -1522,6 +1477,17 @@ def _few_ok(srcs, n: int, h: int, w: int, co: int) -> bool:
             and int(_lib.load().tsplat_conv3x3_few_form(n, ci, h, w, co)) != 0)
 
 
+def _int32_array(values):
+    """A ctypes int32 array as the void pointer the C ABI takes (the pointer keeps the array alive)."""
+    return ctypes.cast((ctypes.c_int32 * len(values))(*values), ctypes.c_void_p)
+
+
+def _src_arrays(srcs):
+    """(source pointers, channel counts) of a multi-source launch: the host arrays its C entry reads."""
+    ptrs = (ctypes.c_void_p * len(srcs))(*[_lib.ptr(t) for t in srcs])
+    return ctypes.cast(ptrs, ctypes.c_void_p), _int32_array([t.shape[1] for t in srcs])
+
+
 def conv3x3_wino(x, weight, bias=None, act: str = "none", extra=(), precision: str | None = None, residual=None,
                  residual2=None, relu_in: bool = False):
     """act(conv2d(cat([x, *extra], 1), weight, bias, stride 1, padding 1)) (+ residual + residual2)
@@ -1529,8 +1495,6 @@ def conv3x3_wino(x, weight, bias=None, act: str = "none", extra=(), precision: s
     is loaded. precision "fp32" (tsplat_conv3x3_wino_cat_f32_fwd, exact fp32 MFMA; relu_in /
     residuals as separate launches) or "bf16x3" (tsplat_conv3x3_wino_bf16x3_ex_fwd, split-bf16
     MFMA, all fused); default: the current dense_precision mode."""
-    import ctypes
-
     lib = _lib.load()
     precision = precision or _DENSE
     if precision != "bf16x3" and (relu_in or residual is not None or residual2 is not None):
@@ -1548,8 +1512,7 @@ def conv3x3_wino(x, weight, bias=None, act: str = "none", extra=(), precision: s
         WINO_FLOP_LOG.append((2.0 * 16 * ci * co * n * ((h + 1) // 2) * ((w + 1) // 2), 2.0 * n * h * w * co * ci * 9))
     y = torch.empty((n, co, h, w), dtype=torch.float32, device=x.device)
     pb = _f32(bias) if bias is not None else None
-    ptrs = (ctypes.c_void_p * len(srcs))(*[_lib.ptr(t) for t in srcs])
-    chans = (ctypes.c_int32 * len(srcs))(*[t.shape[1] for t in srcs])
+    ptrs, chans = _src_arrays(srcs)
     if precision == "bf16x3":
         res = [_f32(r) if r is not None else None for r in (residual, residual2)]
         for r in res:
@@ -1558,19 +1521,16 @@ def conv3x3_wino(x, weight, bias=None, act: str = "none", extra=(), precision: s
         if _few_ok(srcs, n, h, w, co):
             # few-channel full-resolution maps: the direct split-bf16 kernel (csrc/convfew.hip)
             rc = lib.tsplat_conv3x3_few_bf16x3_fwd(
-                ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(chans, ctypes.c_void_p), len(srcs),
-                _lib.ptr(conv_pack_weight_x3(weight)), _lib.ptr(pb), _lib.ptr(res[0]), _lib.ptr(res[1]),
-                _lib.ptr(y), n, h, w, co, _WINO_ACT[act], int(relu_in), _lib.stream_ptr(x.device))
+                ptrs, chans, len(srcs), _lib.ptr(conv_pack_weight_x3(weight)), _lib.ptr(pb), _lib.ptr(res[0]),
+                _lib.ptr(res[1]), _lib.ptr(y), n, h, w, co, _WINO_ACT[act], int(relu_in), _lib.stream_ptr(x.device))
             _lib.check(rc, "tsplat_conv3x3_few_bf16x3_fwd")
             return y
         rc = lib.tsplat_conv3x3_wino_bf16x3_ex_fwd(
-            ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(chans, ctypes.c_void_p), len(srcs),
-            _lib.ptr(wino_pack_weight_bf16x3(weight)), _lib.ptr(pb), _lib.ptr(res[0]), _lib.ptr(res[1]), _lib.ptr(y),
-            n, h, w, co, _WINO_ACT[act], int(relu_in), _lib.stream_ptr(x.device))
+            ptrs, chans, len(srcs), _lib.ptr(wino_pack_weight_bf16x3(weight)), _lib.ptr(pb), _lib.ptr(res[0]),
+            _lib.ptr(res[1]), _lib.ptr(y), n, h, w, co, _WINO_ACT[act], int(relu_in), _lib.stream_ptr(x.device))
         _lib.check(rc, "tsplat_conv3x3_wino_bf16x3_ex_fwd")
         return y
-    rc = lib.tsplat_conv3x3_wino_cat_f32_fwd(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(chans, ctypes.c_void_p),
-                                             len(srcs), _lib.ptr(wino_pack_weight(weight)), _lib.ptr(pb),
+    rc = lib.tsplat_conv3x3_wino_cat_f32_fwd(ptrs, chans, len(srcs), _lib.ptr(wino_pack_weight(weight)), _lib.ptr(pb),
                                              _lib.ptr(y), n, h, w, co, _WINO_ACT[act], _lib.stream_ptr(x.device))
     _lib.check(rc, "tsplat_conv3x3_wino_cat_f32_fwd")
     return y
@@ -1579,38 +1539,27 @@ def conv3x3_wino(x, weight, bias=None, act: str = "none", extra=(), precision: s
 # bf16 implicit-GEMM 3x3 / 1x1 convolution (tsplat_conv2d_bf16_fwd) for the convolutions that run
 # under bf16 autocast (config C3); "0" = MIOpen (A/B knob)
 _CONV_BF16 = os.environ.get("TSPLAT_CONV_BF16", "1") != "0"
-_BF16_PACKED: dict = {}
+
+
+def _pack_conv_bf16(weight):
+    co, ci = weight.shape[:2]
+    taps = weight[0, 0].numel()  # [co, ci, k, k] or a Conv1d's [co, ci, 1]
+    cob, nk = (co + 31) // 32, (ci + 15) // 16
+    w = torch.zeros((cob * 32, nk * 16, taps), dtype=torch.bfloat16, device=weight.device)
+    w[:co, :ci] = weight.reshape(co, ci, taps).to(torch.bfloat16)
+    return w.view(cob, 32, nk, 2, 8, taps).permute(0, 2, 5, 3, 1, 4).contiguous()
 
 
 def conv_bf16_pack_weight(weight):
     """[cout, cin, k, k] (k = 1, 3) -> bf16 [ceil(cout / 32)][ceil(cin / 16)][k * k][64 lanes][8]
     (lane c + 32 h holds w[32 b + c][16 j + 8 h + 0..7][tap]), the A operand of
     tsplat_conv2d_bf16_fwd; cached per weight tensor version."""
-    hit = _BF16_PACKED.get(id(weight))
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2]
-    co, ci = weight.shape[:2]
-    taps = weight[0, 0].numel()  # [co, ci, k, k] or a Conv1d's [co, ci, 1]
-    cob, nk = (co + 31) // 32, (ci + 15) // 16
-    w = torch.zeros((cob * 32, nk * 16, taps), dtype=torch.bfloat16, device=weight.device)
-    w[:co, :ci] = weight.detach().reshape(co, ci, taps).to(torch.bfloat16)
-    packed = w.view(cob, 32, nk, 2, 8, taps).permute(0, 2, 5, 3, 1, 4).contiguous()
-    if len(_BF16_PACKED) > 512:
-        for k in [k for k, v in _BF16_PACKED.items() if v[0]() is None]:
-            del _BF16_PACKED[k]
-    _BF16_PACKED[id(weight)] = (weakref.ref(weight), weight._version, packed)
-    return packed
+    return _derived(weight, "conv_bf16", _pack_conv_bf16)
 
 
 def _bf16_rounded_bias(bias):
     """fp32 copy of the bias rounded to bf16 (autocast's cast), cached per tensor version."""
-    key = ("bias", id(bias))
-    hit = _BF16_PACKED.get(key)
-    if hit is not None and hit[0]() is bias and hit[1] == bias._version:
-        return hit[2]
-    rb = bias.detach().to(torch.bfloat16).float().contiguous()
-    _BF16_PACKED[key] = (weakref.ref(bias), bias._version, rb)
-    return rb
+    return _derived(bias, "bf16_bias", lambda b: b.to(torch.bfloat16).float().contiguous())
 
 
 def conv_bf16_ok(x, weight, stride=1, padding=None, dilation=1, groups=1, extra=(), upsample: bool = False) -> bool:
@@ -1631,8 +1580,7 @@ def conv_bf16_ok(x, weight, stride=1, padding=None, dilation=1, groups=1, extra=
             or (weight.dim() == 3 and weight.shape[2] == 1)) or groups != 1:
         return False
     k = weight.shape[2]
-    as_int = lambda v: v if isinstance(v, int) else (v[0] if len(set(v)) == 1 else -1)
-    if as_int(stride) != 1 or as_int(padding if padding is not None else k // 2) != k // 2 or as_int(dilation) != 1:
+    if _square(stride) != 1 or _square(padding if padding is not None else k // 2) != k // 2 or _square(dilation) != 1:
         return False
     n, _, h, w = x.shape
     if upsample:
@@ -1645,8 +1593,6 @@ def conv_bf16(x, weight, bias=None, act: str = "none", extra=(), upsample: bool 
     """act(conv2d(up(cat([x, *extra], 1)), weight, bias, 1, k // 2)) as autocast would compute it in
     bf16 (bf16-rounded sources, weights and bias, fp32 accumulation), output bf16 NCHW, in one
     tsplat_conv2d_bf16_fwd launch that reads the concatenation / nearest upsample in place."""
-    import ctypes
-
     if not x.is_cuda:
         raise RuntimeError("transplat HIP ops need device tensors (no CPU path)")
     lib = _lib.load()
@@ -1657,13 +1603,11 @@ def conv_bf16(x, weight, bias=None, act: str = "none", extra=(), upsample: bool 
     co, k = weight.shape[0], weight.shape[2]
     y = torch.empty((n, co, h, w), dtype=torch.bfloat16, device=x.device)
     pb = _bf16_rounded_bias(bias) if bias is not None else None
-    ptrs = (ctypes.c_void_p * len(srcs))(*[_lib.ptr(t) for t in srcs])
-    chans = (ctypes.c_int32 * len(srcs))(*[t.shape[1] for t in srcs])
-    f32 = (ctypes.c_int32 * len(srcs))(*[int(t.dtype == torch.float32) for t in srcs])
-    rc = lib.tsplat_conv2d_bf16_fwd(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(chans, ctypes.c_void_p),
-                                    len(srcs), ctypes.cast(f32, ctypes.c_void_p),
-                                    _lib.ptr(conv_bf16_pack_weight(weight)), _lib.ptr(pb), _lib.ptr(y), n, h, w,
-                                    co, k, int(upsample), _ACTS[act], _lib.stream_ptr(x.device))
+    ptrs, chans = _src_arrays(srcs)
+    f32 = _int32_array([int(t.dtype == torch.float32) for t in srcs])
+    rc = lib.tsplat_conv2d_bf16_fwd(ptrs, chans, len(srcs), f32, _lib.ptr(conv_bf16_pack_weight(weight)), _lib.ptr(pb),
+                                    _lib.ptr(y), n, h, w, co, k, int(upsample), _ACTS[act],
+                                    _lib.stream_ptr(x.device))
     _lib.check(rc, "tsplat_conv2d_bf16_fwd")
     return y
 
@@ -1691,9 +1635,7 @@ def conv2d_nhwc(x, weight, bias=None, residual=None, relu_in: bool = False):
         if res.shape != y.shape:
             raise ValueError(f"residual {tuple(res.shape)} != output {tuple(y.shape)}")
     tiles = ((n * h * w + 31) // 32) * ((co + 31) // 32)
-    ksplit = 16
-    while ksplit > 1 and (tiles * ksplit > 4096 or c // 2 < (2 if k == 3 else 16) * ksplit):
-        ksplit //= 2
+    ksplit = _wave_split(tiles, c // 2, 4096, 2 if k == 3 else 16)
     pb = _f32(bias) if bias is not None else None
     rc = lib.tsplat_conv2d_f32_nhwc_fwd(_lib.ptr(x), c, _lib.ptr(conv_pack_weight(weight)), _lib.ptr(pb),
                                         _lib.ptr(res), _lib.ptr(y), n, h, w, co, k, int(relu_in), ksplit,
@@ -1736,8 +1678,6 @@ def qkv_attention_cf(qkv, heads: int, views: int = 1):
 def conv_nhwc_epilogue(conv, x, act: str = "none", res1=None, res2=None):
     """act(conv(x) + bias) (+ res1) (+ res2) on channels-last fp32 maps: the bias-free MIOpen
     convolution, then bias, activation and residuals in one pass (tsplat_bias_act_nhwc_fwd)."""
-    import torch.nn.functional as F
-
     y = F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
     cl = torch.channels_last
     if not y.is_contiguous(memory_format=cl):
@@ -1773,8 +1713,6 @@ def interpolate_bilinear_ac(x, size):
     go through tsplat_resize_bilinear_nchw_fwd (one thread per output element; PyTorch's generic
     kernel serialises the N*C planes per output pixel: 240 us per call at C3's batch 8); anything
     else takes F.interpolate."""
-    import torch.nn.functional as F
-
     size = (int(size[0]), int(size[1]))
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
         return F.interpolate(x, size, mode="bilinear", align_corners=True)
