@@ -694,6 +694,37 @@ constexpr int kVtStrideH = kBK + 8;  // transposed V row (bf16 elements)
 constexpr float kThr = 8.0f;             // deferred-rescale threshold (log2 units): P <= 256
 constexpr float kMaskBonus = 1128.0f;    // bf16-exact; x 1/sqrt(128) = 99.7 (reference: 100)
 
+// The bf16x3 kernels' mask step carries the reference's 100 to fp32 precision instead: where the
+// scores themselves span +-100 (a different-region key whose raw score is 100 above the others is
+// a live softmax term, not a zero), 99.7 for 100 is a 35 % error of that key's weight. A window holds
+// at most four regions -- every window but the last along an axis lies in band 0, the last one in
+// bands 1 and 2 -- so the region within the window is lr = 2 [by == 2] + [bx == 2] and owns the four
+// k slots 4 lr .. 4 lr + 3 of the step: A holds the three bf16 parts of 100 / scale = 100 sqrt(128)
+// there (1128 + 3.375 - 0.004150390625 = 1131.3708496, its fp32 value; the products exact, summed
+// in the fp32 accumulator), B holds ones in the first three.
+static_assert(kC == 128, "the mask parts below are 100 * sqrt(kC)");
+constexpr unsigned kMaskA01 = 0x4058448Du;  // bf16 (1128, 3.375), element 0 in the low half
+constexpr unsigned kMaskA23 = 0x0000BB88u;  // bf16 (-0.004150390625, 0)
+constexpr unsigned kMaskB01 = 0x3F803F80u;  // bf16 (1, 1)
+constexpr unsigned kMaskB23 = 0x00003F80u;  // bf16 (1, 0)
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// region of in-window position t within its window wi: 2 [by == 2] + [bx == 2] (see win_region)
+__device__ __forceinline__ int win_region_local(const Params& p, int wi, int t) {
+    const int sy = wi / p.splits, sx = wi - sy * p.splits;
+    int ty, tx;
+    win_split(p, t, ty, tx);
+    return 2 * (sy * p.wh + ty >= p.H - p.wh / 2) + (sx * p.ww + tx >= p.W - p.ww / 2);
+}
+// k slots 8 h .. 8 h + 7 of a mask-step operand of local region lr, sel = lr - 2 h: the region's
+// four slots are this lane half's first (sel 0) or second (sel 1) four, else none
+__device__ __forceinline__ bf16x8 mask_frag(int sel, unsigned w01, unsigned w23) {
+    const u32x4 v = {sel == 0 ? w01 : 0u, sel == 0 ? w23 : 0u, sel == 1 ? w01 : 0u, sel == 1 ? w23 : 0u};
+    return __builtin_bit_cast(bf16x8, v);
+}
+__device__ __forceinline__ bf16x8 mask_a(int sel) { return mask_frag(sel, kMaskA01, kMaskA23); }
+__device__ __forceinline__ bf16x8 mask_b(int sel) { return mask_frag(sel, kMaskB01, kMaskB23); }
+
 // byte offset of 16-B chunk ch (0..15) of row r in a [rows][128 x bf16] tile, image (b) of T10:
 // conflict-free for ds_read_b128 row reads and ds_read_b64_tr_b16 transposed reads alike
 __device__ __forceinline__ int vimg_off(int r, int ch) {
@@ -1165,8 +1196,9 @@ win_attn_bf16_v3_kernel(Params p, const __bf16* __restrict__ q, const __bf16* __
 //     and are staged as hi / lo LDS images -- K row-major XOR-swizzled, V in the T10 image (b) read
 //     transposed by ds_read_b64_tr_b16 (win_attn_bf16_v2_kernel's operand maps);
 //   * softmax: raw fp32 scores, log2 domain, deferred rescale (P <= 2^kThr, split exactly as well);
-//   * the shifted-window mask as the v2 kernel's extra MFMA step on the hi part (+kMaskBonus to
-//     same-region scores: different-region weights e^-99.7 instead of e^-100, both 0 to fp32 output);
+//   * the shifted-window mask as the v2 kernel's extra MFMA step on the hi part, with the bonus
+//     100 / scale carried in three bf16 parts (kMaskA01 / kMaskA23: different-region weights e^-100 relative to
+//     fp32 precision, as the reference's, also where the scores themselves reach +-100);
 //   * K / V / mask tiles double-buffered, one barrier per tile; one workgroup per CU (132 KB LDS).
 // Writes the same split-key partials (lane-contiguous O, natural-log m, l) as the exact kernel, so
 // tsplat_linear_f32_attn_merge_fwd combines them in its operand staging unchanged.
@@ -1188,7 +1220,7 @@ win_attn_x3_kernel(Params p, const float* __restrict__ q, const __bf16* __restri
     __shared__ __attribute__((aligned(16))) __bf16 sKl[2][kBK * kC];
     __shared__ __attribute__((aligned(16))) unsigned char sVh[2][kBK * kC * 2];
     __shared__ __attribute__((aligned(16))) unsigned char sVl[2][kBK * kC * 2];
-    __shared__ __attribute__((aligned(16))) bf16x8 sMaskAb[2][kBK][2];
+    __shared__ __attribute__((aligned(16))) bf16x8 sMaskAb[2][kBK][2];  // mask_a fragments of the key rows
 
     WA_STAMP(0, wall_clock64());
     WA_STAMP(1, WA_HWID());
@@ -1209,12 +1241,7 @@ win_attn_x3_kernel(Params p, const float* __restrict__ q, const __bf16* __restri
     const int tq = qblk * kBQ3 + wid * kQW + c;
     const int qpix = win_pixel(p, wi, tq);
     bf16x8 qh[8], ql[8];
-    bf16x8 qmask;
-    {
-        const int qreg = p.shift ? win_region(p, wi, tq) : 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qmask[j] = (__bf16)(qreg == 8 * h + j ? 1.0f : 0.0f);
-    }
+    const bf16x8 qmask = mask_b((p.shift ? win_region_local(p, wi, tq) : 0) - 2 * h);
     floatx16 o[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -1243,7 +1270,7 @@ win_attn_x3_kernel(Params p, const float* __restrict__ q, const __bf16* __restri
             vvh[i] = cv[i];
             vvl[i] = dv[i];
         }
-        kreg = p.shift ? win_region(p, wi, j % p.L) : 0;
+        kreg = p.shift ? win_region_local(p, wi, j % p.L) : 0;
     };
     auto stage = [&](int buf) {
 #pragma unroll
@@ -1255,12 +1282,7 @@ win_attn_x3_kernel(Params p, const float* __restrict__ q, const __bf16* __restri
             *reinterpret_cast<bf16x8*>(&sVh[buf][vimg_off(grow, chunk)]) = vvh[i];
             *reinterpret_cast<bf16x8*>(&sVl[buf][vimg_off(grow, chunk)]) = vvl[i];
         }
-        if (p.shift && gpart < 2) {
-            bf16x8 a;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] = (__bf16)(kreg == 8 * gpart + j ? kMaskBonus : 0.0f);
-            sMaskAb[buf][grow][gpart] = a;
-        }
+        if (p.shift && gpart < 2) sMaskAb[buf][grow][gpart] = mask_a(kreg - 2 * gpart);
     };
     // prologue: the first tile's K / V loads go out before Q's, so stage(0) waits only for them;
     // Q[query c][16 i + 8 h .. + 7] is split into hi / lo (the B operand of k-step i) after it
@@ -1463,8 +1485,8 @@ win_attn_x3_v2_kernel(Params p, const float* __restrict__ q, const __bf16* __res
     const int nt = p.keys_per_split / kBK;
 
     const int tq = qblk * kBQ3 + wq * kQW + c;
-    // the query's region slot in the mask step's B operand (formed per tile: 4 registers fewer)
-    const int qslot = (p.shift ? win_region(p, wi, tq) : 0) - 8 * h;
+    // the query's slot group in the mask step's B operand (formed per tile: 4 registers fewer)
+    const int qsel = (p.shift ? win_region_local(p, wi, tq) : 0) - 2 * h;
 
     // gather: wave wq of a group moves image wq (Kh, Kl, Vh, Vl) of its half tile, one 1-KB wave
     // instruction = 4 whole 256-B rows (16 lanes per row, lane = 16-B chunk: 8 cache lines per
@@ -1604,16 +1626,10 @@ win_attn_x3_v2_kernel(Params p, const float* __restrict__ q, const __bf16* __res
                 sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh8, qh[i], sacc, 0, 0, 0);
             }
             if (p.shift) {
-                // one-hot key-region A fragment of key row c (slots 8h .. 8h + 7)
+                // key-region A fragment of key row c (slots 8h .. 8h + 7: mask_a)
                 const int j = kbeg + t * kBK + kHalfK * grp + c;
-                const int kreg = win_region(p, wi, p.m == 1 ? j : j % p.L);
-                bf16x8 ma;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) ma[e] = (__bf16)(kreg == 8 * h + e ? kMaskBonus : 0.0f);
-                bf16x8 qmask;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) qmask[e] = (__bf16)(qslot == e ? 1.0f : 0.0f);
-                sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ma, qmask, sacc, 0, 0, 0);
+                const int kreg = win_region_local(p, wi, p.m == 1 ? j : j % p.L);
+                sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mask_a(kreg - 2 * h), mask_b(qsel), sacc, 0, 0, 0);
             }
         }
         lds_barrier();
