@@ -112,6 +112,35 @@ int tsplat_raster_fwd(const tsplat_raster_desc* desc,
                       float* out_color, int32_t* out_radii,
                       void* workspace, int32_t* status, void* stream);
 
+/* The same rasterizer pass with rendered depth and accumulated opacity as further outputs: replaces
+ * the second rasterizer run of the reference's `render_depth_cuda`
+ * (src/model/decoder/cuda_splatting.py:375-417), which renders a per-Gaussian "fake colour" of the
+ * camera-space depth (:388-400) as a degree-0 SH coefficient over a black background and takes the
+ * mean over the channels. Here the preprocess writes that value per (view, Gaussian),
+ *   d = max(0.28209479 f + 0.5, 0),  f by depth_mode from the unscaled camera-space depth z:
+ *   0 "depth" z; 1 "disparity" 1 / z; 2 "relative_disparity" 1 - (1 / (z + eps) - 1 / (far + eps)) /
+ *   (1 / (near + eps) - 1 / (far + eps) + eps), eps = 1e-10 (depth_to_relative_disparity,
+ *   src/model/encoder/matching/conversions.py:18-28); 3 "log" log(max(min(z, near), far)) (the
+ *   reference's minimum(near).maximum(far) order, i.e. log(far)),
+ * and the blend accumulates it with the colour's own weights w = alpha T:
+ *   out_depth [V, H, W] = sum_i d_i w_i          (no background term)
+ *   out_alpha [V, H, W] = sum_i w_i = 1 - T      (T: the transmittance the colour's background
+ *                                                 term uses)
+ * near / far [V] are the views' unscaled planes (the values tsplat_raster_cameras takes). Each of
+ * out_color, out_depth, out_alpha may be NULL (that output is not computed; without out_color
+ * the SH coefficients are not read), not all three; colour and radii are bit-identical to
+ * tsplat_raster_fwd's. TSPLAT_EINVAL, before any launch, if all three are NULL, depth_mode is not
+ * 0..3, out_depth is set without near and far, or any rule of tsplat_raster_fwd is broken (all of
+ * its other pointers are required). Same workspace layout and size. */
+int tsplat_raster_depth_fwd(const tsplat_raster_desc* desc,
+                            const float* means, const float* cov, const float* shs,
+                            const float* opacity, const float* viewmat, const float* projmat,
+                            const float* campos, const float* tanfov, const float* bg,
+                            const float* scene_scale, const float* near, const float* far,
+                            int32_t depth_mode,
+                            float* out_color, float* out_depth, float* out_alpha,
+                            int32_t* out_radii, void* workspace, int32_t* status, void* stream);
+
 
 /* Depth-candidate softmax head (reference depth_predictor_trans.py:170-180): logits [n, depths, hw]
  * (NCHW), disp [n, depths] -> coarse [n, hw] = sum_d disp softmax_d, pdf_max [n, hw] = max_d softmax_d;

@@ -46,6 +46,10 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.POINTER(RasterDesc)] + [_P] * 15,
     ),
+    "tsplat_raster_depth_fwd": (
+        ctypes.c_int,
+        [ctypes.POINTER(RasterDesc)] + [_P] * 12 + [_I32] + [_P] * 7,
+    ),
     "tsplat_uv_coarse_fwd": (ctypes.c_int, [_P] * 4 + [_I32] * 5 + [_P]),
     "tsplat_uv_cross_fwd": (ctypes.c_int, [_P] * 7 + [_I32] * 6 + [_P]),
     "tsplat_uv_cross_table_fwd": (ctypes.c_int, [_P] * 6 + [_I32] * 6 + [_P]),

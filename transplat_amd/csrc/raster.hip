@@ -45,7 +45,7 @@ constexpr int kSortCap = 4096;            // tile lists up to this length are so
 constexpr int kPreThreads = 256;
 constexpr size_t kMaxLdsBytes = 160 * 1024;  // gfx950 LDS per workgroup
 constexpr int kRecBytes = 64;             // per-(view, Gaussian) record (Workspace::rec)
-constexpr int kRecFields = 9;             // x, y, conic a b c, opacity, r g b
+constexpr int kGeomFields = 6;            // x, y, conic a b c, opacity (then r g b, then the depth value)
 
 __constant__ float kSH_C0 = 0.28209479177387814f;
 __constant__ float kSH_C1 = 0.4886025119029199f;
@@ -66,7 +66,8 @@ struct Workspace {
     //   rec[4i + 1] conic (a, b, c) as log2(e) (-a/2, -b, -c/2) (the blend's log2-domain power
     //               form) + opacity
     //   rec[4i + 2] rgb + view-space depth
-    //   rec[4i + 3] block-cull constants: threshold q, -b/a, -b/c (ellipse_meets_block)
+    //   rec[4i + 3] block-cull constants: threshold q, -b/a, -b/c (ellipse_meets_block) + the depth
+    //               value d the depth output blends (0 when no depth is asked for)
     float4* rec;
     uint32_t* counts;    // [V*T]
     uint32_t* offsets;   // [V*T + 1]
@@ -101,7 +102,28 @@ struct Params {
     int count_sort;  // 1: counting sort for long tile lists (default); 0: bitonic only (A/B)
     int view_rot;    // render: view v's workgroups take tiles rotated by v * view_rot (load balance)
     int sh_vec4;     // preprocess: every wave's SH block is 16-byte aligned (16-byte staging loads)
+    int depth_mode;  // preprocess: -1 no depth value; 0 depth, 1 disparity, 2 relative disparity, 3 log
 };
+
+// The value the depth output blends for one (view, Gaussian): the reference renders depth as a
+// colour (render_depth_cuda, cuda_splatting.py:375-417): fake colour f of the UNSCALED camera-space
+// depth z (:388-400) as the degree-0 SH coefficient, so d = max(C0 f + 0.5, 0). z = vz / s undoes
+// the scale-invariant rendering (vz is the depth of the scaled scene). "log" keeps the reference's
+// minimum(near).maximum(far) order, which gives log(far) for every Gaussian. IEEE division and logf.
+__device__ __forceinline__ float depth_value(int mode, float vz, float s, float near, float far) {
+    const float z = vz / s;
+    float f = z;
+    if (mode == 1) {
+        f = 1.0f / z;
+    } else if (mode == 2) {
+        const float eps = 1e-10f;  // depth_to_relative_disparity (matching/conversions.py:18-28)
+        const float disp_near = 1.0f / (near + eps), disp_far = 1.0f / (far + eps);
+        f = 1.0f - (1.0f / (z + eps) - disp_far) / (disp_near - disp_far + eps);
+    } else if (mode == 3) {
+        f = logf(fmaxf(fminf(z, near), far));
+    }
+    return fmaxf(kSH_C0 * f + 0.5f, 0.0f);
+}
 
 __device__ __forceinline__ void get_rect(float px, float py, int r, int tx, int ty, int& x0,
                                          int& y0, int& x1, int& y1) {
@@ -169,15 +191,19 @@ __global__ void __launch_bounds__(256) zero_kernel(uint4* __restrict__ p, size_t
 // stride), which made the SH reads half of this kernel's time (TSPLAT_RASTER_DIAG=7 skips them).
 constexpr int kMaxShFloats = 75;  // 3 (deg 4 + 1)^2
 constexpr int kShStageIt = (kWave * kMaxShFloats / 4 + kWave - 1) / kWave;  // float4s per lane
+// kColor: the records get colours (SH staged and evaluated); without it the SH block is neither
+// loaded nor evaluated (what TSPLAT_RASTER_DIAG=7 skips). kExtra: the instantiations behind
+// tsplat_raster_depth_fwd, which write the depth value into rec[3].w when p.depth_mode >= 0.
+template <bool kColor, bool kExtra>
 __global__ void __launch_bounds__(kPreThreads)
 preprocess_kernel(Params p, const float* __restrict__ means, const float* __restrict__ cov,
                   const float* __restrict__ shs, const float* __restrict__ opacity,
                   const float* __restrict__ viewmat, const float* __restrict__ projmat,
                   const float* __restrict__ campos, const float* __restrict__ tanfov,
-                  const float* __restrict__ scene_scale, int32_t* __restrict__ out_radii,
-                  Workspace ws) {
+                  const float* __restrict__ scene_scale, const float* __restrict__ near,
+                  const float* __restrict__ far, int32_t* __restrict__ out_radii, Workspace ws) {
     extern __shared__ uint32_t hist[];  // [T]
-    __shared__ __attribute__((aligned(16))) float s_sh[kPreThreads * kMaxShFloats];
+    __shared__ __attribute__((aligned(16))) float s_sh[kColor ? kPreThreads * kMaxShFloats : 4];
     const int scene = blockIdx.y;
     const int lane = threadIdx.x % kWave, wid = threadIdx.x / kWave;
     const int g = blockIdx.x * kPreThreads + threadIdx.x;
@@ -191,7 +217,8 @@ preprocess_kernel(Params p, const float* __restrict__ means, const float* __rest
     const int sh_total = max(0, min(kWave, p.G - gw0)) * nf;
     const float* sh_src = shs + (size_t)nf * ((size_t)scene * p.G + gw0);
     float* sh_dst = s_sh + (size_t)wid * kWave * nf;
-    const bool stage4 = p.sh_vec4 && p.diag != 7;
+    const bool no_sh = !kColor || p.diag == 7;
+    const bool stage4 = p.sh_vec4 && !no_sh;
     const int t4 = stage4 ? sh_total / 4 : 0;
     // 19 named registers, loaded unconditionally at a clamped index (held in an array across the
     // geometry pass, the staging lived in scratch memory)
@@ -317,9 +344,12 @@ preprocess_kernel(Params p, const float* __restrict__ means, const float* __rest
                 constexpr float kLog2e = 1.44269504088896341f;
                 rec[1] = make_float4(-0.5f * kLog2e * conic_a, -kLog2e * conic_b, -0.5f * kLog2e * conic_c, o);
                 // cull threshold in the same log2 units as the stored conic: 2 log2(255 o), + margins
+                float d = 0.0f;
+                if constexpr (kExtra)
+                    if (p.depth_mode >= 0) d = depth_value(p.depth_mode, vz, s, near[v], far[v]);
                 rec[3] = make_float4(2.0f * __log2f(255.0f * o) * 1.001f + 1.5e-3f,
                                      -conic_b * __builtin_amdgcn_rcpf(conic_a),
-                                     -conic_b * __builtin_amdgcn_rcpf(conic_c), 0.0f);
+                                     -conic_b * __builtin_amdgcn_rcpf(conic_c), d);
                 for (int ty = y0; ty < y1; ++ty)
                     for (int tx = x0; tx < x1; ++tx) atomicAdd(&hist[ty * p.tiles_x + tx], 1u);
             } else {
@@ -343,7 +373,7 @@ preprocess_kernel(Params p, const float* __restrict__ means, const float* __rest
     TSPLAT_SH_ST(12) TSPLAT_SH_ST(13) TSPLAT_SH_ST(14) TSPLAT_SH_ST(15) TSPLAT_SH_ST(16) TSPLAT_SH_ST(17)
     TSPLAT_SH_ST(18)
 #undef TSPLAT_SH_ST
-    if (p.diag != 7)
+    if (!no_sh)
         for (int i = 4 * t4 + lane; i < sh_total; i += kWave) sh_dst[i] = sh_src[i];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -357,7 +387,7 @@ preprocess_kernel(Params p, const float* __restrict__ means, const float* __rest
         const float vz = vm[2] * mx + vm[6] * my + vm[10] * mz + vm[14];  // as in pass 1, bit for bit
         float rgb[3] = {0.5f, 0.5f, 0.5f};
         const float* cp = campos + 3 * v;
-        if (p.diag != 7) sh_to_rgb(my_sh, p.M, p.deg, mx - cp[0], my - cp[1], mz - cp[2], rgb);
+        if (!no_sh) sh_to_rgb(my_sh, p.M, p.deg, mx - cp[0], my - cp[1], mz - cp[2], rgb);
         ws.rec[4 * ((size_t)v * p.G + g) + 2] = make_float4(rgb[0], rgb[1], rgb[2], vz);
     }
 }
@@ -736,9 +766,21 @@ __device__ __forceinline__ bool ellipse_meets_block(float mx, float my, float4 c
 // chunk ahead, the entries whose alpha >= 1/255 box can touch the block are compacted in depth
 // order into the wave's LDS slot (conservative, so exact) and blended branch-free; the wave
 // leaves as soon as all its 64 pixels are saturated.
+//
+// Three instantiations. <colour, no extras> is tsplat_raster_fwd's kernel. With kExtra
+// (tsplat_raster_depth_fwd) the compaction carries a further field, the depth value d of
+// rec[3].w, the blend accumulates D += d w with the colour's own weight w = alpha T, and the
+// kernel stores out_depth = D (no background term: the reference renders depth over black) and
+// out_alpha = 1 - T, each where its pointer is set. Without kColor the three rgb fields and
+// their accumulators are gone (the depth-only call). Every blend decision is the same code in all
+// three, so their weights agree bit for bit.
+template <bool kColor, bool kExtra>
 __global__ void __launch_bounds__(kTileThreads)
 render_kernel(Params p, const float* __restrict__ bg, float* __restrict__ out_color,
-              Workspace ws) {
+              float* __restrict__ out_depth, float* __restrict__ out_alpha, Workspace ws) {
+    constexpr int kRgbField = kGeomFields;                          // r g b (kColor)
+    constexpr int kDepthField = kGeomFields + (kColor ? 3 : 0);     // d (kExtra)
+    constexpr int kRecFields = kDepthField + (kExtra ? 1 : 0);      // 9, 10 or 7
     __shared__ uint64_t skeys[kSortCap];
     __shared__ uint32_t s_cnt[kBuckets];
     __shared__ uint32_t s_red[4];
@@ -792,6 +834,7 @@ render_kernel(Params p, const float* __restrict__ bg, float* __restrict__ out_co
     const float pfx = (float)pxi, pfy = (float)pyi;
     float T = 1.0f;
     float C0 = 0.f, C1 = 0.f, C2 = 0.f;
+    float D = 0.f;  // kExtra: sum of d w
     const size_t vbase = (size_t)v * p.G;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
     float (*w_rec)[kWave] = s_rec[wid];
@@ -801,7 +844,8 @@ render_kernel(Params p, const float* __restrict__ bg, float* __restrict__ out_co
     // e^power = 2^power2 is one v_exp_f32, and the quadratic in Horner form (2 FMAs + 3 multiplies).
     // Scalar fp32 on purpose: v_pk_fma_f32 has the same FLOP rate as v_fma_f32 (twice the cycles),
     // and packing the operands costs register moves.
-    auto blend = [&](float x, float y, float ca, float cb, float cc, float o, float r, float g, float bl) {
+    auto blend = [&](float x, float y, float ca, float cb, float cc, float o, float r, float g, float bl,
+                     float d) {
         // (ca, cb, cc) = log2(e) (-a/2, -b, -c/2): power2 = dy (cc dy + cb dx) + (ca dx) dx
         const float dx = x - pfx, dy = y - pfy;
         const float power2 = fmaf(dy, fmaf(cc, dy, cb * dx), (ca * dx) * dx);
@@ -812,12 +856,18 @@ render_kernel(Params p, const float* __restrict__ bg, float* __restrict__ out_co
         const bool stop = contrib && (test_T < 0.0001f);
         const bool acc = contrib && !stop;
         const float w = acc ? alpha * T : 0.0f;  // a skipped entry adds c * 0 = +0: C unchanged
-        C0 = fmaf(r, w, C0);
-        C1 = fmaf(g, w, C1);
-        C2 = fmaf(bl, w, C2);
+        if constexpr (kColor) {
+            C0 = fmaf(r, w, C0);
+            C1 = fmaf(g, w, C1);
+            C2 = fmaf(bl, w, C2);
+        }
+        if constexpr (kExtra) D = fmaf(d, w, D);
         T = acc ? test_T : T;
         done = done || stop;
     };
+    // fields an instantiation does not carry are read from field 0 and never used
+    constexpr int iR = kColor ? kRgbField : 0, iG = kColor ? kRgbField + 1 : 0, iB = kColor ? kRgbField + 2 : 0;
+    constexpr int iD = kExtra ? kDepthField : 0;
 
     struct Quad {
         float4 f[kRecFields];
@@ -828,10 +878,10 @@ render_kernel(Params p, const float* __restrict__ bg, float* __restrict__ out_co
     };
     auto blend_quad = [&](const Quad& q) {
         const float4* f = q.f;
-        blend(f[0].x, f[1].x, f[2].x, f[3].x, f[4].x, f[5].x, f[6].x, f[7].x, f[8].x);
-        blend(f[0].y, f[1].y, f[2].y, f[3].y, f[4].y, f[5].y, f[6].y, f[7].y, f[8].y);
-        blend(f[0].z, f[1].z, f[2].z, f[3].z, f[4].z, f[5].z, f[6].z, f[7].z, f[8].z);
-        blend(f[0].w, f[1].w, f[2].w, f[3].w, f[4].w, f[5].w, f[6].w, f[7].w, f[8].w);
+        blend(f[0].x, f[1].x, f[2].x, f[3].x, f[4].x, f[5].x, f[iR].x, f[iG].x, f[iB].x, f[iD].x);
+        blend(f[0].y, f[1].y, f[2].y, f[3].y, f[4].y, f[5].y, f[iR].y, f[iG].y, f[iB].y, f[iD].y);
+        blend(f[0].z, f[1].z, f[2].z, f[3].z, f[4].z, f[5].z, f[iR].z, f[iG].z, f[iB].z, f[iD].z);
+        blend(f[0].w, f[1].w, f[2].w, f[3].w, f[4].w, f[5].w, f[iR].w, f[iG].w, f[iB].w, f[iD].w);
     };
 
     const uint32_t* sids = reinterpret_cast<const uint32_t*>(skeys);  // sorted ids (n <= kSortCap)
@@ -880,9 +930,12 @@ render_kernel(Params p, const float* __restrict__ bg, float* __restrict__ out_co
                 w_rec[3][pos] = co.y;
                 w_rec[4][pos] = co.z;
                 w_rec[5][pos] = co.w;
-                w_rec[6][pos] = rgb.x;
-                w_rec[7][pos] = rgb.y;
-                w_rec[8][pos] = rgb.z;
+                if constexpr (kColor) {
+                    w_rec[kRgbField][pos] = rgb.x;
+                    w_rec[kRgbField + 1][pos] = rgb.y;
+                    w_rec[kRgbField + 2][pos] = rgb.z;
+                }
+                if constexpr (kExtra) w_rec[kDepthField][pos] = cull.w;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -895,8 +948,8 @@ render_kernel(Params p, const float* __restrict__ bg, float* __restrict__ out_co
                 blend_quad(q);
             }
             for (int i = m4; i < m; ++i)
-                blend(w_rec[0][i], w_rec[1][i], w_rec[2][i], w_rec[3][i], w_rec[4][i], w_rec[5][i], w_rec[6][i],
-                      w_rec[7][i], w_rec[8][i]);
+                blend(w_rec[0][i], w_rec[1][i], w_rec[2][i], w_rec[3][i], w_rec[4][i], w_rec[5][i], w_rec[iR][i],
+                      w_rec[iG][i], w_rec[iB][i], w_rec[iD][i]);
             __builtin_amdgcn_wave_barrier();  // reads of this chunk's records precede the next writes
         }
     };
@@ -912,11 +965,18 @@ render_kernel(Params p, const float* __restrict__ bg, float* __restrict__ out_co
     }
     if (inside) {
         const size_t hw = (size_t)p.H * p.W;
-        float* o = out_color + (size_t)v * 3 * hw + (size_t)pyi * p.W + pxi;
-        const float* bgv = bg + 3 * v;
-        o[0] = C0 + T * bgv[0];
-        o[hw] = C1 + T * bgv[1];
-        o[2 * hw] = C2 + T * bgv[2];
+        const size_t pix = (size_t)pyi * p.W + pxi;
+        if constexpr (kColor) {
+            float* o = out_color + (size_t)v * 3 * hw + pix;
+            const float* bgv = bg + 3 * v;
+            o[0] = C0 + T * bgv[0];
+            o[hw] = C1 + T * bgv[1];
+            o[2 * hw] = C2 + T * bgv[2];
+        }
+        if constexpr (kExtra) {
+            if (out_depth) out_depth[(size_t)v * hw + pix] = D;
+            if (out_alpha) out_alpha[(size_t)v * hw + pix] = 1.0f - T;
+        }
     }
 }
 
@@ -940,15 +1000,61 @@ extern "C" size_t tsplat_raster_num_rendered_offset(int32_t G, int32_t V, int32_
     return (size_t)((char*)(w.offsets + (size_t)V * T) - (char*)(uintptr_t)0x100000);
 }
 
-extern "C" int tsplat_raster_fwd(const tsplat_raster_desc* d, const float* means, const float* cov,
-                                 const float* shs, const float* opacity, const float* viewmat,
-                                 const float* projmat, const float* campos, const float* tanfov,
-                                 const float* bg, const float* scene_scale, float* out_color,
-                                 int32_t* out_radii, void* workspace, int32_t* status,
-                                 void* stream_) {
+// The launch sequence of both entry points. kColor / kExtra pick the preprocess and render
+// instantiations: <true, false> is tsplat_raster_fwd; tsplat_raster_depth_fwd takes <true, true>
+// with a colour output and <false, true> without one.
+template <bool kColor, bool kExtra>
+static int raster_launch(Params p, const float* means, const float* cov, const float* shs,
+                         const float* opacity, const float* viewmat, const float* projmat,
+                         const float* campos, const float* tanfov, const float* bg,
+                         const float* scene_scale, const float* near, const float* far,
+                         float* out_color, float* out_depth, float* out_alpha, int32_t* out_radii,
+                         Workspace ws, int32_t* status, hipStream_t stream) {
+    TSPLAT_PROF_BEGIN(prof::kRasterAll, stream);
+    {
+        // counts + cursor: 2 V T uint32, padded by carve()'s 256-byte alignment to whole uint4s
+        const size_t n4 = ceil_div((size_t)2 * p.V * p.T, (size_t)4);
+        const int blocks = (int)std::min<size_t>(ceil_div(n4, (size_t)256), 1024);
+        hipLaunchKernelGGL(zero_kernel, dim3(blocks), dim3(256), 0, stream, (uint4*)ws.counts, n4);
+        TSPLAT_CHECK_LAUNCH();
+    }
+    const int scenes = p.V / p.vps;
+    dim3 pre_grid(ceil_div(p.G, kPreThreads), p.V);
+    TSPLAT_PROF_BEGIN(prof::kRasterPreprocess, stream);
+    hipLaunchKernelGGL((preprocess_kernel<kColor, kExtra>), dim3(ceil_div(p.G, kPreThreads), scenes),
+                       dim3(kPreThreads), p.T * sizeof(uint32_t),
+                       stream, p, means, cov, shs, opacity, viewmat, projmat, campos, tanfov,
+                       scene_scale, near, far, out_radii, ws);
+    TSPLAT_PROF_END(prof::kRasterPreprocess, stream);
+    TSPLAT_CHECK_LAUNCH();
+    TSPLAT_PROF_BEGIN(prof::kRasterScatter, stream);
+    hipLaunchKernelGGL(scatter_kernel, pre_grid, dim3(kPreThreads), 3 * p.T * sizeof(uint32_t),
+                       stream, p, (const int32_t*)out_radii, ws, status);
+    TSPLAT_PROF_END(prof::kRasterScatter, stream);
+    TSPLAT_CHECK_LAUNCH();
+    TSPLAT_PROF_BEGIN(prof::kRasterRender, stream);
+    hipLaunchKernelGGL((render_kernel<kColor, kExtra>), dim3(p.T, p.V), dim3(kTileThreads), 0, stream, p,
+                       bg, out_color, out_depth, out_alpha, ws);
+    TSPLAT_PROF_END(prof::kRasterRender, stream);
+    TSPLAT_PROF_END(prof::kRasterAll, stream);
+    TSPLAT_CHECK_LAUNCH();
+    return TSPLAT_OK;
+}
+
+// Argument checks and launch parameters shared by tsplat_raster_fwd (depth_mode = -1, no extra
+// outputs) and tsplat_raster_depth_fwd. Every check comes before the first launch: a rejected call
+// queues nothing.
+static int raster_run(const tsplat_raster_desc* d, const float* means, const float* cov,
+                      const float* shs, const float* opacity, const float* viewmat,
+                      const float* projmat, const float* campos, const float* tanfov,
+                      const float* bg, const float* scene_scale, const float* near, const float* far,
+                      int depth_mode, bool extra, float* out_color, float* out_depth,
+                      float* out_alpha, int32_t* out_radii, void* workspace, int32_t* status,
+                      void* stream_) {
     if (!d || !means || !cov || !shs || !opacity || !viewmat || !projmat || !campos || !tanfov ||
-        !bg || !scene_scale || !out_color || !out_radii || !workspace || !status)
+        !bg || !scene_scale || !out_radii || !workspace || !status)
         return TSPLAT_EINVAL;
+    if (!out_color && !out_depth && !out_alpha) return TSPLAT_EINVAL;
     if (d->num_gaussians <= 0 || d->num_views <= 0 || d->views_per_scene <= 0 ||
         d->num_views % d->views_per_scene != 0 || d->height <= 0 || d->width <= 0 ||
         d->sh_coeffs <= 0 || d->sh_degree < 0 || d->sh_degree > 4 ||
@@ -967,6 +1073,7 @@ extern "C" int tsplat_raster_fwd(const tsplat_raster_desc* d, const float* means
     p.tiles_y = ceil_div(p.H, kTile);
     p.T = p.tiles_x * p.tiles_y;
     p.capacity = d->capacity;
+    p.depth_mode = depth_mode;
     {
         const char* e = getenv("TSPLAT_RASTER_DIAG");
         p.diag = e ? atoi(e) : 0;
@@ -977,7 +1084,6 @@ extern "C" int tsplat_raster_fwd(const tsplat_raster_desc* d, const float* means
         const int rows = (p.tiles_y + 1) / 3;
         p.view_rot = (r && !strcmp(r, "0")) ? 0 : rows * p.tiles_x;
     }
-    // every argument check before the first launch (a rejected call queues nothing)
     if (3 * p.M > kMaxShFloats || p.vps > 32) return TSPLAT_EINVAL;
     // scatter keeps 3 T uint32 of per-tile counters in LDS: up to gfx950's 160 KB per workgroup
     // (13,653 16x16 tiles, about 1860 x 1860 px); above 64 KB the kernel's dynamic-LDS limit is raised
@@ -988,39 +1094,44 @@ extern "C" int tsplat_raster_fwd(const tsplat_raster_desc* d, const float* means
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds) != hipSuccess)
         return TSPLAT_EINVAL;
     Workspace ws = carve(workspace, p.G, p.V, p.T, p.capacity, nullptr);
-
-    TSPLAT_PROF_BEGIN(prof::kRasterAll, stream);
-    {
-        // counts + cursor: 2 V T uint32, padded by carve()'s 256-byte alignment to whole uint4s
-        const size_t n4 = ceil_div((size_t)2 * p.V * p.T, (size_t)4);
-        const int blocks = (int)std::min<size_t>(ceil_div(n4, (size_t)256), 1024);
-        hipLaunchKernelGGL(zero_kernel, dim3(blocks), dim3(256), 0, stream, (uint4*)ws.counts, n4);
-        TSPLAT_CHECK_LAUNCH();
-    }
-    const int scenes = p.V / p.vps;
     // a wave's SH block starts at 3 M (scene G + 64 k) floats: 16-byte aligned when the base is
     // and 3 M G is a multiple of 4 (or there is one scene)
+    const int scenes = p.V / p.vps;
     p.sh_vec4 = ((uintptr_t)shs % 16 == 0) && (scenes == 1 || ((size_t)3 * p.M * p.G) % 4 == 0);
-    dim3 pre_grid(ceil_div(p.G, kPreThreads), p.V);
-    TSPLAT_PROF_BEGIN(prof::kRasterPreprocess, stream);
-    hipLaunchKernelGGL(preprocess_kernel, dim3(ceil_div(p.G, kPreThreads), scenes), dim3(kPreThreads),
-                       p.T * sizeof(uint32_t),
-                       stream, p, means, cov, shs, opacity, viewmat, projmat, campos, tanfov,
-                       scene_scale, out_radii, ws);
-    TSPLAT_PROF_END(prof::kRasterPreprocess, stream);
-    TSPLAT_CHECK_LAUNCH();
-    TSPLAT_PROF_BEGIN(prof::kRasterScatter, stream);
-    hipLaunchKernelGGL(scatter_kernel, pre_grid, dim3(kPreThreads), 3 * p.T * sizeof(uint32_t),
-                       stream, p, (const int32_t*)out_radii, ws, status);
-    TSPLAT_PROF_END(prof::kRasterScatter, stream);
-    TSPLAT_CHECK_LAUNCH();
-    TSPLAT_PROF_BEGIN(prof::kRasterRender, stream);
-    hipLaunchKernelGGL(render_kernel, dim3(p.T, p.V), dim3(kTileThreads), 0, stream, p, bg,
-                       out_color, ws);
-    TSPLAT_PROF_END(prof::kRasterRender, stream);
-    TSPLAT_PROF_END(prof::kRasterAll, stream);
-    TSPLAT_CHECK_LAUNCH();
-    return TSPLAT_OK;
+#define TSPLAT_RASTER_ARGS                                                                          \
+    p, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale, near, far,     \
+        out_color, out_depth, out_alpha, out_radii, ws, status, stream
+    if (!extra) return raster_launch<true, false>(TSPLAT_RASTER_ARGS);
+    if (out_color) return raster_launch<true, true>(TSPLAT_RASTER_ARGS);
+    return raster_launch<false, true>(TSPLAT_RASTER_ARGS);
+#undef TSPLAT_RASTER_ARGS
+}
+
+extern "C" int tsplat_raster_fwd(const tsplat_raster_desc* d, const float* means, const float* cov,
+                                 const float* shs, const float* opacity, const float* viewmat,
+                                 const float* projmat, const float* campos, const float* tanfov,
+                                 const float* bg, const float* scene_scale, float* out_color,
+                                 int32_t* out_radii, void* workspace, int32_t* status,
+                                 void* stream_) {
+    if (!out_color) return TSPLAT_EINVAL;
+    return raster_run(d, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale,
+                      nullptr, nullptr, -1, false, out_color, nullptr, nullptr, out_radii, workspace,
+                      status, stream_);
+}
+
+extern "C" int tsplat_raster_depth_fwd(const tsplat_raster_desc* d, const float* means,
+                                       const float* cov, const float* shs, const float* opacity,
+                                       const float* viewmat, const float* projmat,
+                                       const float* campos, const float* tanfov, const float* bg,
+                                       const float* scene_scale, const float* near, const float* far,
+                                       int32_t depth_mode, float* out_color, float* out_depth,
+                                       float* out_alpha, int32_t* out_radii, void* workspace,
+                                       int32_t* status, void* stream_) {
+    if (depth_mode < 0 || depth_mode > 3) return TSPLAT_EINVAL;
+    if (out_depth && (!near || !far)) return TSPLAT_EINVAL;
+    return raster_run(d, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale,
+                      near, far, out_depth ? depth_mode : -1, true, out_color, out_depth, out_alpha,
+                      out_radii, workspace, status, stream_);
 }
 
 // ---------------------------------------------------------------------------------------------

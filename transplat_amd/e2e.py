@@ -26,13 +26,15 @@ class TransplatModel(torch.nn.Module):
         self.data_shim = self.encoder.get_data_shim()
 
     @torch.no_grad()
-    def test_step(self, batch: dict, global_step: int = 0, benchmarker=None):
+    def test_step(self, batch: dict, global_step: int = 0, benchmarker=None, depth_mode=None):
+        """`depth_mode` (a DepthRenderingMode): the step's DecoderOutput carries the depth render too."""
         batch = self.data_shim(batch)
         _, _, _, h, w = batch["target"]["image"].shape
         gaussians = self.encoder(batch["context"], global_step, deterministic=True, benchmarker=benchmarker)
         t = batch["target"]
         with stage(benchmarker, "decoder"):  # reference model_wrapper.py:209-218 tags it "decoder"
-            return self.decoder(gaussians, t["extrinsics"], t["intrinsics"], t["near"], t["far"], (h, w))
+            return self.decoder(gaussians, t["extrinsics"], t["intrinsics"], t["near"], t["far"], (h, w),
+                                depth_mode=depth_mode)
 
     def load_checkpoint(self, path: str, strict: bool = True):
         """Lightning checkpoint of the reference (`state_dict` with `encoder.` / `decoder.` keys);
@@ -108,9 +110,10 @@ class GraphedStep:
     """The whole test_step captured once into a hipGraph (torch.cuda.CUDAGraph) and replayed:
     at batch 1 the ~2,500 kernel launches of a step otherwise leave ~30 % of the GPU time idle.
     Inputs live in static buffers: `run(batch)` copies a new batch in (device-to-device) and
-    replays; outputs are the graph's static output tensors (valid until the next replay)."""
+    replays; outputs are the graph's static output tensors (valid until the next replay).
+    `depth_mode`: the captured step renders depth too (DecoderOutput.depth)."""
 
-    def __init__(self, model: TransplatModel, example: dict, warmup: int = 2):
+    def __init__(self, model: TransplatModel, example: dict, warmup: int = 2, depth_mode=None):
         from . import _lib
 
         if _lib.debug_enabled():  # its per-launch hipDeviceSynchronize is illegal inside a capture
@@ -123,11 +126,11 @@ class GraphedStep:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                model.test_step(self.static)
+                model.test_step(self.static, depth_mode=depth_mode)
         torch.cuda.current_stream().wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.out = model.test_step(self.static)
+            self.out = model.test_step(self.static, depth_mode=depth_mode)
 
     def run(self, batch: dict | None = None):
         if batch is not None:

@@ -2,10 +2,13 @@
 (reference src/model/decoder/decoder_splatting_cuda.py:26-97).
 
 Differences by design: the Gaussians are NOT repeated per target view (the reference
-materialises V copies, 46 MB each at G = 131072); all (b v) views go to one rasterizer call.
+materialises V copies, 46 MB each at G = 131072); all (b v) views go to one rasterizer call, and
+the depth render of `depth_mode` comes out of that same call (the reference runs the rasterizer a
+second time over fake colours).
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Literal, Optional
 
@@ -15,7 +18,7 @@ from torch import Tensor
 
 from ..types import Gaussians
 from .decoder import Decoder, DecoderOutput, DepthRenderingMode
-from .hip_splatting import check_status, prepare_cameras, rasterize
+from .hip_splatting import RasterOutput, check_status, prepare_cameras, rasterize, rasterize_with_depth
 
 
 @dataclass
@@ -24,6 +27,11 @@ class DecoderSplattingHIPCfg:
     sh_eval_degree: Optional[int] = None  # None: min(isqrt(d_sh) - 1, 3), the upstream behaviour
     check_overflow: bool = True  # sync after each call to surface capacity overflow
     debug: bool = False  # upstream GaussianRasterizationSettings.debug: sync + check after every launch
+
+
+def _depth_fused() -> bool:
+    """A/B knob, read per call: TSPLAT_DEPTH_FUSED=0 renders depth by the two-pass route."""
+    return os.environ.get("TSPLAT_DEPTH_FUSED", "1") != "0"
 
 
 def depth_fake_color(extrinsics: Tensor, means: Tensor, near: Tensor, far: Tensor,
@@ -66,30 +74,37 @@ class DecoderSplattingHIP(Decoder[DecoderSplattingHIPCfg]):
         depth_mode: DepthRenderingMode | None = None,
     ) -> DecoderOutput:
         b, v, _, _ = extrinsics.shape
+        fused = depth_mode is not None and _depth_fused()
+        out = self._render(gaussians, extrinsics, intrinsics, near, far, image_shape,
+                           depth_mode if fused else None, color=True)
+        color = rearrange(out.color, "(b v) c h w -> b v c h w", b=b, v=v)
+        depth = None
+        if fused:
+            depth = rearrange(out.depth, "(b v) h w -> b v h w", b=b, v=v)
+        elif depth_mode is not None:
+            depth = self.render_depth(gaussians, extrinsics, intrinsics, near, far, image_shape, depth_mode)
+        return DecoderOutput(color, depth)
+
+    def _render(self, gaussians, extrinsics, intrinsics, near, far, image_shape, depth_mode, color):
+        """One rasterizer call over the un-repeated Gaussians for all (b v) views: colour and / or
+        the depth render of `depth_mode` from the same pass."""
+        b, v, _, _ = extrinsics.shape
+        nr = rearrange(near, "b v -> (b v)")
+        fr = rearrange(far, "b v -> (b v)")
         cams = prepare_cameras(
             rearrange(extrinsics, "b v i j -> (b v) i j"),
             rearrange(intrinsics, "b v i j -> (b v) i j"),
-            rearrange(near, "b v -> (b v)"),
-            rearrange(far, "b v -> (b v)"),
+            nr,
+            fr,
             repeat(self.background_color, "c -> (b v) c", b=b, v=v),
         )
-        color, _ = rasterize(
-            gaussians.means,
-            gaussians.covariances,
-            gaussians.harmonics,
-            gaussians.opacities,
-            cams,
-            image_shape,
-            views_per_scene=v,
-            sh_degree=self.cfg.sh_eval_degree,
-            check=self.cfg.check_overflow,
-            debug=self.cfg.debug,
-        )
-        color = rearrange(color, "(b v) c h w -> b v c h w", b=b, v=v)
-        depth = None
-        if depth_mode is not None:
-            depth = self.render_depth(gaussians, extrinsics, intrinsics, near, far, image_shape, depth_mode)
-        return DecoderOutput(color, depth)
+        args = (gaussians.means, gaussians.covariances, gaussians.harmonics, gaussians.opacities, cams, image_shape)
+        kw = dict(views_per_scene=v, sh_degree=self.cfg.sh_eval_degree, check=self.cfg.check_overflow,
+                  debug=self.cfg.debug)
+        if depth_mode is None:
+            rgb, radii = rasterize(*args, **kw)
+            return RasterOutput(rgb, radii, None, None)
+        return rasterize_with_depth(*args, near=nr, far=fr, depth_mode=depth_mode, color=color, **kw)
 
     def render_depth(
         self,
@@ -101,8 +116,14 @@ class DecoderSplattingHIP(Decoder[DecoderSplattingHIPCfg]):
         image_shape: tuple[int, int],
         mode: DepthRenderingMode = "depth",
     ) -> Tensor:
-        """Depth as fake colour (reference cuda_splatting.py:375-417); one call per view set."""
+        """The reference's depth render (render_depth_cuda, cuda_splatting.py:375-417): one
+        depth-only rasterizer call for every view (the fake colour is computed per (view, Gaussian)
+        in the preprocess kernel). TSPLAT_DEPTH_FUSED=0 keeps the two-pass route: the Gaussians
+        repeated per view and rendered with depth_fake_color as their colour."""
         b, v, _, _ = extrinsics.shape
+        if _depth_fused():
+            out = self._render(gaussians, extrinsics, intrinsics, near, far, image_shape, mode, color=False)
+            return rearrange(out.depth, "(b v) h w -> b v h w", b=b, v=v)
         ext = rearrange(extrinsics, "b v i j -> (b v) i j")
         means = repeat(gaussians.means, "b g xyz -> (b v) g xyz", v=v)
         nr = rearrange(near, "b v -> (b v)")

@@ -144,6 +144,83 @@ def default_capacity(num_gaussians: int, num_views: int, height: int, width: int
     return max(1, min(num_gaussians * num_views * tiles, MAX_CAPACITY))
 
 
+DEPTH_MODES = {"depth": 0, "disparity": 1, "relative_disparity": 2, "log": 3}  # tsplat_raster_depth_fwd
+
+
+@dataclass
+class RasterOutput:
+    """What `rasterize_with_depth` returns; an output that was not asked for is None."""
+
+    color: Tensor | None  # [V, 3, H, W]
+    radii: Tensor  # [V, G] int32
+    depth: Tensor | None  # [V, H, W]
+    alpha: Tensor | None  # [V, H, W]
+
+
+def _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
+               capacity, check, debug, extra=None) -> RasterOutput:
+    """The call behind rasterize() (extra None: tsplat_raster_fwd) and rasterize_with_depth()
+    (extra = (near, far, mode id, color, depth, alpha): tsplat_raster_depth_fwd), with the same
+    capacity, overflow and debug rules."""
+    lib = _lib.load()
+    s, g, _ = means.shape
+    m = harmonics.shape[-1]
+    v = cameras.viewmat.shape[0]
+    if v != s * views_per_scene:
+        raise ValueError(f"{v} views for {s} scenes x {views_per_scene} views per scene")
+    if covariances.shape != (s, g, 3, 3) or harmonics.shape[:3] != (s, g, 3) or opacities.shape != (s, g):
+        raise ValueError("Gaussian tensor shapes disagree")
+    if sh_degree is None:
+        sh_degree = min(isqrt(m) - 1, 3)
+    h, w = image_shape
+    dev = means.device
+    f32 = lambda t: t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
+    means, covariances, harmonics, opacities = map(f32, (means, covariances, harmonics, opacities))
+    if capacity is None:
+        capacity = default_capacity(g, v, h, w)
+    nbytes = int(lib.tsplat_raster_workspace_bytes(g, v, h, w, capacity))
+    ws, status = _STATE.get(dev, nbytes)
+    want_color, want_depth, want_alpha = (True, False, False) if extra is None else extra[3:]
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    color = new(v, 3, h, w) if want_color else None
+    depth = new(v, h, w) if want_depth else None
+    alpha = new(v, h, w) if want_alpha else None
+    radii = torch.empty((v, g), dtype=torch.int32, device=dev)
+    desc = _lib.RasterDesc(g, v, views_per_scene, h, w, m, sh_degree, capacity)
+    cams = [f32(cameras.viewmat), f32(cameras.projmat), f32(cameras.campos), f32(cameras.tanfov),
+            f32(cameras.bg), f32(cameras.scale)]
+    planes = []
+    if extra is not None:
+        planes = [None if t is None else f32(t).reshape(-1) for t in extra[:2]]
+        for t in planes:
+            if t is not None and t.shape != (v,):
+                raise ValueError(f"near / far must hold one value per view ({v})")
+    for t in cams + [t for t in planes if t is not None]:
+        if t.device != dev:
+            raise ValueError("camera tensors must be on the Gaussians' device")
+    name = "tsplat_raster_fwd" if extra is None else "tsplat_raster_depth_fwd"
+    if debug and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("rasterize(debug=True) synchronises after every launch: not inside hipGraph capture")
+    was = lib.tsplat_set_debug(1) if debug else None
+    try:
+        gauss = [_lib.ptr(t) for t in (means, covariances, harmonics, opacities)]
+        tail = (_lib.ptr(radii), _lib.ptr(ws), _lib.ptr(status), _lib.stream_ptr(dev))
+        if extra is None:
+            rc = lib.tsplat_raster_fwd(desc, *gauss, *(_lib.ptr(t) for t in cams), _lib.ptr(color), *tail)
+        else:
+            rc = lib.tsplat_raster_depth_fwd(desc, *gauss, *(_lib.ptr(t) for t in cams),
+                                             *(_lib.ptr(t) for t in planes), extra[2],
+                                             _lib.ptr(color), _lib.ptr(depth), _lib.ptr(alpha), *tail)
+    finally:
+        if was is not None:
+            lib.tsplat_set_debug(was)
+    _lib.check(rc, name)
+    _STATE.last[(dev.type, dev.index)] = (ws, int(lib.tsplat_raster_num_rendered_offset(g, v, h, w)))
+    if check:
+        check_status(dev)
+    return RasterOutput(color, radii, depth, alpha)
+
+
 def rasterize(
     means: Tensor,
     covariances: Tensor,
@@ -168,54 +245,50 @@ def rasterize(
     `sh_degree` defaults to isqrt(M) - 1 (the degree render_cuda passes) capped at the
     evaluated degree of the upstream rasterizer (3); pass 4 to evaluate degree-4 terms.
     """
-    lib = _lib.load()
-    s, g, _ = means.shape
-    m = harmonics.shape[-1]
-    v = cameras.viewmat.shape[0]
-    if v != s * views_per_scene:
-        raise ValueError(f"{v} views for {s} scenes x {views_per_scene} views per scene")
-    if covariances.shape != (s, g, 3, 3) or harmonics.shape[:3] != (s, g, 3) or opacities.shape != (s, g):
-        raise ValueError("Gaussian tensor shapes disagree")
-    if sh_degree is None:
-        sh_degree = min(isqrt(m) - 1, 3)
-    h, w = image_shape
-    dev = means.device
-    f32 = lambda t: t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
-    means, covariances, harmonics, opacities = map(f32, (means, covariances, harmonics, opacities))
-    if capacity is None:
-        capacity = default_capacity(g, v, h, w)
-    nbytes = int(lib.tsplat_raster_workspace_bytes(g, v, h, w, capacity))
-    ws, status = _STATE.get(dev, nbytes)
-    color = torch.empty((v, 3, h, w), dtype=torch.float32, device=dev)
-    radii = torch.empty((v, g), dtype=torch.int32, device=dev)
-    desc = _lib.RasterDesc(g, v, views_per_scene, h, w, m, sh_degree, capacity)
-    cams = [f32(cameras.viewmat), f32(cameras.projmat), f32(cameras.campos), f32(cameras.tanfov),
-            f32(cameras.bg), f32(cameras.scale)]
-    for t in cams:
-        if t.device != dev:
-            raise ValueError("camera tensors must be on the Gaussians' device")
-    if debug and torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("rasterize(debug=True) synchronises after every launch: not inside hipGraph capture")
-    was = lib.tsplat_set_debug(1) if debug else None
-    try:
-        rc = lib.tsplat_raster_fwd(
-            desc,
-            *(_lib.ptr(t) for t in (means, covariances, harmonics, opacities)),
-            *(_lib.ptr(t) for t in cams),
-            _lib.ptr(color),
-            _lib.ptr(radii),
-            _lib.ptr(ws),
-            _lib.ptr(status),
-            _lib.stream_ptr(dev),
-        )
-    finally:
-        if was is not None:
-            lib.tsplat_set_debug(was)
-    _lib.check(rc, "tsplat_raster_fwd")
-    _STATE.last[(dev.type, dev.index)] = (ws, int(lib.tsplat_raster_num_rendered_offset(g, v, h, w)))
-    if check:
-        check_status(dev)
-    return color, radii
+    out = _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
+                     capacity, check, debug)
+    return out.color, out.radii
+
+
+def rasterize_with_depth(
+    means: Tensor,
+    covariances: Tensor,
+    harmonics: Tensor,
+    opacities: Tensor,
+    cameras: RasterCameras,
+    image_shape: tuple[int, int],
+    views_per_scene: int,
+    sh_degree: int | None = None,
+    capacity: int | None = None,
+    check: bool = True,
+    debug: bool = False,
+    *,
+    near: Tensor | None = None,
+    far: Tensor | None = None,
+    depth_mode: str | None = "depth",
+    color: bool = True,
+    alpha: bool = False,
+) -> RasterOutput:
+    """rasterize() with rendered depth and accumulated opacity from the same pass
+    (tsplat_raster_depth_fwd; replaces the second rasterizer run of the reference's
+    render_depth_cuda, cuda_splatting.py:375-417).
+
+    near / far [V]: the views' unscaled planes (what prepare_cameras took). `depth_mode`: one of
+    DEPTH_MODES -> depth [V, H, W], the reference's depth render (the blend of max(C0 f + 0.5, 0)
+    over black, f the mode's function of the camera-space depth); None: no depth. alpha=True ->
+    alpha [V, H, W] = 1 - T, the accumulated opacity. color=False skips the colours (the SH
+    coefficients are not read). Colour and radii are bit-identical to rasterize()'s.
+    """
+    if depth_mode is not None and depth_mode not in DEPTH_MODES:
+        raise ValueError(f"depth_mode {depth_mode!r}: expected one of {sorted(DEPTH_MODES)} or None")
+    want_depth = depth_mode is not None
+    if not (color or want_depth or alpha):
+        raise ValueError("rasterize_with_depth: no output asked for")
+    if want_depth and (near is None or far is None):
+        raise ValueError("a depth render needs the views' near and far planes")
+    extra = (near, far, DEPTH_MODES[depth_mode] if want_depth else 0, bool(color), want_depth, bool(alpha))
+    return _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
+                      capacity, check, debug, extra)
 
 
 def num_rendered(device) -> int:

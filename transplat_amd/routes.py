@@ -67,6 +67,7 @@ _HIP = {
     "tsplat_gaussian_adapter_fwd": ("gaussian adapter (HIP)", "fp32"),
     "tsplat_sh_rotation_fwd": ("gaussian adapter (HIP)", "fp32"),
     "tsplat_raster_fwd": ("rasterizer (HIP)", "fp32"),
+    "tsplat_raster_depth_fwd": ("rasterizer (HIP)", "fp32"),
 }
 _ORDER = ("window attention", "transformer linears (HIP)", "GEMMs (HIP)", "3x3 convs (HIP Winograd)", "direct convs (HIP)",
           "DINOv2 attention (HIP)", "U-Net attention (HIP)", "library GEMMs (hipBLASLt)", "library convs (MIOpen)",
