@@ -63,24 +63,36 @@ def test_camera_prep_matches_reference_golden():
 
 
 # ------------------------------------------------------------------ HIP kernels vs oracle
+def _map_hw(hw):
+    """(h, w) of a map given as one side (square) or as an (h, w) pair"""
+    return hw if isinstance(hw, tuple) else (hw, hw)
+
+
+# 32 x 96 in 2 x 2 windows: window width 48 (no power of two) on a non-square map, key split 4 -- every
+# shared geometry function takes its division path
+WIDE = (32, 96)
+WINATTN_CASES = [(16, 1, False, 2), (16, 1, True, 2), (16, 2, True, 2), (64, 1, False, 2), (64, 1, True, 2),
+                 (64, 2, True, 2), (32, 2, False, 2), (64, 1, True, 8), (64, 1, True, 1), (64, 1, False, 1)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["auto", "16"])
-@pytest.mark.parametrize("hw,m,shift,b", [(16, 1, False, 2), (16, 1, True, 2), (16, 2, True, 2), (64, 1, False, 2),
-                                          (64, 1, True, 2), (64, 2, True, 2), (32, 2, False, 2), (64, 1, True, 8),
-                                          (64, 1, True, 1), (64, 1, False, 1)])
+@pytest.mark.parametrize("hw,m,shift,b,variant",
+                         [(*c, v) for v in ("auto", "16") for c in WINATTN_CASES]
+                         + [pytest.param(WIDE, 1, True, 1, "auto", id="32x96-1-True-1-auto")])
 def test_window_attention_kernel(device, monkeypatch, hw, m, shift, b, variant):
     """auto: 128-query blocks as 4 waves x 32 queries (32x32x2) with the global key split + combine
-    (b = 1 / 2 at 64x64), without split at b = 8, the 64-query 16x16x4 kernel for 8x8 windows;
-    "16": the 64-query 16x16x4 kernel forced (TSPLAT_WINATTN=16) at every shape."""
+    (b = 1 / 2 at 64x64, b = 1 at 32x96), without split at b = 8, the 64-query 16x16x4 kernel for 8x8
+    windows; "16": the 64-query 16x16x4 kernel forced (TSPLAT_WINATTN=16) at every shape."""
     from transplat_amd import kernels as K
 
     if variant != "auto":
         monkeypatch.setenv("TSPLAT_WINATTN", variant)
-    q = seeded((b, hw * hw, 128), 11)
-    k = seeded((b, m, hw * hw, 128), 12) if m > 1 else seeded((b, hw * hw, 128), 12)
+    h, w = _map_hw(hw)
+    q = seeded((b, h * w, 128), 11)
+    k = seeded((b, m, h * w, 128), 12) if m > 1 else seeded((b, h * w, 128), 12)
     v = seeded(k.shape, 13)
-    ref = E.window_attention(q, k, v, hw, hw, 2, shift)
-    out = K.window_attention(q.to(device), k.to(device), v.to(device), hw, hw, 2, shift).cpu()
+    ref = E.window_attention(q, k, v, h, w, 2, shift)
+    out = K.window_attention(q.to(device), k.to(device), v.to(device), h, w, 2, shift).cpu()
     err = (out - ref).abs().max().item()
     assert err < 2e-4, err
 
@@ -458,7 +470,8 @@ def test_sh_rotation_op_matches_oracle(device):
 @pytest.mark.gpu
 @pytest.mark.parametrize("hw,m,shift,b,grow", [(64, 1, False, 2, False), (64, 1, True, 2, False), (64, 2, True, 2, False),
                                                (32, 1, True, 2, False), (64, 1, True, 8, False), (64, 1, True, 1, False),
-                                               (64, 1, True, 2, True), (64, 1, False, 1, True)])
+                                               (64, 1, True, 2, True), (64, 1, False, 1, True),
+                                               pytest.param(WIDE, 1, True, 1, False, id="32x96-1-True-1-False")])
 def test_window_attention_x3_kernel(device, hw, m, shift, b, grow):
     """bf16x3 window attention (tsplat_win_attn_x3_fwd: split-bf16 products, fp32 softmax; the C2
     step's dense-precision mode) vs the oracle in float64, relative to max(1, max |O|): within 3e-5
@@ -468,22 +481,23 @@ def test_window_attention_x3_kernel(device, hw, m, shift, b, grow):
     ~10^2 -- the score error scales with the logits (measured 5.6e-5 there), hence 2e-4."""
     from transplat_amd import kernels as K
 
-    q = seeded((b, hw * hw, 128), 51) * (3.0 if grow else 1.0)
-    k = seeded((b, m, hw * hw, 128), 52) if m > 1 else seeded((b, hw * hw, 128), 52)
+    h, w = _map_hw(hw)
+    q = seeded((b, h * w, 128), 51) * (3.0 if grow else 1.0)
+    k = seeded((b, m, h * w, 128), 52) if m > 1 else seeded((b, h * w, 128), 52)
     if grow:
-        ys, xs = torch.meshgrid(torch.arange(hw), torch.arange(hw), indexing="ij")
-        t = ((ys % (hw // 2)) * (hw // 2) + xs % (hw // 2)).reshape(-1).float() / (hw * hw / 4)
+        ys, xs = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
+        t = ((ys % (h // 2)) * (w // 2) + xs % (w // 2)).reshape(-1).float() / (h * w / 4)
         k = k * (0.25 + 3.75 * t)[None, :, None]
     v = seeded(k.shape, 53)
-    ref = E.window_attention(q.double(), k.double(), v.double(), hw, hw, 2, shift)
-    out = K.window_attention_x3(q.to(device), k.to(device), v.to(device), hw, hw, 2, shift).cpu().double()
+    ref = E.window_attention(q.double(), k.double(), v.double(), h, w, 2, shift)
+    out = K.window_attention_x3(q.to(device), k.to(device), v.to(device), h, w, 2, shift).cpu().double()
     scale = max(1.0, ref.abs().max().item())
     err = (out - ref).abs().max().item() / scale
     def tf(t):  # fp32 -> TF32 (10 explicit mantissa bits, round to nearest even)
         i = t.float().contiguous().view(torch.int32)
         return ((i + 0xFFF + ((i >> 13) & 1)) & ~0x1FFF).view(torch.float32).double()
 
-    ref_tf = E.window_attention(tf(q), tf(k), tf(v), hw, hw, 2, shift)
+    ref_tf = E.window_attention(tf(q), tf(k), tf(v), h, w, 2, shift)
     err_tf = (ref_tf - ref).abs().max().item() / scale
     print(f"x3 attention hw={hw} m={m} shift={shift} b={b} grow={grow}: rel err {err:.2e}, TF32 operands {err_tf:.2e}")
     assert err < (2e-4 if grow else 3e-5) and err <= err_tf / 8, (err, err_tf)
@@ -739,7 +753,8 @@ def test_fused_linear_kernel(device, m, k1, k2, n, gelu, ln, res, split, bias, g
                                                   (64, 2, True, 3, True, 0), (32, 1, True, 2, False, 0),
                                                   (64, 1, True, 8, True, 0), (64, 1, True, 2, True, 1),
                                                   (64, 1, False, 4, False, 2), (64, 1, True, 8, False, 4),
-                                                  (64, 1, True, 1, True, 0)])
+                                                  (64, 1, True, 1, True, 0),
+                                                  pytest.param(WIDE, 1, True, 1, True, 0, id="32x96-1-True-1-True-0")])
 @pytest.mark.parametrize("dense", ["fp32", "bf16x3"])
 def test_attention_merge_kernel(device, monkeypatch, hw, m, shift, b, res, kvs, dense):
     """Window attention + merge Linear + LayerNorm (+ residual) with the split-key combine folded
@@ -749,18 +764,19 @@ def test_attention_merge_kernel(device, monkeypatch, hw, m, shift, b, res, kvs, 
     from transplat_amd import _lib
     from transplat_amd import kernels as K
 
-    q = seeded((b, hw * hw, 128), 41)
-    k = seeded((b, m, hw * hw, 128), 42) if m > 1 else seeded((b, hw * hw, 128), 42)
+    h, w = _map_hw(hw)
+    q = seeded((b, h * w, 128), 41)
+    k = seeded((b, m, h * w, 128), 42) if m > 1 else seeded((b, h * w, 128), 42)
     v = seeded(k.shape, 43)
     wm = seeded((128, 128), 44) / math.sqrt(128)
     ln = (seeded((128,), 45) * 0.1 + 1.0, seeded((128,), 46) * 0.1, 1e-5)
-    r = seeded((b, hw * hw, 128), 47) if res else None
-    ks = int(_lib.load().tsplat_win_attn_split(b, hw, hw, m, 2))
+    r = seeded((b, h * w, 128), 47) if res else None
+    ks = int(_lib.load().tsplat_win_attn_split(b, h, w, m, 2))
     assert (ks > 1) == (b < 8)
-    ref = E.attention_merge(q, k, v, hw, hw, 2, shift, wm, ln, residual=r, kv_shift=kvs)
+    ref = E.attention_merge(q, k, v, h, w, 2, shift, wm, ln, residual=r, kv_shift=kvs)
     d = lambda t: t.to(device) if t is not None else None
     with K.dense_precision(dense):
-        out = K.attention_merge(d(q), d(k), d(v), hw, hw, 2, shift, d(wm), (d(ln[0]), d(ln[1]), ln[2]),
+        out = K.attention_merge(d(q), d(k), d(v), h, w, 2, shift, d(wm), (d(ln[0]), d(ln[1]), ln[2]),
                                 residual=d(r), kv_shift=kvs)
     err = (out.cpu() - ref).abs().max().item()
     assert err < 1e-3, err

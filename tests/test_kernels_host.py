@@ -183,3 +183,101 @@ def test_launch_shapes_match_previous_loops(zi, monkeypatch, default_shape_knobs
         assert K._conv_x3_shape(tiles, units) == want[zi], (tiles, units)
     for (tiles, pairs), want in NHWC.items():
         assert [K._wave_split(tiles, pairs, 4096, 2), K._wave_split(tiles, pairs, 4096, 16)] == want
+
+
+# ---- window attention: the launch plan through its C entry points (the library loads without a GPU)
+WINATTN_SHAPES = {  # (b, h, w, key views, splits) -> key split of the exact-fp32 128-query kernel
+    (1, 64, 64, 1, 2): 8,
+    (2, 64, 64, 1, 2): 4,
+    (8, 64, 64, 1, 2): 1,
+    (1, 96, 128, 2, 2): 4,
+    (1, 32, 96, 1, 2): 4,
+    (2, 16, 16, 1, 2): 0,  # L = 64: another kernel serves it
+}
+WINATTN_KNOBS = ("TSPLAT_WINATTN", "TSPLAT_WINATTN_KSPLIT", "TSPLAT_WINATTN_BF16", "TSPLAT_WINATTN_X3",
+                 "TSPLAT_WINATTN_X3_PRIO", "TSPLAT_WINATTN_X3_XCD")
+
+
+def _choose_ksplit(base, key_tiles, target):
+    ks = 1
+    while base * ks < target and ks * 2 <= key_tiles and key_tiles % (ks * 2) == 0 and ks < 8:
+        ks *= 2
+    return ks
+
+
+def _winattn_bytes(shape, ks):
+    b, h, w, m, s = shape
+    return b * s * s * ks * (h // s) * (w // s) * 130 * 4 if ks > 1 else 0
+
+
+@pytest.fixture
+def winattn_lib(monkeypatch):
+    from transplat_amd import _lib
+    for name in WINATTN_KNOBS:
+        monkeypatch.delenv(name, raising=False)
+    return _lib.load()
+
+
+@pytest.mark.parametrize("shape", WINATTN_SHAPES)
+def test_win_attn_split_and_workspace_agree(shape, winattn_lib, monkeypatch):
+    lib = winattn_lib
+    b, h, w, m, s = shape
+    L = (h // s) * (w // s)
+    tiles = L * m // 64
+    ks = WINATTN_SHAPES[shape]
+    assert lib.tsplat_win_attn_split(*shape) == ks
+    assert ks == (_choose_ksplit(L // 128 * s * s * b, tiles, 256) if L % 128 == 0 else 0)
+    # L = 64 runs the 64-query kernel: its own split (two workgroups per CU), never reported by _split
+    ks_ws = ks if ks else _choose_ksplit(L // 64 * s * s * b, tiles, 512)
+    assert lib.tsplat_win_attn_workspace_bytes(*shape) == _winattn_bytes(shape, ks_ws)
+    assert K._win_attn_workspace_bytes(lib, "x3", *shape) == K._win_attn_workspace_bytes(lib, "fp32", *shape)
+    bf16_bytes = lib.tsplat_win_attn_bf16_workspace_bytes(*shape)
+    assert bf16_bytes == (_winattn_bytes(shape, _choose_ksplit(L // 128 * s * s * b, tiles, 512)) if L % 128 == 0 else 0)
+
+    monkeypatch.setenv("TSPLAT_WINATTN_KSPLIT", "2")
+    forced = 2 if tiles % 2 == 0 else None
+    assert lib.tsplat_win_attn_split(*shape) == ((forced or ks) if L % 128 == 0 else 0)
+    assert lib.tsplat_win_attn_workspace_bytes(*shape) == _winattn_bytes(shape, forced or ks_ws)
+    assert K._win_attn_workspace_bytes(lib, "x3", *shape) == K._win_attn_workspace_bytes(lib, "fp32", *shape)
+    assert lib.tsplat_win_attn_bf16_workspace_bytes(*shape) == bf16_bytes  # the bf16 family has no forced split
+    monkeypatch.delenv("TSPLAT_WINATTN_KSPLIT")
+
+    monkeypatch.setenv("TSPLAT_WINATTN", "16")
+    assert lib.tsplat_win_attn_split(*shape) == 0  # 0 whenever the knob is set at all
+    ks16 = _choose_ksplit(L // 64 * s * s * b, tiles, 512)  # the 64-query rule
+    assert lib.tsplat_win_attn_workspace_bytes(*shape) == _winattn_bytes(shape, ks16)
+    assert K._win_attn_workspace_bytes(lib, "x3", *shape) == K._win_attn_workspace_bytes(lib, "fp32", *shape)
+    monkeypatch.setenv("TSPLAT_WINATTN", "32")
+    assert lib.tsplat_win_attn_split(*shape) == 0
+    assert lib.tsplat_win_attn_workspace_bytes(*shape) == _winattn_bytes(shape, ks_ws)
+
+
+def test_win_attn_rejects_what_it_rejected(winattn_lib):
+    lib = winattn_lib
+    for bad in ((0, 64, 64, 1, 2), (1, 64, 64, 0, 2), (1, 64, 64, 1, 0), (1, 63, 64, 1, 2), (1, 64, 66, 1, 2),
+                (1, 24, 24, 1, 2)):  # L = 144: no multiple of 64
+        assert lib.tsplat_win_attn_split(*bad) == 0
+        assert lib.tsplat_win_attn_workspace_bytes(*bad) == 0
+        assert lib.tsplat_win_attn_bf16_workspace_bytes(*bad) == 0
+    # null pointers are refused before any launch, so these calls need no GPU
+    assert lib.tsplat_win_attn_fwd(None, None, None, None, None, 1, 64, 64, 128, 1, 2, 1, None) != 0
+    assert lib.tsplat_win_attn_partials_fwd(None, None, None, None, 1, 64, 64, 128, 1, 2, 1, 0, None) != 0
+    assert lib.tsplat_win_attn_x3_fwd(None, None, None, None, 1, 64, 64, 128, 1, 2, 1, None) != 0
+
+
+def test_win_attn_layout_round_trip(tmp_path):
+    """winattn_layout.h as host C++: the pixel map and its inverse, and the partials indices tiling the
+    workspace (tests/winattn_layout_check.cc), on 16x16, 32x96 (window width 48) and 96x128 maps."""
+    import shutil
+    import subprocess
+    from pathlib import Path
+    here = Path(__file__).resolve().parent
+    cxx = next((c for c in map(shutil.which, ("c++", "g++", "clang++")) if c), None)
+    if cxx is None:  # the HIP compiler the build needs anyway brings a host clang++
+        from transplat_amd import build
+        cxx = str(Path(build._hipcc()).resolve().parent.parent / "lib" / "llvm" / "bin" / "clang++")
+    exe = tmp_path / "winattn_layout_check"
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", f"-I{here.parent / 'transplat_amd' / 'csrc'}",
+                    str(here / "winattn_layout_check.cc"), "-o", str(exe)], check=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "mfma.h"
 #include "prof.h"
+#include "winattn_layout.h"
 
 namespace tsplat {
 namespace linear {
@@ -50,12 +51,10 @@ struct Args {
     long long split_stride;
     float eps;
     int k1, k2, M, N, flags;
-    // X = combined split-key attention partials (tsplat_win_attn_partials_fwd layout), see
-    // tsplat_linear_f32_attn_merge_fwd: o / m / l arrays and the window geometry
-    const float* po;
-    const float* pm;
-    const float* pl;
-    int aks, aH, aW, aS, aL, awh, aww, ash, asw;
+    // X = combined split-key attention partials (tsplat_win_attn_partials_fwd's, read only), see
+    // tsplat_linear_f32_attn_merge_fwd: the o / m / l arrays and the launch's windows and key split
+    winattn::Partials part;
+    winattn::Window win;
     // kSplit outputs from column block x3_from on go to kv_x3 as bf16 hi / lo pairs (x = hi + lo):
     // block x3_from + i -> hi at kv_x3 + 2 i M 128, lo at kv_x3 + (2 i + 1) M 128 (the K / V operands
     // of tsplat_win_attn_x3_*); x3_from < 0: none
@@ -66,36 +65,33 @@ struct Args {
 constexpr int kMaxSplit = 8;
 
 // Per-thread source of one X row when X is the attention output still split over key ranges:
-// float offset of (row, split 0, this query's lane) in o, the split stride, the combine weights
+// float offset in o of this query's float4 run in the wave slot of key split 0 (winattn_layout.h),
+// and the combine weights
 struct AttnRow {
     size_t obase;
     float w[kMaxSplit];
 };
 
 __device__ __forceinline__ void attn_row(const Args& a, int m, AttnRow& r) {
-    const int HW = a.aH * a.aW;
-    const int b = m / HW, pix = m - b * HW;
-    const int y = pix / a.aW, x = pix - y * a.aW;
-    int Y = y - a.ash, X = x - a.asw;  // position on the rolled grid (the attention rolled by -shift)
-    if (Y < 0) Y += a.aH;
-    if (X < 0) X += a.aW;
-    const int sy = Y / a.awh, sx = X / a.aww;
-    const int wi = sy * a.aS + sx, t = (Y - sy * a.awh) * a.aww + (X - sx * a.aww);
-    const size_t win = (size_t)b * a.aS * a.aS + wi;
-    const int nqb = a.aL / 128;
-    r.obase = ((win * a.aks * nqb + (t >> 7)) * 128 + 32 * ((t >> 5) & 3)) * 128 + 4 * (t & 31);
+    const winattn::Window& g = a.win;
+    const int HW = g.H * g.W;
+    const int b = m / HW;
+    int wi, t, qblk, wid, c;
+    winattn::win_locate(g, m - b * HW, wi, t);
+    winattn::tile_query_split(t, qblk, wid, c);
+    r.obase = winattn::lane_tile_base(g, b, wi, 0, qblk, wid) + 4 * winattn::slot_float4(0, 0, c);
     float mx = -INFINITY;
 #pragma unroll
     for (int s = 0; s < kMaxSplit; ++s)
-        if (s < a.aks) mx = fmaxf(mx, a.pm[(win * a.aks + s) * a.aL + t]);
+        if (s < g.ksplit) mx = fmaxf(mx, a.part.m[winattn::pidx(g, b, wi, s, t)]);
     float L = 0.f;
 #pragma unroll
     for (int s = 0; s < kMaxSplit; ++s) {
         r.w[s] = 0.f;
-        if (s < a.aks) {
-            const size_t row = (win * a.aks + s) * a.aL + t;
-            r.w[s] = __expf(a.pm[row] - mx);
-            L += r.w[s] * a.pl[row];
+        if (s < g.ksplit) {
+            const size_t row = winattn::pidx(g, b, wi, s, t);
+            r.w[s] = __expf(a.part.m[row] - mx);
+            L += r.w[s] * a.part.l[row];
         }
     }
     const float inv = 1.0f / L;
@@ -103,15 +99,15 @@ __device__ __forceinline__ void attn_row(const Args& a, int m, AttnRow& r) {
     for (int s = 0; s < kMaxSplit; ++s) r.w[s] *= inv;
 }
 
-// channels k .. k+3 of the combined attention row: O^T[d][q] float4 (dt * 4 + u) * 64 + lane of
-// the wave slot holds d = 32 dt + 8 u + 4 h + (0..3) for lane = q + 32 h
+// channels k .. k+3 of the combined attention row: their float4 of the query's wave slot, summed over
+// the key splits
 __device__ __forceinline__ floatx4 attn_x4(const Args& a, const AttnRow& r, int k) {
-    const size_t sstride = (size_t)(a.aL / 128) * 128 * 128;
-    const size_t off = r.obase + ((size_t)(((k >> 5) * 4 + ((k >> 3) & 3)) * 64 + 32 * ((k >> 2) & 1))) * 4;
+    const size_t sstride = winattn::lane_tile_split_stride(a.win);
+    const size_t off = r.obase + (size_t)winattn::slot_float4_of_channel(k, 0) * 4;
     floatx4 acc = (floatx4)(0.f);
 #pragma unroll
     for (int s = 0; s < kMaxSplit; ++s)
-        if (s < a.aks) acc += r.w[s] * *reinterpret_cast<const floatx4*>(a.po + off + s * sstride);
+        if (s < a.win.ksplit) acc += r.w[s] * *reinterpret_cast<const floatx4*>(a.part.o + off + s * sstride);
     return acc;
 }
 
@@ -497,7 +493,7 @@ extern "C" int tsplat_linear_f32_fwd(const float* x1, int32_t k1, const float* x
     if ((flags & kXBf16) && (k2 > 0 || ((uintptr_t)x1 & 7))) return TSPLAT_EINVAL;
     if ((flags & kOutBf16) && ((flags & kResidual) || ((uintptr_t)out & 7))) return TSPLAT_EINVAL;
     Args a{x1, x2, w, bias, ln_gamma, ln_beta, residual, out, split_stride, ln_eps, k1, k2, M, N, flags};
-    a.po = a.pm = a.pl = nullptr;
+    a.part = winattn::Partials{nullptr, nullptr, nullptr};
     a.kv_x3 = nullptr;
     a.x3_from = -1;
     return launch_linear(a, stream_);
@@ -515,7 +511,7 @@ extern "C" int tsplat_linear_f32_split_x3_fwd(const float* x1, int32_t k1, const
     if (((uintptr_t)kv_x3) & 7) return TSPLAT_EINVAL;
     Args a{x1, nullptr, w, nullptr, nullptr, nullptr, nullptr, out, (long long)M * kBN, 0.f, k1, 0, M, N,
            flags | kSplit};
-    a.po = a.pm = a.pl = nullptr;
+    a.part = winattn::Partials{nullptr, nullptr, nullptr};
     a.kv_x3 = (__bf16*)kv_x3;
     a.x3_from = x3_from;
     return launch_linear(a, stream_);
@@ -553,9 +549,6 @@ static int launch_linear(tsplat::linear::Args a, void* stream_) {
     return TSPLAT_OK;
 }
 
-extern "C" int32_t tsplat_win_attn_split(int32_t batch, int32_t height, int32_t width, int32_t key_views,
-                                         int32_t splits);
-
 extern "C" int tsplat_linear_f32_attn_merge_fwd(const float* partials, int32_t batch, int32_t height, int32_t width,
                                                 int32_t key_views, int32_t splits, int32_t with_shift,
                                                 const float* w, const float* ln_gamma, const float* ln_beta,
@@ -573,19 +566,8 @@ extern "C" int tsplat_linear_f32_attn_merge_fwd(const float* partials, int32_t b
     Args a{nullptr, nullptr, w, nullptr, ln_gamma, ln_beta, residual, out, 0, ln_eps, kBN, 0, M, N, flags};
     a.kv_x3 = nullptr;
     a.x3_from = -1;
-    a.aks = ks;
-    a.aH = height;
-    a.aW = width;
-    a.aS = splits;
-    a.awh = height / splits;
-    a.aww = width / splits;
-    a.aL = a.awh * a.aww;
-    a.ash = with_shift ? a.awh / 2 : 0;
-    a.asw = with_shift ? a.aww / 2 : 0;
-    const size_t n = (size_t)batch * splits * splits * ks * a.aL;
-    a.po = partials;
-    a.pm = partials + n * kBN;
-    a.pl = a.pm + n;
+    winattn::fill_window(a.win, height, width, splits, key_views, with_shift, ks);
+    a.part = winattn::carve_partials(a.win, batch, const_cast<float*>(partials));
     hipStream_t stream = (hipStream_t)stream_;
     TSPLAT_PROF_BEGIN(prof::kLinear, stream);
     if (flags & kBf16x3)

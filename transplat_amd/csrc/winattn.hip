@@ -28,6 +28,7 @@
 #include "common.h"
 #include "mfma.h"
 #include "prof.h"
+#include "winattn_layout.h"
 
 namespace tsplat {
 namespace winattn {
@@ -89,38 +90,16 @@ __device__ unsigned long long* g_wa_stamps = nullptr;
 #define WA_STAMP(slot, val) do {} while (0)
 #endif
 
-constexpr int kC = 128;          // channels (d_model of the reference transformer)
 constexpr int kBQ = 64;          // queries per workgroup
 constexpr int kBK = 64;          // keys per LDS tile
 constexpr int kThreads = 256;
 constexpr int kVStride = kC + 4;  // padded V row (floats)
 
-struct Params {
-    int H, W, splits, shift, m, L;  // L = window pixels; shift != 0: shifted (masked) layer
-    int shift_h, shift_w;           // roll of the shifted layer: half a window per axis
-    int ksplit, keys_per_split;     // key range [s * keys_per_split, (s+1) * keys_per_split)
-    int wh, ww, ww_log2;            // window rows / columns; log2(ww), or -1 if not a power of 2
-    int kv_shift, nbatch;           // keys / values of query batch b come from batch (b + kv_shift) % nbatch
+// kernel arguments: the launch's windows and key split (winattn_layout.h) and the batch pairing
+struct Params : Window {
+    int kv_shift, nbatch;  // keys / values of query batch b come from batch (b + kv_shift) % nbatch
     float scale;
 };
-
-// t / ww and t % ww without a per-lane integer division when the window width is a power of 2
-__device__ __forceinline__ void win_split(const Params& p, int t, int& ty, int& tx) {
-    ty = p.ww_log2 >= 0 ? (t >> p.ww_log2) : t / p.ww;
-    tx = t - ty * p.ww;
-}
-
-// split-key partials of one workgroup (64 queries): O (unnormalised, [64][128]), m, l
-struct Partials {
-    float* o;
-    float* m;
-    float* l;
-};
-
-// row of query t (in-window index) of window wi, batch b, key split ks in the partial arrays
-__device__ __forceinline__ size_t pidx(const Params& p, int b, int wi, int ks, int t) {
-    return (((size_t)b * p.splits * p.splits + wi) * p.ksplit + ks) * p.L + t;
-}
 
 // Logical (x, y, z) of this workgroup after the bijective XCD remap of its linear id: the
 // dispatcher deals consecutive ids round-robin over the 8 XCDs, so without the remap the query
@@ -134,27 +113,60 @@ __device__ __forceinline__ void xcd_block_coords(int& x, int& y, int& z) {
     z = m / (X * Y);
 }
 
-// original pixel of in-window position t of window wi after the roll by -shift
-__device__ __forceinline__ int win_pixel(const Params& p, int wi, int t) {
-    const int sy = wi / p.splits, sx = wi - sy * p.splits;
-    int ty, tx;
-    win_split(p, t, ty, tx);
-    int y = sy * p.wh + ty + p.shift_h;
-    int x = sx * p.ww + tx + p.shift_w;
-    if (y >= p.H) y -= p.H;
-    if (x >= p.W) x -= p.W;
-    return y * p.W + x;
+__device__ __forceinline__ void store4(float* dst, float4 v) { *reinterpret_cast<float4*>(dst) = v; }
+__device__ __forceinline__ void store4(__bf16* dst, float4 v) {
+    *reinterpret_cast<bf16x4*>(dst) = bf16x4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
 }
 
-// Swin region id of in-window position t of window wi (on the rolled grid)
-__device__ __forceinline__ int win_region(const Params& p, int wi, int t) {
-    const int sy = wi / p.splits, sx = wi - sy * p.splits;
-    int ty, tx;
-    win_split(p, t, ty, tx);
-    const int Y = sy * p.wh + ty, X = sx * p.ww + tx;
-    const int by = Y < p.H - p.wh ? 0 : (Y < p.H - p.wh / 2 ? 1 : 2);
-    const int bx = X < p.W - p.ww ? 0 : (X < p.W - p.ww / 2 ? 1 : 2);
-    return by * 3 + bx;
+// batch whose keys / values query batch b attends to (the exact-fp32 kernels; the bf16 and bf16x3
+// kernels take the remainder unconditionally -- this form costs them 1 to 4 instructions)
+__device__ __forceinline__ int kv_batch(const Params& p, int b) {
+    return p.kv_shift ? (b + p.kv_shift) % p.nbatch : b;
+}
+
+// row max of a 2 x 16-score tile as a v_maximum3 tree (16 instructions for 32 scores)
+__device__ __forceinline__ float tile_max32(const floatx16& s0, const floatx16& s1) {
+    float bmax = max3_raw(s0[0], s1[0], s0[1]);
+    bmax = max3_raw(bmax, s1[1], s0[2]);
+#pragma unroll
+    for (int r = 2; r < 15; ++r) bmax = max3_raw(bmax, s1[r], s0[r + 1]);
+    return fmaxf(bmax, s1[15]);
+}
+
+// Epilogue of the 128-query kernels with one wave per 32 queries: this lane's accumulators,
+// O^T[d = 32 dt + 8u + 4h + j][q = c] in o[dt][4u + j] (lane = c + 32 h, query tq of the window, at
+// pixel qpix of the batch's HW = H * W). Normalised rows go to out[b][qpix]; a key split's partial
+// goes lane-contiguously into the wave slot (one 1-KB run per store instruction), and the h == 0
+// lanes leave its running max -- natural-log domain for the combine -- and sum. (HW and h are passed,
+// not re-derived from p and lane: re-deriving them changes the callers' register allocation.)
+template <typename OutT>
+__device__ __forceinline__ void store_o_tiles(const Params& p, const floatx16 (&o)[4], float m_run, float l_run,
+                                              bool partial, OutT* out, const Partials& part, int b, int wi, int ks,
+                                              int qblk, int wid, int tq, int qpix, size_t HW, int lane, int h) {
+    if (!partial) {
+        const float inv = 1.0f / l_run;
+        OutT* dst = out + ((size_t)b * HW + qpix) * kC + 4 * h;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                store4(dst + 32 * dt + 8 * u, make_float4(o[dt][4 * u] * inv, o[dt][4 * u + 1] * inv,
+                                                          o[dt][4 * u + 2] * inv, o[dt][4 * u + 3] * inv));
+    } else {
+        const size_t row = pidx(p, b, wi, ks, tq);
+        float4* dst =
+            reinterpret_cast<float4*>(part.o + lane_tile_base(p, b, wi, ks, qblk, wid)) + slot_float4(0, 0, lane);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                dst[slot_float4(dt, u, 0)] =
+                    make_float4(o[dt][4 * u], o[dt][4 * u + 1], o[dt][4 * u + 2], o[dt][4 * u + 3]);
+        if (h == 0) {
+            part.m[row] = m_run * kLn2;
+            part.l[row] = l_run;
+        }
+    }
 }
 
 // key j of a window (pixel-major, view-minor over m key views): offset of its row in the
@@ -214,7 +226,7 @@ win_attn_f32_kernel(Params p, const float* __restrict__ q, const float* __restri
     const int g = lane >> 4, ql = lane & 15;
     const size_t HW = (size_t)p.H * p.W;
     const float* qb = q + (size_t)b * HW * kC;
-    const int bkv = p.kv_shift ? (b + p.kv_shift) % p.nbatch : b;
+    const int bkv = kv_batch(p, b);
     const float* kb = k + (size_t)bkv * p.m * HW * kC;
     const float* vb = v + (size_t)bkv * p.m * HW * kC;
 
@@ -343,10 +355,6 @@ win_attn_f32_kernel(Params p, const float* __restrict__ q, const float* __restri
 // combine the ksplit partials of each query: out = sum_s e^(m_s - M) O_s / sum_s e^(m_s - M) l_s
 // grid (L / 8, windows, batch); 32 threads per query, one float4 of channels each (1024+
 // workgroups for the 2-view map: the partials are the only HBM/MALL traffic of the split)
-__device__ __forceinline__ void store4(float* dst, float4 v) { *reinterpret_cast<float4*>(dst) = v; }
-__device__ __forceinline__ void store4(__bf16* dst, float4 v) {
-    *reinterpret_cast<bf16x4*>(dst) = bf16x4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-}
 
 template <typename OutT>
 __global__ void __launch_bounds__(kThreads)
@@ -373,14 +381,6 @@ win_attn_combine_kernel(Params p, Partials part, OutT* __restrict__ out) {
     store4(out + ((size_t)b * HW + qpix) * kC + 4 * c4, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
 }
 
-// x32 / bf16 kernels store each wave's unnormalised O^T tile lane-contiguously: float4 number
-// (dt * 4 + u) * 64 + lane of the wave's 16-KB slot holds O^T[d = 32 dt + 8u + 4h .. +3][query c]
-// (lane = c + 32 h). Slot of (b, wi, ks, query block, wave) in the partial buffer (floats):
-__device__ __forceinline__ size_t lane_tile_base(const Params& p, int b, int wi, int ks, int qblk, int wid) {
-    const size_t nqb = (size_t)p.L / 128;
-    return ((((size_t)b * p.splits * p.splits + wi) * p.ksplit + ks) * nqb + qblk) * 128 * kC + (size_t)wid * 32 * kC;
-}
-
 // combine for the lane-contiguous layout: grid (L / 128 * 16, windows, batch), 256 threads; a
 // workgroup owns 256 consecutive float4s of one 128-query block (one wave slot's quarter, i.e.
 // 32 queries): it forms those queries' weights e^(m_s - M) / L in LDS, then reads every partial
@@ -392,11 +392,13 @@ win_attn_combine_x32_kernel(Params p, Partials part, OutT* __restrict__ out) {
     const int qblk = blockIdx.x >> 4, part16 = blockIdx.x & 15, wi = blockIdx.y, b = blockIdx.z;
     const int t = threadIdx.x;
     const int idx = part16 * kThreads + t;  // float4 index within the 128-query block
-    const int wid = idx >> 10, rem = idx & 1023, du = rem >> 6, lane = rem & 63;
-    const int c = lane & 31, h = lane >> 5, dt = du >> 2, u = du & 3;
+    const int wid = idx / kSlotFloat4;  // the block's four wave slots are consecutive
+    int dt, u, lane;
+    slot_float4_split(idx % kSlotFloat4, dt, u, lane);
+    const int c = lane & 31, h = lane >> 5;
     const size_t HW = (size_t)p.H * p.W;
     if (t < 32) {
-        const int tq = qblk * 128 + wid * 32 + t;
+        const int tq = tile_query(qblk, wid, t);
         float M = -INFINITY;
         for (int s = 0; s < p.ksplit; ++s) M = fmaxf(M, part.m[pidx(p, b, wi, s, tq)]);
         float L = 0.f;
@@ -419,7 +421,7 @@ win_attn_combine_x32_kernel(Params p, Partials part, OutT* __restrict__ out) {
         acc.z += w * v.z;
         acc.w += w * v.w;
     }
-    const int qpix = win_pixel(p, wi, qblk * 128 + wid * 32 + c);
+    const int qpix = win_pixel(p, wi, tile_query(qblk, wid, c));
     store4(out + ((size_t)b * HW + qpix) * kC + 32 * dt + 8 * u + 4 * h, acc);
 }
 
@@ -459,7 +461,7 @@ win_attn_f32x32_kernel(Params p, const float* __restrict__ q, const float* __res
     const int c = lane & 31, h = lane >> 5;
     const size_t HW = (size_t)p.H * p.W;
     const float* qb = q + (size_t)b * HW * kC;
-    const int bkv = p.kv_shift ? (b + p.kv_shift) % p.nbatch : b;
+    const int bkv = kv_batch(p, b);
     const float* kb = k + (size_t)bkv * p.m * HW * kC;
     const float* vb = v + (size_t)bkv * p.m * HW * kC;
 
@@ -578,13 +580,7 @@ win_attn_f32x32_kernel(Params p, const float* __restrict__ q, const float* __res
                     s[sub][4 * u + 3] += rg.w == qreg ? 0.0f : kMaskLog2;
                 }
         }
-        // row max as a v_max3 tree (16 instructions for 32 scores)
-        float bmax = max3_raw(s[0][0], s[1][0], s[0][1]);
-        bmax = max3_raw(bmax, s[1][1], s[0][2]);
-#pragma unroll
-        for (int r = 2; r < 15; ++r) bmax = max3_raw(bmax, s[1][r], s[0][r + 1]);
-        bmax = fmaxf(bmax, s[1][15]);
-        bmax = halves_max(bmax);
+        const float bmax = halves_max(tile_max32(s[0], s[1]));
         const float m_new = fmaxf(m_run, bmax);
         if (__any(m_new > m_run)) {  // exact: corr == 1 for every lane otherwise
             const float corr = fast_exp2(m_run - m_new);
@@ -637,31 +633,7 @@ win_attn_f32x32_kernel(Params p, const float* __restrict__ q, const float* __res
         if ((k0 - kbeg) / kBK < 8) WA_STAMP(4 + (k0 - kbeg) / kBK, WA_CLOCK());
     }
 
-    // O^T[d = 32 dt + 8u + 4h + j][q = c] in o[dt][4u + j]
-    if (p.ksplit == 1) {
-        const float inv = 1.0f / l_run;
-        float* dst = out + ((size_t)b * HW + qpix) * kC + 4 * h;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                *reinterpret_cast<float4*>(dst + 32 * dt + 8 * u) =
-                    make_float4(o[dt][4 * u] * inv, o[dt][4 * u + 1] * inv, o[dt][4 * u + 2] * inv,
-                                o[dt][4 * u + 3] * inv);
-    } else {
-        // lane-contiguous partial tile: each store instruction writes one 1-KB run
-        const size_t row = pidx(p, b, wi, ks, tq);
-        float4* dst = reinterpret_cast<float4*>(part.o + lane_tile_base(p, b, wi, ks, qblk, wid)) + lane;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                dst[(dt * 4 + u) * 64] = make_float4(o[dt][4 * u], o[dt][4 * u + 1], o[dt][4 * u + 2], o[dt][4 * u + 3]);
-        if (h == 0) {
-            part.m[row] = m_run * kLn2;  // natural-log domain for the combine
-            part.l[row] = l_run;
-        }
-    }
+    store_o_tiles(p, o, m_run, l_run, p.ksplit != 1, out, part, b, wi, ks, qblk, wid, tq, qpix, HW, lane, h);
     WA_STAMP(12, WA_CLOCK());
     WA_STAMP(13, wall_clock64());
 }
@@ -694,6 +666,19 @@ constexpr int kVtStrideH = kBK + 8;  // transposed V row (bf16 elements)
 constexpr float kThr = 8.0f;             // deferred-rescale threshold (log2 units): P <= 256
 constexpr float kMaskBonus = 1128.0f;    // bf16-exact; x 1/sqrt(128) = 99.7 (reference: 100)
 
+// deferred rescale: the running max follows the tile's max bm2 (log2 units) only once some lane's
+// exceeds it by more than kThr, a wave-uniform branch; then l and O are rescaled to the new max
+__device__ __forceinline__ void rescale_if_grown(float bm2, float& m_run, float& l_run, floatx16 (&o)[4]) {
+    if (__any(bm2 > m_run + kThr)) {
+        const float m_new = fmaxf(m_run, bm2);
+        const float corr = fast_exp2(m_run - m_new);
+        l_run *= corr;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o[dt] *= corr;
+        m_run = m_new;
+    }
+}
+
 // The bf16x3 kernels' mask step carries the reference's 100 to fp32 precision instead: where the
 // scores themselves span +-100 (a different-region key whose raw score is 100 above the others is
 // a live softmax term, not a zero), 99.7 for 100 is a 35 % error of that key's weight. A window holds
@@ -709,7 +694,11 @@ constexpr unsigned kMaskB01 = 0x3F803F80u;  // bf16 (1, 1)
 constexpr unsigned kMaskB23 = 0x00003F80u;  // bf16 (1, 0)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// region of in-window position t within its window wi: 2 [by == 2] + [bx == 2] (see win_region)
+// region of in-window position t within its window wi: 2 [by == 2] + [bx == 2]. Not win_region
+// (winattn_layout.h): that numbers the map's nine Swin regions 3 by + bx, bands 0 / 1 / 2 per axis;
+// this one numbers only the at most four regions that meet inside one window (bands 0 and 1 never
+// share a window), which is what the bf16x3 mask step's four k-slot groups hold. Equal within a
+// window exactly where win_region is equal.
 __device__ __forceinline__ int win_region_local(const Params& p, int wi, int t) {
     const int sy = wi / p.splits, sx = wi - sy * p.splits;
     int ty, tx;
@@ -846,20 +835,7 @@ win_attn_bf16_v2_kernel(Params p, const __bf16* __restrict__ q, const __bf16* __
         }
         // ---- online softmax (fp32, log2 domain), deferred rescale
         if (kAbl2 != 1) {
-        float bmax = max3_raw(s[0][0], s[1][0], s[0][1]);
-        bmax = max3_raw(bmax, s[1][1], s[0][2]);
-#pragma unroll
-        for (int r = 2; r < 15; ++r) bmax = max3_raw(bmax, s[1][r], s[0][r + 1]);
-        bmax = fmaxf(bmax, s[1][15]);
-        const float bm2 = halves_max(bmax) * cl2;
-        if (__any(bm2 > m_run + kThr)) {
-            const float m_new = fmaxf(m_run, bm2);
-            const float corr = fast_exp2(m_run - m_new);
-            l_run *= corr;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[dt] *= corr;
-            m_run = m_new;
-        }
+        rescale_if_grown(halves_max(tile_max32(s[0], s[1])) * cl2, m_run, l_run, o);
         float bsum = 0.f;
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub)
@@ -904,29 +880,7 @@ win_attn_bf16_v2_kernel(Params p, const __bf16* __restrict__ q, const __bf16* __
         __syncthreads();
     }
 
-    // O^T[d = 32 dt + 8u + 4h + j][q = c] in o[dt][4u + j]
-    if (p.ksplit == 1) {
-        const float inv = 1.0f / l_run;
-        __bf16* dst = out + ((size_t)b * HW + qpix) * kC + 4 * h;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                store4(dst + 32 * dt + 8 * u, make_float4(o[dt][4 * u] * inv, o[dt][4 * u + 1] * inv,
-                                                          o[dt][4 * u + 2] * inv, o[dt][4 * u + 3] * inv));
-    } else {
-        const size_t row = pidx(p, b, wi, ks, tq);
-        float4* dst = reinterpret_cast<float4*>(part.o + lane_tile_base(p, b, wi, ks, qblk, wid)) + lane;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                dst[(dt * 4 + u) * 64] = make_float4(o[dt][4 * u], o[dt][4 * u + 1], o[dt][4 * u + 2], o[dt][4 * u + 3]);
-        if (h == 0) {
-            part.m[row] = m_run * kLn2;  // the combine kernel takes natural-log maxima
-            part.l[row] = l_run;
-        }
-    }
+    store_o_tiles(p, o, m_run, l_run, p.ksplit != 1, out, part, b, wi, ks, qblk, wid, tq, qpix, HW, lane, h);
 }
 
 // ============================================================================================
@@ -1136,20 +1090,7 @@ win_attn_bf16_v3_kernel(Params p, const __bf16* __restrict__ q, const __bf16* __
                 if (wtile + 1 < ntiles) gather(wtile + 1);
             }
         }
-        float bmax = max3_raw(sacc[0][0], sacc[1][0], sacc[0][1]);
-        bmax = max3_raw(bmax, sacc[1][1], sacc[0][2]);
-#pragma unroll
-        for (int r = 2; r < 15; ++r) bmax = max3_raw(bmax, sacc[1][r], sacc[0][r + 1]);
-        bmax = fmaxf(bmax, sacc[1][15]);
-        const float bm2 = halves_max(bmax) * cl2;
-        if (__any(bm2 > m_run + kThr)) {
-            const float m_new = fmaxf(m_run, bm2);
-            const float corr = fast_exp2(m_run - m_new);
-            l_run *= corr;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[dt] *= corr;
-            m_run = m_new;
-        }
+        rescale_if_grown(halves_max(tile_max32(sacc[0], sacc[1])) * cl2, m_run, l_run, o);
         // scalar fma per score: the packed v_pk_fma / v_pk_add form measured 1.5 us slower at B = 16
         // (same box, profiles/r4/g22: 53.9 / 54.3 vs 52.2 / 52.9 us)
         float bsum = 0.f;
@@ -1172,6 +1113,8 @@ win_attn_bf16_v3_kernel(Params p, const __bf16* __restrict__ q, const __bf16* __
     }
     if (grp == 0) lds_barrier();
 
+    // (its own copy of store_o_tiles' normalised branch: through the helper this kernel allocates 238
+    // instead of 242 VGPRs and schedules differently; profiles/winattn_plan/resource_usage.txt)
     // O^T[d = 32 dt + 8u + 4h + j][q = c] in o[dt][4u + j]
     const float inv = 1.0f / l_run;
     __bf16* dst = out + ((size_t)b * HW + qpix) * kC + 4 * h;
@@ -1331,20 +1274,7 @@ win_attn_x3_kernel(Params p, const float* __restrict__ q, const __bf16* __restri
                 s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sMaskAb[buf][row][h], qmask, s[sub], 0, 0, 0);
         }
         // ---- online softmax (fp32, log2 domain), deferred rescale
-        float bmax = max3_raw(s[0][0], s[1][0], s[0][1]);
-        bmax = max3_raw(bmax, s[1][1], s[0][2]);
-#pragma unroll
-        for (int r = 2; r < 15; ++r) bmax = max3_raw(bmax, s[1][r], s[0][r + 1]);
-        bmax = fmaxf(bmax, s[1][15]);
-        const float bm2 = halves_max(bmax) * cl2;
-        if (__any(bm2 > m_run + kThr)) {
-            const float m_new = fmaxf(m_run, bm2);
-            const float corr = fast_exp2(m_run - m_new);
-            l_run *= corr;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[dt] *= corr;
-            m_run = m_new;
-        }
+        rescale_if_grown(halves_max(tile_max32(s[0], s[1])) * cl2, m_run, l_run, o);
         float bsum = 0.f;
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub)
@@ -1393,29 +1323,7 @@ win_attn_x3_kernel(Params p, const float* __restrict__ q, const __bf16* __restri
         if ((k0 - kbeg) / kBK < 8) WA_STAMP(4 + (k0 - kbeg) / kBK, WA_CLOCK());
     }
 
-    // O^T[d = 32 dt + 8u + 4h + j][q = c] in o[dt][4u + j]
-    if (p.ksplit == 1) {
-        const float inv = 1.0f / l_run;
-        float* dst = out + ((size_t)b * HW + qpix) * kC + 4 * h;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                store4(dst + 32 * dt + 8 * u, make_float4(o[dt][4 * u] * inv, o[dt][4 * u + 1] * inv,
-                                                          o[dt][4 * u + 2] * inv, o[dt][4 * u + 3] * inv));
-    } else {
-        const size_t row = pidx(p, b, wi, ks, tq);
-        float4* dst = reinterpret_cast<float4*>(part.o + lane_tile_base(p, b, wi, ks, qblk, wid)) + lane;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                dst[(dt * 4 + u) * 64] = make_float4(o[dt][4 * u], o[dt][4 * u + 1], o[dt][4 * u + 2], o[dt][4 * u + 3]);
-        if (h == 0) {
-            part.m[row] = m_run * kLn2;  // natural-log maxima for the combine
-            part.l[row] = l_run;
-        }
-    }
+    store_o_tiles(p, o, m_run, l_run, p.ksplit != 1, out, part, b, wi, ks, qblk, wid, tq, qpix, HW, lane, h);
     WA_STAMP(12, WA_CLOCK());
     WA_STAMP(13, wall_clock64());
 }
@@ -1644,15 +1552,7 @@ win_attn_x3_v2_kernel(Params p, const float* __restrict__ q, const __bf16* __res
 #pragma unroll
         for (int r = 3; r < 15; r += 2) bmax = max3_raw(bmax, sacc[r], sacc[r + 1]);
         bmax = fmaxf(bmax, sacc[15]);
-        const float bm2 = halves_max(bmax) * cl2;
-        if (__any(bm2 > m_run + kThr)) {
-            const float m_new = fmaxf(m_run, bm2);
-            const float corr = fast_exp2(m_run - m_new);
-            l_run *= corr;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[dt] *= corr;
-            m_run = m_new;
-        }
+        rescale_if_grown(halves_max(bmax) * cl2, m_run, l_run, o);
         float bsum = 0.f;
 #pragma unroll
         for (int ksx = 0; ksx < 2; ++ksx) {
@@ -1708,7 +1608,9 @@ win_attn_x3_v2_kernel(Params p, const float* __restrict__ q, const __bf16* __res
                 o[D + j][4 * u + 2] = o[D + j][4 * u + 2] * f0 + x.z * f1;
                 o[D + j][4 * u + 3] = o[D + j][4 * u + 3] * f0 + x.w * f1;
             }
-        // O^T[d = 32 dt + 8u + 4h + j][q = c] in o[dt][4u + j]
+        // this group's two d tiles (its own copy of store_o_tiles: through the helper the kernel keeps
+        // its registers but schedules this combine differently, 5 instructions more;
+        // profiles/winattn_plan/resource_usage.txt)
         if (p.ksplit == 1) {
             const float inv = 1.0f / l_run;
             float* dst = out + ((size_t)b * HW + win_pixel(p, wi, tq)) * kC + 4 * h;
@@ -1725,7 +1627,7 @@ win_attn_x3_v2_kernel(Params p, const float* __restrict__ q, const __bf16* __res
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
-                    dst[((D + j) * 4 + u) * 64] =
+                    dst[slot_float4(D + j, u, 0)] =
                         make_float4(o[D + j][4 * u], o[D + j][4 * u + 1], o[D + j][4 * u + 2], o[D + j][4 * u + 3]);
             if (G == 0 && h == 0) {
                 const size_t row = pidx(p, b, wi, ks, tq);
@@ -1764,119 +1666,217 @@ __global__ void __launch_bounds__(256) split_kv_kernel(const float4* __restrict_
 }  // namespace tsplat
 
 using namespace tsplat;
+using namespace tsplat::winattn;
 
-// keys are split so a launch fills the 256 CUs: >= 512 workgroups for the 16x16 kernel (two per
-// CU), >= 256 for the 32x32 kernel (one per CU, software-pipelined)
+// ============================================================================================
+// Host side: every entry point validates its pointers, builds one Plan and launches what it says.
+// ============================================================================================
+
+// Tuning knobs (benchmarking only), read once per call -- tests change them between calls -- and
+// only here. (Round 4: the opt-in variants measured slower than the defaults -- the 16-query-wave
+// x16 kernel, the key-pair kernel, the split-free quad kernel and the round-1 bf16 kernel -- were
+// removed; DESIGN.md §3 keeps their measurements.)
+struct Knobs {
+    const char* winattn;  // TSPLAT_WINATTN: "16" forces the 16x16x4 kernel (fp32 family)
+    int ksplit;           // TSPLAT_WINATTN_KSPLIT: forces the key split (fp32 and x3 families)
+    const char* bf16;     // TSPLAT_WINATTN_BF16: "v2" / "v3" selects the bf16 kernel
+    const char* x3;       // TSPLAT_WINATTN_X3: "v1" selects the round-5 4-wave bf16x3 kernel
+    const char* x3_prio;  // TSPLAT_WINATTN_X3_PRIO: "0" = no static priority (A/B knob)
+    const char* x3_xcd;   // TSPLAT_WINATTN_X3_XCD: "split" = key-split-major XCD order (A/B knob)
+};
+static Knobs read_knobs() {
+    const char* ks = getenv("TSPLAT_WINATTN_KSPLIT");
+    return {getenv("TSPLAT_WINATTN"),      ks ? atoi(ks) : 0,           getenv("TSPLAT_WINATTN_BF16"),
+            getenv("TSPLAT_WINATTN_X3"), getenv("TSPLAT_WINATTN_X3_PRIO"), getenv("TSPLAT_WINATTN_X3_XCD")};
+}
+static bool is(const char* knob, const char* val) { return knob && !strcmp(knob, val); }
+
+// keys are split so a launch fills the 256 CUs: `target` workgroups or the most the tiles allow
 static int choose_ksplit(int base_wgs, int key_tiles, int target) {
     int ks = 1;
     while (base_wgs * ks < target && ks * 2 <= key_tiles && key_tiles % (ks * 2) == 0 && ks < 8) ks *= 2;
     return ks;
 }
 
-// Tuning knobs (benchmarking only): TSPLAT_WINATTN=16 forces the 16x16x4 kernel;
-// TSPLAT_WINATTN_KSPLIT forces the key split. (Round 4: the opt-in variants measured slower than the
-// defaults -- the 16-query-wave x16 kernel, the key-pair kernel, the split-free quad kernel and the
-// round-1 bf16 kernel -- were removed; DESIGN.md §3 keeps their measurements.)
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-static bool env_is(const char* name, const char* val) {
-    const char* e = getenv(name);
-    return e && !strcmp(e, val);
+enum class Family { fp32, bf16, x3 };
+enum class Main { f32_16, f32_32, bf16_v2, bf16_v3, x3_v1, x3_v2 };
+enum class Combine { none, rows, lane_tiles };  // win_attn_combine_kernel / win_attn_combine_x32_kernel
+
+struct Shape {
+    int batch, height, width, channels, key_views, splits, with_shift, key_batch_shift;
+};
+
+struct Plan {
+    Params p;
+    Main main;
+    bool prio, wxcd;  // win_attn_x3_v2_kernel's PRIO / WXCD
+    Combine combine;
+    dim3 grid, block, combine_grid;
+    size_t workspace_bytes;
+    Partials part;  // of the caller's workspace: bind_workspace
+};
+
+// The launch decision, a pure function of its arguments. TSPLAT_EINVAL: no kernel serves the shape.
+static int make_plan(Family family, const Shape& s, const Knobs& knobs, Plan& pl) {
+    if (s.channels != kC || s.batch <= 0 || s.key_views <= 0 || s.splits <= 0) return TSPLAT_EINVAL;
+    if (s.height % s.splits || s.width % s.splits) return TSPLAT_EINVAL;
+    if (s.key_batch_shift < 0 || s.key_batch_shift >= s.batch) return TSPLAT_EINVAL;
+    const int wh = s.height / s.splits, ww = s.width / s.splits, L = wh * ww, windows = s.splits * s.splits;
+    if (s.with_shift && (wh / 2 == 0 || ww / 2 == 0)) return TSPLAT_EINVAL;
+    // queries per workgroup: 128 (the 32x32 MFMA kernels) where the window allows, else the fp32
+    // family's 16x16x4 kernel of 64
+    const int qb = family == Family::fp32 && (is(knobs.winattn, "16") || L % kBQ3) ? kBQ : kBQ3;
+    if (L % qb || (L * s.key_views) % kBK) return TSPLAT_EINVAL;
+    const int key_tiles = L * s.key_views / kBK, base = (L / qb) * windows * s.batch;
+
+    // v3 (8 staggered waves, 256 queries per workgroup, no key split) where the launch gives
+    // >= 1 workgroup per CU without splitting keys
+    const bool v3 = family == Family::bf16 && L % kBQ8 == 0 &&
+                    (is(knobs.bf16, "v3") || (!knobs.bf16 && (L / kBQ8) * windows * s.batch >= 256));
+    int ks;
+    if (family == Family::bf16)
+        // the bf16 family wants two workgroups per CU and has no forced split: TSPLAT_WINATTN_KSPLIT
+        // is not read for it
+        ks = choose_ksplit(base, key_tiles, 512);
+    else if (knobs.ksplit > 0 && key_tiles % knobs.ksplit == 0)
+        ks = knobs.ksplit;
+    else
+        // 128-query kernels: one workgroup per CU is enough (measured: b = 2 at 256 workgroups beats
+        // 512, and the key-pair kernel); the 16x16x4 kernel wants two per CU
+        ks = choose_ksplit(base, key_tiles, qb == kBQ3 ? 256 : 512);
+    // The workspace is sized before v3 drops the split: the two sizes differ only where
+    // TSPLAT_WINATTN_BF16=v3 forces v3 onto a launch v2 would split (then the workspace goes unused).
+    Window sized;
+    fill_window(sized, s.height, s.width, s.splits, s.key_views, s.with_shift, ks);
+    pl.workspace_bytes = partials_bytes(sized, s.batch);
+    if (v3) ks = 1;
+
+    fill_window(pl.p, s.height, s.width, s.splits, s.key_views, s.with_shift, ks);
+    pl.p.kv_shift = s.key_batch_shift;
+    pl.p.nbatch = s.batch;
+    pl.p.scale = 1.0f / sqrtf((float)kC);
+
+    pl.prio = pl.wxcd = true;
+    if (family == Family::fp32) {
+        pl.main = qb == kBQ3 ? Main::f32_32 : Main::f32_16;
+    } else if (family == Family::bf16) {
+        pl.main = v3 ? Main::bf16_v3 : Main::bf16_v2;
+    } else {
+        // the 8-wave two-group form (default) or the round-5 4-wave form; same grid, partials and
+        // output either way. The PRIO knob is looked at before the XCD knob.
+        pl.main = is(knobs.x3, "v1") ? Main::x3_v1 : Main::x3_v2;
+        pl.prio = !is(knobs.x3_prio, "0");
+        // window-major XCD order (profiles/r6/traffic_win_attn_x3_xcd.txt: fetch 17.4 vs 30.0 MB)
+        pl.wxcd = !(pl.prio && is(knobs.x3_xcd, "split"));
+    }
+    pl.combine = ks == 1 ? Combine::none : qb == kBQ3 ? Combine::lane_tiles : Combine::rows;
+    pl.block = dim3(pl.main == Main::bf16_v3 || pl.main == Main::x3_v2 ? kThreads8 : kThreads);
+    pl.grid = v3 ? dim3(L / kBQ8, windows, s.batch) : dim3(L / qb, windows, s.batch * ks);
+    pl.combine_grid = pl.combine == Combine::lane_tiles ? dim3(L / kBQ3 * 16, windows, s.batch)
+                                                        : dim3(L / (kThreads / 32), windows, s.batch);
+    pl.part = Partials{nullptr, nullptr, nullptr};
+    return TSPLAT_OK;
 }
 
-// query-block size of the kernel used for window size L (128: 32x32x2 kernel, 64: 16x16x4)
-static int query_block(int L) {
-    if (env_is("TSPLAT_WINATTN", "16")) return tsplat::winattn::kBQ;
-    return L % tsplat::winattn::kBQ3 == 0 ? tsplat::winattn::kBQ3 : tsplat::winattn::kBQ;
+// split launches write their partials into the caller's workspace (plan.workspace_bytes of it)
+static int bind_workspace(Plan& pl, void* workspace) {
+    if (pl.p.ksplit == 1) return TSPLAT_OK;
+    if (!workspace) return TSPLAT_EINVAL;
+    pl.part = carve_partials(pl.p, pl.p.nbatch, workspace);
+    return TSPLAT_OK;
 }
-// 128-query kernel: one workgroup per CU is enough (measured: b = 2 at 256 workgroups beats 512,
-// and the key-pair kernel); the 16x16x4 kernel wants two per CU
-static int pick_ksplit(int base, int key_tiles, int qb) {
-    const int forced = env_int("TSPLAT_WINATTN_KSPLIT", 0);
-    if (forced > 0 && key_tiles % forced == 0) return forced;
-    return choose_ksplit(base, key_tiles, qb == tsplat::winattn::kBQ3 ? 256 : 512);
+
+// Key split of the exact-fp32 128-query kernel for a consumer of its partials (0: another kernel
+// serves the shape). It is 0 whenever TSPLAT_WINATTN is set at all, not only when it is "16":
+// any value of that knob turns the partials path (and the merge projection's fused combine) off.
+static int fp32_partials_split(const Plan& pl, const Knobs& knobs) {
+    return knobs.winattn || pl.main != Main::f32_32 ? 0 : pl.p.ksplit;
+}
+
+// ev: the main kernel's own dispatch timestamps when timed (prof.h), null for a plain launch
+static void launch_f32(const Plan& pl, const float* q, const float* k, const float* v, float* out,
+                       const prof::ExtEvents* ev, hipStream_t stream) {
+    if (pl.main == Main::f32_16)
+        hipLaunchKernelGGL(win_attn_f32_kernel, pl.grid, pl.block, 0, stream, pl.p, q, k, v, out, pl.part);
+    else if (ev)
+        hipExtLaunchKernelGGL(win_attn_f32x32_kernel, pl.grid, pl.block, 0, stream, ev->start, ev->stop, 0, pl.p, q, k,
+                              v, out, pl.part);
+    else
+        hipLaunchKernelGGL(win_attn_f32x32_kernel, pl.grid, pl.block, 0, stream, pl.p, q, k, v, out, pl.part);
+}
+
+static void launch_bf16(const Plan& pl, const __bf16* q, const __bf16* k, const __bf16* v, __bf16* out,
+                        const prof::ExtEvents& ev, hipStream_t stream) {
+    if (pl.main == Main::bf16_v3)
+        hipExtLaunchKernelGGL(win_attn_bf16_v3_kernel, pl.grid, pl.block, 0, stream, ev.start, ev.stop, 0, pl.p, q, k,
+                              v, out);
+    else
+        hipExtLaunchKernelGGL(win_attn_bf16_v2_kernel, pl.grid, pl.block, 0, stream, ev.start, ev.stop, 0, pl.p, q, k,
+                              v, out, pl.part);
+}
+
+// kv = tsplat_split_kv_bf16x3(k, v): [kh | kl | vh | vl], nkv bf16 each
+static void launch_x3(const Plan& pl, const float* q, const __bf16* kv, size_t nkv, float* out,
+                      const prof::ExtEvents& ev, hipStream_t stream) {
+    auto go = [&](auto kernel) {
+        hipExtLaunchKernelGGL(kernel, pl.grid, pl.block, 0, stream, ev.start, ev.stop, 0, pl.p, q, kv, kv + nkv,
+                              kv + 2 * nkv, kv + 3 * nkv, out, pl.part);
+    };
+    if (pl.main == Main::x3_v1)
+        go(win_attn_x3_kernel);
+    else if (!pl.prio)
+        go(win_attn_x3_v2_kernel<false, true>);
+    else if (!pl.wxcd)
+        go(win_attn_x3_v2_kernel<true, false>);
+    else
+        go(win_attn_x3_v2_kernel<true, true>);
+}
+
+template <typename OutT>
+static void launch_combine(const Plan& pl, OutT* out, hipStream_t stream) {
+    if (pl.combine == Combine::lane_tiles)
+        hipLaunchKernelGGL(win_attn_combine_x32_kernel<OutT>, pl.combine_grid, dim3(kThreads), 0, stream, pl.p,
+                           pl.part, out);
+    else if constexpr (sizeof(OutT) == sizeof(float))  // the 64-query kernel is fp32 only
+        if (pl.combine == Combine::rows)
+            hipLaunchKernelGGL(win_attn_combine_kernel<float>, pl.combine_grid, dim3(kThreads), 0, stream, pl.p,
+                               pl.part, out);
 }
 
 extern "C" size_t tsplat_win_attn_workspace_bytes(int32_t batch, int32_t height, int32_t width,
                                                   int32_t key_views, int32_t splits) {
-    using namespace tsplat::winattn;
-    if (batch <= 0 || key_views <= 0 || splits <= 0 || height % splits || width % splits) return 0;
-    const int L = (height / splits) * (width / splits);
-    if (L % kBQ || (L * key_views) % kBK) return 0;
-    const int base = (L / query_block(L)) * splits * splits * batch;
-    const int ks = pick_ksplit(base, L * key_views / kBK, query_block(L));
-    if (ks == 1) return 0;
-    return (size_t)batch * splits * splits * ks * L * (kC + 2) * sizeof(float);
+    Plan pl;
+    if (make_plan(Family::fp32, {batch, height, width, kC, key_views, splits, 0, 0}, read_knobs(), pl)) return 0;
+    return pl.workspace_bytes;
 }
 
 extern "C" int tsplat_win_attn_fwd(const float* q, const float* k, const float* v, float* out,
                                    void* workspace, int32_t batch, int32_t height, int32_t width,
                                    int32_t channels, int32_t key_views, int32_t splits,
                                    int32_t with_shift, void* stream_) {
-    using namespace tsplat::winattn;
     if (!q || !k || !v || !out) return TSPLAT_EINVAL;
-    if (channels != kC || batch <= 0 || key_views <= 0 || splits <= 0) return TSPLAT_EINVAL;
-    if (height % splits || width % splits) return TSPLAT_EINVAL;
-    Params p;
-    p.H = height;
-    p.W = width;
-    p.splits = splits;
-    p.m = key_views;
-    p.L = (height / splits) * (width / splits);
-    p.shift_h = with_shift ? (height / splits) / 2 : 0;
-    p.shift_w = with_shift ? (width / splits) / 2 : 0;
-    p.shift = with_shift ? 1 : 0;
-    p.wh = height / splits;
-    p.ww = width / splits;
-    p.ww_log2 = (p.ww & (p.ww - 1)) == 0 ? __builtin_ctz(p.ww) : -1;
-    p.kv_shift = 0;
-    p.nbatch = batch;
-    if (with_shift && (p.shift_h == 0 || p.shift_w == 0)) return TSPLAT_EINVAL;
-    if (p.L % kBQ || (p.L * p.m) % kBK) return TSPLAT_EINVAL;
-    p.scale = 1.0f / sqrtf((float)kC);
+    Plan pl;
+    if (make_plan(Family::fp32, {batch, height, width, channels, key_views, splits, with_shift, 0}, read_knobs(), pl) ||
+        bind_workspace(pl, workspace))
+        return TSPLAT_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
-    const int qb = query_block(p.L);
-    const int base = (p.L / qb) * splits * splits * batch;
-    p.ksplit = pick_ksplit(base, p.L * p.m / kBK, qb);
-    p.keys_per_split = p.L * p.m / p.ksplit;
-    Partials part{nullptr, nullptr, nullptr};
-    if (p.ksplit > 1) {
-        if (!workspace) return TSPLAT_EINVAL;
-        const size_t n = (size_t)batch * splits * splits * p.ksplit * p.L;
-        part.o = (float*)workspace;
-        part.m = part.o + n * kC;
-        part.l = part.m + n;
-    }
-    const dim3 grid(p.L / qb, splits * splits, batch * p.ksplit);
     TSPLAT_PROF_BEGIN(prof::kWinAttn, stream);
-    if (qb == kBQ3)
-        hipLaunchKernelGGL(win_attn_f32x32_kernel, grid, dim3(kThreads), 0, stream, p, q, k, v, out, part);
-    else
-        hipLaunchKernelGGL(win_attn_f32_kernel, grid, dim3(kThreads), 0, stream, p, q, k, v, out, part);
-    if (p.ksplit > 1 && qb == kBQ3)
-        hipLaunchKernelGGL(win_attn_combine_x32_kernel<float>, dim3(p.L / kBQ3 * 16, splits * splits, batch),
-                           dim3(kThreads), 0, stream, p, part, out);
-    else if (p.ksplit > 1)
-        hipLaunchKernelGGL(win_attn_combine_kernel<float>, dim3(p.L / (kThreads / 32), splits * splits, batch),
-                           dim3(kThreads), 0, stream, p, part, out);
+    launch_f32(pl, q, k, v, out, nullptr, stream);
+    launch_combine(pl, out, stream);
     TSPLAT_PROF_END(prof::kWinAttn, stream);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
 }
 
-// Key split the exact-fp32 128-query kernel uses for this launch shape (the same decision as
+// Key split the exact-fp32 128-query kernel uses for this launch shape (the same plan as
 // tsplat_win_attn_fwd): > 1 means the call runs main + combine and tsplat_win_attn_partials_fwd
 // may be used instead; 1 = no split; 0 = another kernel serves this shape.
 extern "C" int32_t tsplat_win_attn_split(int32_t batch, int32_t height, int32_t width, int32_t key_views,
                                          int32_t splits) {
-    using namespace tsplat::winattn;
-    if (batch <= 0 || key_views <= 0 || splits <= 0 || height % splits || width % splits) return 0;
-    const int L = (height / splits) * (width / splits);
-    if (L % kBQ3 || (L * key_views) % kBK || getenv("TSPLAT_WINATTN")) return 0;
-    const int base = (L / kBQ3) * splits * splits * batch;
-    return pick_ksplit(base, L * key_views / kBK, kBQ3);
+    const Knobs knobs = read_knobs();
+    Plan pl;
+    if (make_plan(Family::fp32, {batch, height, width, kC, key_views, splits, 0, 0}, knobs, pl)) return 0;
+    return fp32_partials_split(pl, knobs);
 }
 
 // The main kernel only: the split-key partials (O unnormalised, m in natural log, l) stay in
@@ -1886,38 +1886,15 @@ extern "C" int tsplat_win_attn_partials_fwd(const float* q, const float* k, cons
                                             int32_t batch, int32_t height, int32_t width, int32_t channels,
                                             int32_t key_views, int32_t splits, int32_t with_shift,
                                             int32_t key_batch_shift, void* stream_) {
-    using namespace tsplat::winattn;
-    if (!q || !k || !v || !workspace || channels != kC) return TSPLAT_EINVAL;
-    if (key_batch_shift < 0 || key_batch_shift >= batch) return TSPLAT_EINVAL;
-    const int ks = tsplat_win_attn_split(batch, height, width, key_views, splits);
-    if (ks <= 1) return TSPLAT_EINVAL;
-    Params p;
-    p.H = height;
-    p.W = width;
-    p.splits = splits;
-    p.m = key_views;
-    p.L = (height / splits) * (width / splits);
-    p.shift_h = with_shift ? (height / splits) / 2 : 0;
-    p.shift_w = with_shift ? (width / splits) / 2 : 0;
-    p.shift = with_shift ? 1 : 0;
-    p.wh = height / splits;
-    p.ww = width / splits;
-    p.ww_log2 = (p.ww & (p.ww - 1)) == 0 ? __builtin_ctz(p.ww) : -1;
-    p.kv_shift = 0;
-    p.nbatch = batch;
-    if (with_shift && (p.shift_h == 0 || p.shift_w == 0)) return TSPLAT_EINVAL;
-    p.scale = 1.0f / sqrtf((float)kC);
-    p.ksplit = ks;
-    p.keys_per_split = p.L * p.m / p.ksplit;
-    p.kv_shift = key_batch_shift;
-    const size_t n = (size_t)batch * splits * splits * p.ksplit * p.L;
-    Partials part{(float*)workspace, nullptr, nullptr};
-    part.m = part.o + n * kC;
-    part.l = part.m + n;
-    hipStream_t stream = (hipStream_t)stream_;
+    if (!q || !k || !v || !workspace) return TSPLAT_EINVAL;
+    const Knobs knobs = read_knobs();
+    Plan pl;
+    if (make_plan(Family::fp32, {batch, height, width, channels, key_views, splits, with_shift, key_batch_shift},
+                  knobs, pl) ||
+        fp32_partials_split(pl, knobs) <= 1 || bind_workspace(pl, workspace))
+        return TSPLAT_EINVAL;
     const prof::ExtEvents ev = prof::ext_events(prof::kWinAttn);  // kernel timestamps when timed
-    hipExtLaunchKernelGGL(win_attn_f32x32_kernel, dim3(p.L / kBQ3, splits * splits, batch * p.ksplit),
-                              dim3(kThreads), 0, stream, ev.start, ev.stop, 0, p, q, k, v, (float*)nullptr, part);
+    launch_f32(pl, q, k, v, (float*)nullptr, &ev, (hipStream_t)stream_);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
 }
@@ -1932,27 +1909,9 @@ extern "C" int tsplat_win_attn_stamps(void* buf) {
 
 extern "C" size_t tsplat_win_attn_bf16_workspace_bytes(int32_t batch, int32_t height, int32_t width,
                                                        int32_t key_views, int32_t splits) {
-    using namespace tsplat::winattn;
-    if (batch <= 0 || key_views <= 0 || splits <= 0 || height % splits || width % splits) return 0;
-    const int L = (height / splits) * (width / splits);
-    if (L % kBQ3 || (L * key_views) % kBK) return 0;
-    const int base = (L / kBQ3) * splits * splits * batch;
-    const int ks = choose_ksplit(base, L * key_views / kBK, 512);
-    if (ks == 1) return 0;
-    return (size_t)batch * splits * splits * ks * L * (kC + 2) * sizeof(float);
-}
-
-extern "C" int tsplat_win_attn_bf16_shift_fwd(const void* q, const void* k, const void* v, void* out,
-                                              void* workspace, int32_t batch, int32_t height, int32_t width,
-                                              int32_t channels, int32_t key_views, int32_t splits,
-                                              int32_t with_shift, int32_t key_batch_shift, void* stream_);
-
-extern "C" int tsplat_win_attn_bf16_fwd(const void* q, const void* k, const void* v, void* out,
-                                        void* workspace, int32_t batch, int32_t height, int32_t width,
-                                        int32_t channels, int32_t key_views, int32_t splits,
-                                        int32_t with_shift, void* stream_) {
-    return tsplat_win_attn_bf16_shift_fwd(q, k, v, out, workspace, batch, height, width, channels, key_views, splits,
-                                          with_shift, 0, stream_);
+    Plan pl;
+    if (make_plan(Family::bf16, {batch, height, width, kC, key_views, splits, 0, 0}, read_knobs(), pl)) return 0;
+    return pl.workspace_bytes;
 }
 
 // tsplat_win_attn_bf16_fwd where query batch b attends to the keys / values of batch
@@ -1961,59 +1920,27 @@ extern "C" int tsplat_win_attn_bf16_shift_fwd(const void* q, const void* k, cons
                                               void* workspace, int32_t batch, int32_t height, int32_t width,
                                               int32_t channels, int32_t key_views, int32_t splits,
                                               int32_t with_shift, int32_t key_batch_shift, void* stream_) {
-    using namespace tsplat::winattn;
     if (!q || !k || !v || !out) return TSPLAT_EINVAL;
-    if (key_batch_shift < 0 || key_batch_shift >= batch) return TSPLAT_EINVAL;
-    if (channels != kC || batch <= 0 || key_views <= 0 || splits <= 0) return TSPLAT_EINVAL;
-    if (height % splits || width % splits) return TSPLAT_EINVAL;
-    Params p;
-    p.H = height;
-    p.W = width;
-    p.splits = splits;
-    p.m = key_views;
-    p.L = (height / splits) * (width / splits);
-    p.shift_h = with_shift ? (height / splits) / 2 : 0;
-    p.shift_w = with_shift ? (width / splits) / 2 : 0;
-    p.shift = with_shift ? 1 : 0;
-    p.wh = height / splits;
-    p.ww = width / splits;
-    p.ww_log2 = (p.ww & (p.ww - 1)) == 0 ? __builtin_ctz(p.ww) : -1;
-    p.kv_shift = key_batch_shift;
-    p.nbatch = batch;
-    if (with_shift && (p.shift_h == 0 || p.shift_w == 0)) return TSPLAT_EINVAL;
-    if (p.L % kBQ3 || (p.L * p.m) % kBK) return TSPLAT_EINVAL;
-    p.scale = 1.0f / sqrtf((float)kC);
-    // v3 (8 staggered waves, 256 queries per workgroup, no key split) where the launch gives
-    // >= 1 workgroup per CU without splitting keys; TSPLAT_WINATTN_BF16=v2 / v3 selects
-    const bool v3 = p.L % kBQ8 == 0 &&
-                    (env_is("TSPLAT_WINATTN_BF16", "v3") ||
-                     (!getenv("TSPLAT_WINATTN_BF16") && (p.L / kBQ8) * splits * splits * batch >= 256));
-    const int base = (p.L / kBQ3) * splits * splits * batch;
-    p.ksplit = v3 ? 1 : choose_ksplit(base, p.L * p.m / kBK, 512);
-    p.keys_per_split = p.L * p.m / p.ksplit;
-    Partials part{nullptr, nullptr, nullptr};
-    if (p.ksplit > 1) {
-        if (!workspace) return TSPLAT_EINVAL;
-        const size_t n = (size_t)batch * splits * splits * p.ksplit * p.L;
-        part.o = (float*)workspace;
-        part.m = part.o + n * kC;
-        part.l = part.m + n;
-    }
+    Plan pl;
+    if (make_plan(Family::bf16, {batch, height, width, channels, key_views, splits, with_shift, key_batch_shift},
+                  read_knobs(), pl) ||
+        bind_workspace(pl, workspace))
+        return TSPLAT_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     // the main kernel's own dispatch timestamps when timed (the split path's combine is not in it)
     const prof::ExtEvents ev = prof::ext_events(prof::kWinAttn);
-    const __bf16 *qh = (const __bf16*)q, *kh = (const __bf16*)k, *vh = (const __bf16*)v;
-    if (v3)
-        hipExtLaunchKernelGGL(win_attn_bf16_v3_kernel, dim3(p.L / kBQ8, splits * splits, batch), dim3(kThreads8), 0,
-                              stream, ev.start, ev.stop, 0, p, qh, kh, vh, (__bf16*)out);
-    else
-        hipExtLaunchKernelGGL(win_attn_bf16_v2_kernel, dim3(p.L / kBQ3, splits * splits, batch * p.ksplit),
-                              dim3(kThreads), 0, stream, ev.start, ev.stop, 0, p, qh, kh, vh, (__bf16*)out, part);
-    if (p.ksplit > 1)
-        hipLaunchKernelGGL(win_attn_combine_x32_kernel<__bf16>, dim3(p.L / kBQ3 * 16, splits * splits, batch),
-                           dim3(kThreads), 0, stream, p, part, (__bf16*)out);
+    launch_bf16(pl, (const __bf16*)q, (const __bf16*)k, (const __bf16*)v, (__bf16*)out, ev, stream);
+    launch_combine(pl, (__bf16*)out, stream);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
+}
+
+extern "C" int tsplat_win_attn_bf16_fwd(const void* q, const void* k, const void* v, void* out,
+                                        void* workspace, int32_t batch, int32_t height, int32_t width,
+                                        int32_t channels, int32_t key_views, int32_t splits,
+                                        int32_t with_shift, void* stream_) {
+    return tsplat_win_attn_bf16_shift_fwd(q, k, v, out, workspace, batch, height, width, channels, key_views, splits,
+                                          with_shift, 0, stream_);
 }
 
 // bf16x3 key / value split for tsplat_win_attn_x3_*: out = [kh | kl | vh | vl], each n bf16
@@ -2027,56 +1954,6 @@ extern "C" int tsplat_split_kv_bf16x3(const float* k, const float* v, void* out,
     return TSPLAT_OK;
 }
 
-static int x3_params(tsplat::winattn::Params& p, int32_t batch, int32_t height, int32_t width, int32_t channels,
-                     int32_t key_views, int32_t splits, int32_t with_shift, int32_t key_batch_shift) {
-    using namespace tsplat::winattn;
-    if (channels != kC || batch <= 0 || key_views <= 0 || splits <= 0 || height % splits || width % splits)
-        return TSPLAT_EINVAL;
-    if (key_batch_shift < 0 || key_batch_shift >= batch) return TSPLAT_EINVAL;
-    p.H = height;
-    p.W = width;
-    p.splits = splits;
-    p.m = key_views;
-    p.L = (height / splits) * (width / splits);
-    p.shift_h = with_shift ? (height / splits) / 2 : 0;
-    p.shift_w = with_shift ? (width / splits) / 2 : 0;
-    p.shift = with_shift ? 1 : 0;
-    p.wh = height / splits;
-    p.ww = width / splits;
-    p.ww_log2 = (p.ww & (p.ww - 1)) == 0 ? __builtin_ctz(p.ww) : -1;
-    p.kv_shift = key_batch_shift;
-    p.nbatch = batch;
-    if (with_shift && (p.shift_h == 0 || p.shift_w == 0)) return TSPLAT_EINVAL;
-    if (p.L % kBQ3 || (p.L * p.m) % kBK) return TSPLAT_EINVAL;
-    p.scale = 1.0f / sqrtf((float)kC);
-    // the exact kernel's key split (so the workspace / partials layout is the same)
-    const int base = (p.L / kBQ3) * splits * splits * batch;
-    p.ksplit = pick_ksplit(base, p.L * p.m / kBK, kBQ3);
-    p.keys_per_split = p.L * p.m / p.ksplit;
-    return TSPLAT_OK;
-}
-
-// the bf16x3 main kernel: the 8-wave two-group form (default) or the round-5 4-wave form
-// (TSPLAT_WINATTN_X3=v1, the A/B knob); same grid, partials and output either way
-static void launch_x3(const tsplat::winattn::Params& p, int splits, int batch, const float* q, const __bf16* kv,
-                      size_t nkv, float* out, tsplat::winattn::Partials part, const tsplat::prof::ExtEvents& ev,
-                      hipStream_t stream) {
-    using namespace tsplat::winattn;
-    const dim3 grid(p.L / kBQ3, splits * splits, batch * p.ksplit);
-    if (env_is("TSPLAT_WINATTN_X3", "v1"))
-        hipExtLaunchKernelGGL(win_attn_x3_kernel, grid, dim3(kThreads), 0, stream, ev.start, ev.stop, 0, p, q, kv,
-                              kv + nkv, kv + 2 * nkv, kv + 3 * nkv, out, part);
-    else if (env_is("TSPLAT_WINATTN_X3_PRIO", "0"))  // A/B knob: no static priority
-        hipExtLaunchKernelGGL((win_attn_x3_v2_kernel<false, true>), grid, dim3(kThreads8), 0, stream, ev.start,
-                              ev.stop, 0, p, q, kv, kv + nkv, kv + 2 * nkv, kv + 3 * nkv, out, part);
-    else if (env_is("TSPLAT_WINATTN_X3_XCD", "split"))  // A/B knob: key-split-major XCD order
-        hipExtLaunchKernelGGL((win_attn_x3_v2_kernel<true, false>), grid, dim3(kThreads8), 0, stream, ev.start,
-                              ev.stop, 0, p, q, kv, kv + nkv, kv + 2 * nkv, kv + 3 * nkv, out, part);
-    else  // window-major XCD order (profiles/r6/traffic_win_attn_x3_xcd.txt: fetch 17.4 vs 30.0 MB)
-        hipExtLaunchKernelGGL((win_attn_x3_v2_kernel<true, true>), grid, dim3(kThreads8), 0, stream, ev.start,
-                              ev.stop, 0, p, q, kv, kv + nkv, kv + 2 * nkv, kv + 3 * nkv, out, part);
-}
-
 // bf16x3 window attention, main kernel only (partials for the merge projection); kv_x3 =
 // tsplat_split_kv_bf16x3(k, v) ([kh | kl | vh | vl], k / v [batch, key_views, H*W, 128]). Same
 // shapes, key split and workspace as tsplat_win_attn_partials_fwd.
@@ -2084,21 +1961,15 @@ extern "C" int tsplat_win_attn_x3_partials_fwd(const float* q, const void* kv_x3
                                                int32_t height, int32_t width, int32_t channels, int32_t key_views,
                                                int32_t splits, int32_t with_shift, int32_t key_batch_shift,
                                                void* stream_) {
-    using namespace tsplat::winattn;
     if (!q || !kv_x3 || !workspace) return TSPLAT_EINVAL;
-    Params p;
-    if (x3_params(p, batch, height, width, channels, key_views, splits, with_shift, key_batch_shift) != TSPLAT_OK)
+    Plan pl;
+    if (make_plan(Family::x3, {batch, height, width, channels, key_views, splits, with_shift, key_batch_shift},
+                  read_knobs(), pl) ||
+        pl.p.ksplit <= 1 || bind_workspace(pl, workspace))
         return TSPLAT_EINVAL;
-    if (p.ksplit <= 1) return TSPLAT_EINVAL;
-    const size_t n = (size_t)batch * splits * splits * p.ksplit * p.L;
-    Partials part{(float*)workspace, nullptr, nullptr};
-    part.m = part.o + n * kC;
-    part.l = part.m + n;
     const size_t nkv = (size_t)batch * key_views * height * width * kC;
-    const __bf16* kv = (const __bf16*)kv_x3;
-    hipStream_t stream = (hipStream_t)stream_;
     const prof::ExtEvents ev = prof::ext_events(prof::kWinAttn);
-    launch_x3(p, splits, batch, q, kv, nkv, (float*)nullptr, part, ev, stream);
+    launch_x3(pl, q, (const __bf16*)kv_x3, nkv, (float*)nullptr, ev, (hipStream_t)stream_);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
 }
@@ -2108,27 +1979,16 @@ extern "C" int tsplat_win_attn_x3_partials_fwd(const float* q, const void* kv_x3
 extern "C" int tsplat_win_attn_x3_fwd(const float* q, const void* kv_x3, float* out, void* workspace, int32_t batch,
                                       int32_t height, int32_t width, int32_t channels, int32_t key_views,
                                       int32_t splits, int32_t with_shift, void* stream_) {
-    using namespace tsplat::winattn;
     if (!q || !kv_x3 || !out) return TSPLAT_EINVAL;
-    Params p;
-    if (x3_params(p, batch, height, width, channels, key_views, splits, with_shift, 0) != TSPLAT_OK)
+    Plan pl;
+    if (make_plan(Family::x3, {batch, height, width, channels, key_views, splits, with_shift, 0}, read_knobs(), pl) ||
+        bind_workspace(pl, workspace))
         return TSPLAT_EINVAL;
-    Partials part{nullptr, nullptr, nullptr};
-    if (p.ksplit > 1) {
-        if (!workspace) return TSPLAT_EINVAL;
-        const size_t n = (size_t)batch * splits * splits * p.ksplit * p.L;
-        part.o = (float*)workspace;
-        part.m = part.o + n * kC;
-        part.l = part.m + n;
-    }
     const size_t nkv = (size_t)batch * key_views * height * width * kC;
-    const __bf16* kv = (const __bf16*)kv_x3;
     hipStream_t stream = (hipStream_t)stream_;
     const prof::ExtEvents ev = prof::ext_events(prof::kWinAttn);
-    launch_x3(p, splits, batch, q, kv, nkv, out, part, ev, stream);
-    if (p.ksplit > 1)
-        hipLaunchKernelGGL(win_attn_combine_x32_kernel<float>, dim3(p.L / kBQ3 * 16, splits * splits, batch),
-                           dim3(kThreads), 0, stream, p, part, out);
+    launch_x3(pl, q, (const __bf16*)kv_x3, nkv, out, ev, stream);
+    launch_combine(pl, out, stream);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
 }

@@ -77,6 +77,19 @@ def pack_cameras(intr: torch.Tensor, pose: torch.Tensor) -> torch.Tensor:
          pose[:, :3, 3].float()], dim=1).contiguous()
 
 
+def _win_attn_workspace_bytes(lib, family: str, b: int, h: int, w: int, m: int, num_splits: int) -> int:
+    """Bytes of split-key partials the window attention of `family` ("fp32", "bf16" or "x3") writes for
+    this launch shape (0: no key split). The bf16x3 kernels share the exact-fp32 kernels' plan."""
+    fn = lib.tsplat_win_attn_bf16_workspace_bytes if family == "bf16" else lib.tsplat_win_attn_workspace_bytes
+    return int(fn(b, h, w, m, num_splits))
+
+
+def _win_attn_workspace(lib, family: str, b: int, h: int, w: int, m: int, num_splits: int, device):
+    """The workspace tensor of _win_attn_workspace_bytes, or None where the launch needs none."""
+    nbytes = _win_attn_workspace_bytes(lib, family, b, h, w, m, num_splits)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
 def window_attention(q, k, v, h: int, w: int, num_splits: int, with_shift: bool, kv_shift: int = 0):
     """Shifted-window attention (reference single_head_split_window_attention).
     q [B, L, C]; k, v [B, L, C] or [B, m, L, C] -> [B, L, C]. bf16 inputs (the dense layers under
@@ -89,8 +102,7 @@ def window_attention(q, k, v, h: int, w: int, num_splits: int, with_shift: bool,
     if q.dtype == k.dtype == v.dtype == torch.bfloat16 and wl % 128 == 0:
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         out = torch.empty((b, l, c), dtype=torch.bfloat16, device=q.device)
-        nbytes = int(lib.tsplat_win_attn_bf16_workspace_bytes(b, h, w, m, num_splits))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+        ws = _win_attn_workspace(lib, "bf16", b, h, w, m, num_splits, q.device)
         rc = lib.tsplat_win_attn_bf16_shift_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(ws),
                                                 b, h, w, c, m, num_splits, int(with_shift), int(kv_shift) % b,
                                                 _lib.stream_ptr(q.device))
@@ -100,8 +112,7 @@ def window_attention(q, k, v, h: int, w: int, num_splits: int, with_shift: bool,
         k, v = torch.roll(k, -kv_shift, dims=0), torch.roll(v, -kv_shift, dims=0)
     q, k, v = _f32(q), _f32(k), _f32(v)
     out = torch.empty((b, l, c), dtype=torch.float32, device=q.device)
-    nbytes = int(lib.tsplat_win_attn_workspace_bytes(b, h, w, m, num_splits))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+    ws = _win_attn_workspace(lib, "fp32", b, h, w, m, num_splits, q.device)
     rc = lib.tsplat_win_attn_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(ws), b, h, w, c,
                                  m, num_splits, int(with_shift), _lib.stream_ptr(q.device))
     _lib.check(rc, "tsplat_win_attn_fwd")
@@ -492,8 +503,7 @@ def window_attention_x3(q, k, v, h: int, w: int, num_splits: int, with_shift: bo
     kv = split_kv_bf16x3(k, v)
     qf = _f32(q).contiguous()
     out = torch.empty_like(qf)
-    ws = torch.empty(max(int(lib.tsplat_win_attn_workspace_bytes(b, h, w, m, num_splits)), 4), dtype=torch.uint8,
-                     device=q.device)
+    ws = _win_attn_workspace(lib, "x3", b, h, w, m, num_splits, q.device)
     _lib.check(lib.tsplat_win_attn_x3_fwd(_lib.ptr(qf), _lib.ptr(kv), _lib.ptr(out), _lib.ptr(ws), b, h, w, c, m,
                                           num_splits, int(with_shift), _lib.stream_ptr(q.device)),
                "tsplat_win_attn_x3_fwd")
@@ -589,8 +599,7 @@ def _merge_partials(lib, q, k, v, h, w, num_splits, with_shift, merge_weight, ln
     """attention_merge's key-split path: the attention kernel's partials + the merge projection."""
     b, l, c = q.shape
     q = q.contiguous()
-    ws = torch.empty(int(lib.tsplat_win_attn_workspace_bytes(b, h, w, m, num_splits)), dtype=torch.uint8,
-                     device=q.device)
+    ws = _win_attn_workspace(lib, "x3" if _ATTN == "bf16x3" else "fp32", b, h, w, m, num_splits, q.device)
     if _ATTN == "bf16x3":
         kv = kv_x3 if kv_x3 is not None else split_kv_bf16x3(k, v)
         rc = lib.tsplat_win_attn_x3_partials_fwd(_lib.ptr(q), _lib.ptr(kv), _lib.ptr(ws), b, h, w, c, m, num_splits,
