@@ -667,6 +667,22 @@ int tsplat_residual_ln_slabs_fwd(const float* x, const float* y, int32_t nslab, 
                                  const float* ln_b, float ln_eps, float* x_out, float* n_out, int32_t rows,
                                  int32_t dim, void* stream);
 
+/* SSIM of the evaluation (reference compute_ssim, src/evaluation/metrics.py:36-52, recorded per scene
+ * by test_step, src/model/model_wrapper.py:315-317): skimage's structural_similarity(gt, hat,
+ * win_size=11, gaussian_weights=True, channel_axis=0, data_range=1.0) per image, on the device. gt and
+ * pred [n, 3, height, width] fp32 contiguous (not clipped), ssim [n] fp32. Per channel the separable
+ * 11-tap Gaussian (sigma 1.5, weights normalised in float64) filters x, y, x x, y y and x y; with the
+ * sample covariances (factor 121 / 120), C1 = 1e-4 and C2 = 9e-4 the SSIM map is averaged over rows
+ * 5..height-6, columns 5..width-6 and the three channels. Every intermediate is float64; only ssim[i]
+ * is rounded to fp32. Deterministic (no atomics; one partial per 32 x 32 tile in workspace, summed per
+ * image in a fixed order by a second launch), and ssim[i] depends on neither n nor i.
+ * workspace: tsplat_ssim_workspace_bytes(n, height, width) bytes, 8-byte aligned (0 for arguments
+ * tsplat_ssim_fwd rejects). TSPLAT_EINVAL, before any launch: a null pointer, n <= 0, height or width
+ * below 11 (skimage raises there), or n * 3 * tiles beyond a 1-D grid (2^31 - 1). */
+size_t tsplat_ssim_workspace_bytes(int32_t n, int32_t height, int32_t width);
+int tsplat_ssim_fwd(const float* gt, const float* pred, float* ssim, void* workspace, int32_t n, int32_t height,
+                    int32_t width, void* stream);
+
 /* Diagnostics: write the 100-MHz device wall clock into ((uint64_t*)buf)[slot] when this launch
  * runs on `stream` (stage marks of a captured / replayed step, tools/graph_stages.py). */
 int tsplat_timestamp(void* buf, int32_t slot, void* stream);

@@ -1,8 +1,8 @@
 """Scene-sharded evaluation: rank r of N takes scenes r, r+N, ... of the evaluation
-index, runs the reference test_step sequence (encoder -> decoder -> PSNR per target view,
+index, runs the reference test_step sequence (encoder -> decoder -> PSNR and SSIM per target view,
 reference src/model/model_wrapper.py:185-323) and the per-scene metrics are gathered once at the
-end with ONE all_gather of a fixed-width fp32 tensor [n_local, 4] = (scene_idx, psnr, n_views,
-seconds) — RCCL over xGMI on GPUs, gloo on CPU. No collective touches the data path.
+end with ONE all_gather of a fixed-width fp32 tensor [n_local, 6] = (scene_idx, psnr, n_views,
+seconds, capture, ssim) — RCCL over xGMI on GPUs, gloo on CPU. No collective touches the data path.
 
 With no dataset offline, scenes are synthetic (transplat_amd.synthetic) unless a loader is passed;
 the evaluation index (e.g. the reference's assets/evaluation_index_re10k_small.json) supplies the
@@ -10,8 +10,11 @@ scene keys and context/target frame indices.
 
 The step the CLI evaluates is the benched one: `GraphedSteps` replays the whole test_step as one
 hipGraph per input-shape signature (bench.py's timed region), in the bench's default dense precision
-(bf16x3). Per scene the PSNR stays on the device and the step is bracketed by HIP events; the host
-synchronises ONCE per shard, after its last scene, then reads the PSNRs and event times.
+(bf16x3). Per scene the PSNR and the SSIM (tsplat_ssim_fwd) stay on the device and the step is
+bracketed by HIP events; the host synchronises ONCE per shard, after its last scene, then reads the
+metrics and event times. `--output-path DIR` writes the reference's scores files
+(model_wrapper.py:325-343): scores_psnr_all.json, scores_ssim_all.json, scene_all.json,
+scores_all_avg.json.
 """
 from __future__ import annotations
 
@@ -24,7 +27,7 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
-from .evaluation.metrics import compute_psnr
+from .evaluation.metrics import SSIM_WIN, compute_psnr, compute_ssim
 
 
 @dataclass
@@ -34,6 +37,7 @@ class SceneResult:
     n_views: int
     seconds: float
     capture: bool = False  # the step captured its hipGraph (warmup + capture inside `seconds`)
+    ssim: float = float("nan")  # mean over the target views; NaN where it was not computed
 
 
 def load_index(path: str | Path) -> list[tuple[str, dict]]:
@@ -49,9 +53,9 @@ def shard(items: list, rank: int, world: int) -> list[tuple[int, object]]:
 
 
 def gather_results(local: list[SceneResult], device: torch.device, world: int) -> list[SceneResult]:
-    """One all_gather of [n_local_max, 5] fp32 rows (padded with scene_idx = -1)."""
-    rows = torch.tensor([[r.scene_idx, r.psnr, r.n_views, r.seconds, float(r.capture)] for r in local],
-                        dtype=torch.float32, device=device).reshape(-1, 5)
+    """One all_gather of [n_local_max, 6] fp32 rows (padded with scene_idx = -1)."""
+    rows = torch.tensor([[r.scene_idx, r.psnr, r.n_views, r.seconds, float(r.capture), r.ssim] for r in local],
+                        dtype=torch.float32, device=device).reshape(-1, 6)
     if world == 1:
         gathered = [rows]
     else:
@@ -59,7 +63,7 @@ def gather_results(local: list[SceneResult], device: torch.device, world: int) -
         counts = [torch.zeros_like(n) for _ in range(world)]
         dist.all_gather(counts, n)
         nmax = int(max(c.item() for c in counts))
-        pad = torch.full((nmax, 5), -1.0, device=device)
+        pad = torch.full((nmax, 6), -1.0, device=device)
         pad[: rows.shape[0]] = rows
         gathered = [torch.empty_like(pad) for _ in range(world)]
         dist.all_gather(gathered, pad)
@@ -67,7 +71,7 @@ def gather_results(local: list[SceneResult], device: torch.device, world: int) -
     for g in gathered:
         for row in g.cpu().tolist():
             if row[0] >= 0:
-                out.append(SceneResult(int(row[0]), row[1], int(row[2]), row[3], row[4] > 0.5))
+                out.append(SceneResult(int(row[0]), row[1], int(row[2]), row[3], row[4] > 0.5, row[5]))
     return sorted(out, key=lambda r: r.scene_idx)
 
 
@@ -121,6 +125,14 @@ class _Pending:
     def __init__(self, device: torch.device):
         self.device, self.rows = device, []
 
+    @staticmethod
+    def _ssim(gt: torch.Tensor, color: torch.Tensor) -> torch.Tensor:
+        """Mean SSIM over the scene's target views, left on color's device (the per-view fp32 values
+        averaged in float64); NaN for images the 11 x 11 window does not fit, which have no SSIM."""
+        if min(color.shape[-2:]) < SSIM_WIN:
+            return torch.full((), float("nan"), dtype=torch.float64, device=color.device)
+        return compute_ssim(gt, color).double().mean()
+
     def run(self, idx: int, step, batch: dict) -> None:
         from .model.decoder.hip_splatting import status_tensor
 
@@ -129,16 +141,20 @@ class _Pending:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             color = step(batch)
-            psnr = compute_psnr(gt.to(color.device), color[0]).mean()  # before a replay reuses color
-            e1.record()
+            gt = gt.to(color.device)
+            psnr = compute_psnr(gt, color[0]).mean()  # before a replay reuses color
+            e1.record()  # `seconds` = step + PSNR; the SSIM follows on the same stream, outside it
+            ssim = self._ssim(gt, color[0])  # also before the next replay
             st = status_tensor(self.device)
             self.rows.append((idx, psnr, int(color.shape[1]), (e0, e1), getattr(step, "last_captured", False),
-                              st.clone() if st is not None else None))
+                              st.clone() if st is not None else None, ssim))
         else:
             t0 = time.perf_counter()
             color = step(batch)
-            psnr = compute_psnr(gt.to(color.device), color[0]).mean()
-            self.rows.append((idx, psnr, int(color.shape[1]), time.perf_counter() - t0, False, None))
+            gt = gt.to(color.device)
+            psnr = compute_psnr(gt, color[0]).mean()
+            sec = time.perf_counter() - t0
+            self.rows.append((idx, psnr, int(color.shape[1]), sec, False, None, self._ssim(gt, color[0])))
 
     def results(self) -> list[SceneResult]:
         if self.device.type == "cuda":
@@ -150,9 +166,9 @@ class _Pending:
                 raise RuntimeError(f"tsplat_raster_fwd: instance capacity exceeded (first at scene {bad[0]})")
             _raster_status(self.device)
         out = []
-        for idx, psnr, nv, t, cap, _ in self.rows:
+        for idx, psnr, nv, t, cap, _, ssim in self.rows:
             sec = t[0].elapsed_time(t[1]) / 1e3 if isinstance(t, tuple) else t
-            out.append(SceneResult(idx, float(psnr.item()), nv, sec, bool(cap)))
+            out.append(SceneResult(idx, float(psnr.item()), nv, sec, bool(cap), float(ssim.item())))
         return out
 
 
@@ -168,12 +184,16 @@ def evaluate(step: Callable[[dict], torch.Tensor], scenes: list, make_batch: Cal
 
 
 def evaluate_stream(step: Callable[[dict], torch.Tensor], examples, device: torch.device, rank: int = 0,
-                    world: int = 1) -> list[SceneResult]:
+                    world: int = 1, keys: Optional[list] = None) -> list[SceneResult]:
     """Like `evaluate`, over an iterable of ready batches (the chunk reader): example i of the
     stream is scene i, and rank r keeps i = r, r + N, ... (every rank decodes the same stream
-    order, so the split matches the index-driven one)."""
+    order, so the split matches the index-driven one). `keys`, if given, receives every example's
+    scene key (batch["scene"][0], the reference's model_wrapper.py:321-323) in stream order, on
+    every rank."""
     pend = _Pending(device)
     for idx, batch in enumerate(examples):
+        if keys is not None:
+            keys.append(batch["scene"][0])
         if idx % world != rank:
             continue
         batch = {k: ({kk: vv.to(device) for kk, vv in v.items()} if isinstance(v, dict) else v)
@@ -183,19 +203,38 @@ def evaluate_stream(step: Callable[[dict], torch.Tensor], examples, device: torc
 
 
 def summarize(results: list[SceneResult]) -> dict:
-    """PSNR over every scene; `seconds` over the steady scenes only (a scene whose step captured a
-    hipGraph carries the warmup and the capture, reported apart as `capture_seconds`)."""
+    """PSNR and SSIM over every scene; `seconds` over the steady scenes only (a scene whose step
+    captured a hipGraph carries the warmup and the capture, reported apart as `capture_seconds`)."""
     n = len(results)
     steady = [r for r in results if not r.capture]
     return {
         "scenes": n,
         "psnr": sum(r.psnr for r in results) / max(n, 1),
+        "ssim": sum(r.ssim for r in results) / max(n, 1),
         "views": sum(r.n_views for r in results),
         "seconds": sum(r.seconds for r in steady),
         "steady_scenes": len(steady),
         "capture_scenes": n - len(steady),
         "capture_seconds": sum(r.seconds for r in results if r.capture),
     }
+
+
+def write_scores(results: list[SceneResult], keys: list[str], out_dir: str | Path) -> dict:
+    """The reference's scores files (on_test_end, src/model/model_wrapper.py:325-343, :521-522) in
+    `out_dir`: scores_psnr_all.json and scores_ssim_all.json (per-scene floats in scene order),
+    scene_all.json (keys[r.scene_idx] in the same order) and scores_all_avg.json ({"psnr", "ssim"}:
+    sum / count as there). Returns the averages."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    results = sorted(results, key=lambda r: r.scene_idx)
+    avg = {}
+    for metric in ("psnr", "ssim"):
+        scores = [getattr(r, metric) for r in results]
+        avg[metric] = sum(scores) / len(scores) if scores else float("nan")
+        (out_dir / f"scores_{metric}_all.json").write_text(json.dumps(scores))
+    (out_dir / "scene_all.json").write_text(json.dumps([keys[r.scene_idx] for r in results]))
+    (out_dir / "scores_all_avg.json").write_text(json.dumps(avg))
+    return avg
 
 
 def index_batch(idx: int, key: str, entry: dict, image_shape=(256, 256), device="cpu") -> dict:
@@ -228,6 +267,9 @@ def main(argv=None):
     ap.add_argument("--data-root", action="append", default=None,
                     help="dataset root holding test/*.torch chunks (repeatable); real frames instead of synthetic")
     ap.add_argument("--experiment", choices=["re10k", "acid", "dtu"], default="re10k")
+    ap.add_argument("--output-path", default=None,
+                    help="directory for the reference's scores files (scores_psnr_all.json, scores_ssim_all.json, "
+                         "scene_all.json, scores_all_avg.json), written by rank 0; nothing is written without it")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -255,14 +297,18 @@ def main(argv=None):
         cfg = ChunkDatasetCfg(roots=tuple(args.data_root), **EXPERIMENTS[args.experiment])
         ds = ChunkTestDataset.from_index_file(cfg, args.index)
         stream = (ChunkTestDataset.batch(ex) for ex in islice(iter(ds), args.limit))
-        results = evaluate_stream(step, stream, device, rank, world)
+        keys = []  # the examples' scene strings, in stream order
+        results = evaluate_stream(step, stream, device, rank, world, keys)
         data = f"{args.experiment} chunks under {args.data_root}"
     else:
         scenes = load_index(args.index)[: args.limit]
+        keys = [k for k, _ in scenes]
         results = evaluate(step, [(k, v) for k, v in scenes],
                            lambda i, kv: index_batch(i, kv[0], kv[1], device=device), device, rank, world)
         data = "synthetic frames at the index's frame positions"
     if rank == 0:
+        if args.output_path:
+            write_scores(results, keys, args.output_path)
         summary = summarize(results)
         summary.update({"index": str(args.index), "world": world, "weights": args.checkpoint or "synthetic",
                         "data": data, "dense_dtype": args.dense_dtype, "graph": not args.no_graph,

@@ -717,6 +717,30 @@ def depth_tail(fullres, head, near, far):
     return depth, dens
 
 
+def ssim(gt, pred):
+    """Per-image SSIM of [n, 3, H, W] pairs as the reference's compute_ssim defines it (skimage's
+    structural_similarity with win_size=11, gaussian_weights=True, data_range=1.0; inputs not
+    clipped) -> [n] fp32, float64 inside (tsplat_ssim_fwd). H, W >= 11."""
+    lib = _lib.load()
+    if not (gt.is_cuda and pred.is_cuda):
+        raise RuntimeError("transplat HIP ops need device tensors (no CPU path)")
+    if gt.shape != pred.shape:
+        raise ValueError(f"ssim: ground truth {tuple(gt.shape)} != prediction {tuple(pred.shape)}")
+    if gt.dim() != 4 or gt.shape[1] != 3:
+        raise ValueError(f"ssim: expected [n, 3, H, W] images, got {tuple(gt.shape)}")
+    n, _, h, w = gt.shape
+    if h < 11 or w < 11:
+        raise ValueError(f"ssim: the 11 x 11 window does not fit a {h} x {w} image")
+    out = torch.empty((n,), dtype=torch.float32, device=gt.device)
+    if n == 0:
+        return out
+    g, p = _f32(gt), _f32(pred)
+    ws = torch.empty(int(lib.tsplat_ssim_workspace_bytes(n, h, w)), dtype=torch.uint8, device=gt.device)
+    _lib.check(lib.tsplat_ssim_fwd(_lib.ptr(g), _lib.ptr(p), _lib.ptr(out), _lib.ptr(ws), n, h, w,
+                                   _lib.stream_ptr(gt.device)), "tsplat_ssim_fwd")
+    return out
+
+
 # DINOv2's attention in split-bf16 precision inside dense_precision("bf16x3") (tsplat_mha_x3_fwd) for
 # up to _MHA_X3_ROWS tokens per call: same-box C2 (2 x 325 tokens) 446.9 / 447.8 vs 445.6 / 445.5
 # views/s with the exact-fp32 kernel, but C3 (16 x 325) 900.1 / 899.8 vs 903.4 / 902.1 -- there the
