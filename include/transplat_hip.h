@@ -666,6 +666,31 @@ int tsplat_gemm_x3_fwd(const float* x, const void* wp, const float* bias, float*
 int tsplat_residual_ln_slabs_fwd(const float* x, const float* y, int32_t nslab, const float* ls, const float* ln_w,
                                  const float* ln_b, float ln_eps, float* x_out, float* n_out, int32_t rows,
                                  int32_t dim, void* stream);
+/* The same with x [x_rows, dim] repeated over the rows (row r reads x row r % x_rows; rows % x_rows == 0):
+ * DINOv2's first step, x = (position embedding + class token / patch bias, one [1 + N, dim] constant for
+ * every image) + the patch projection's slabs (src/depth_anything_v2/dinov2.py prepare_tokens). */
+int tsplat_residual_ln_slabs_bcast_fwd(const float* x, int32_t x_rows, const float* y, int32_t nslab, const float* ls,
+                                       const float* ln_w, const float* ln_b, float ln_eps, float* x_out, float* n_out,
+                                       int32_t rows, int32_t dim, void* stream);
+
+/* Depth-Anything's input glue in one launch (reference src/model/encoder/encoder_trans.py:215-222 and
+ * dinov2.py PatchEmbed): image [nimg, 3, height, width] fp32 -> out [nimg * (1 + grid_h grid_w),
+ * 3 patch^2], the patch projection's GEMM operand. Row 0 of an image is zeros (the class-token slot);
+ * row 1 + py grid_w + px is patch (py, px) of the image normalised ((v - mean[c]) / std[c]), reordered
+ * to channels (2, 0, 1) and resized to (grid_h patch, grid_w patch) bilinearly with
+ * align_corners = True, unfolded as [channel][i][j]. Same fp32 operations as the separate launches
+ * (tsplat_resize_bilinear_nchw_fwd's formula): bit-identical values. mean / std: 3 floats on the device. */
+int tsplat_da_patches_fwd(const float* image, const float* mean, const float* stdv, float* out, int32_t nimg,
+                          int32_t height, int32_t width, int32_t grid_h, int32_t grid_w, int32_t patch, void* stream);
+
+/* Depth-Anything's output glue in two launches (encoder_trans.py:226-240): x [nimg, height, width] fp32
+ * (the DPT's last 1x1 output) -> resized [nimg, out_height, out_width] = bilinear resize
+ * (align_corners = True) of relu(x), with one (min, max) pair per workgroup in partials
+ * [nimg, tsplat_depth_norm_blocks(out_height, out_width), 2] (plain stores, fixed order); then out =
+ * (resized - min) / (max - min) per image (max == min gives NaN, as the elementwise sequence does). */
+int32_t tsplat_depth_norm_blocks(int32_t out_height, int32_t out_width);
+int tsplat_depth_norm_fwd(const float* x, float* resized, float* partials, float* out, int32_t nimg, int32_t height,
+                          int32_t width, int32_t out_height, int32_t out_width, void* stream);
 
 /* SSIM of the evaluation (reference compute_ssim, src/evaluation/metrics.py:36-52, recorded per scene
  * by test_step, src/model/model_wrapper.py:315-317): skimage's structural_similarity(gt, hat,

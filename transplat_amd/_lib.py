@@ -98,6 +98,11 @@ SIGNATURES = {
     "tsplat_gemm_x3_pack_bytes": (ctypes.c_size_t, [_I32, _I32]),
     "tsplat_gemm_x3_pack": (ctypes.c_int, [_P, _P, _I32, _I32, _P]),
     "tsplat_gemm_x3_fwd": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "tsplat_residual_ln_slabs_bcast_fwd": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P, ctypes.c_float, _P, _P, _I32,
+                                                          _I32, _P]),
+    "tsplat_da_patches_fwd": (ctypes.c_int, [_P] * 4 + [_I32] * 6 + [_P]),
+    "tsplat_depth_norm_blocks": (_I32, [_I32, _I32]),
+    "tsplat_depth_norm_fwd": (ctypes.c_int, [_P] * 4 + [_I32] * 5 + [_P]),
     "tsplat_residual_ln_bf16_fwd": (ctypes.c_int, [_P] * 5 + [ctypes.c_float, _P, _P, _I32, _I32, _P]),
     "tsplat_bias_act_fwd": (ctypes.c_int, [_P] * 4 + [_I32, _I32, ctypes.c_int64, _I32, _P]),
     "tsplat_bias_act_nhwc_fwd": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int64, _I32, _I32, _P]),

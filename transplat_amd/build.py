@@ -35,7 +35,8 @@ HIPCC_FLAGS = [
 # and the SLP vectoriser's packed form needs operand-pairing register moves: 84 -> 74 cycles per
 # (entry, pixel) without it)
 FILE_FLAGS = {"raster.hip": ["-fno-slp-vectorize"],
-              "upsample.hip": ["-ffp-contract=off"]}  # torch's rounding of the interpolation weights
+              "upsample.hip": ["-ffp-contract=off"],  # torch's rounding of the interpolation weights
+              "daglue.hip": ["-ffp-contract=off"]}  # the same formula, and torch's separate sub / div / mul / add
 
 
 def _hipcc() -> str:

@@ -531,18 +531,19 @@ template <int V4, typename TY, typename TN>  // float4s per lane (dim = 256 V4)
 __global__ void __launch_bounds__(kThreads)
 residual_ln_kernel(const float* __restrict__ x, const TY* __restrict__ y, const float* __restrict__ ls,
                    const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ x_out,
-                   TN* __restrict__ n_out, int rows, float eps, int nslab) {
+                   TN* __restrict__ n_out, int rows, float eps, int nslab, int xrows) {
     const int row = blockIdx.x * (kThreads / kWave) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
     constexpr int D = 256 * V4;
     const size_t off = (size_t)row * D;
+    const size_t xoff = (size_t)(row % xrows) * D;  // x [xrows, D] repeats every xrows rows (xrows = rows: no repeat)
     float4 v[V4];
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < V4; ++k) {
         const int c = 4 * (lane + 64 * k);
-        v[k] = *reinterpret_cast<const float4*>(x + off + c);
+        v[k] = *reinterpret_cast<const float4*>(x + xoff + c);
         if (y) {
             float4 t = ld4(y + off + c);
             // split-K slabs, summed in slab order (deterministic)
@@ -590,15 +591,17 @@ residual_ln_kernel(const float* __restrict__ x, const TY* __restrict__ y, const 
 template <typename TY, typename TN>
 static int residual_ln_launch(const float* x, const TY* y, const float* ls, const float* ln_w, const float* ln_b,
                               float ln_eps, float* x_out, TN* n_out, int32_t rows, int32_t dim, void* stream_,
-                              int32_t nslab = 1) {
+                              int32_t nslab = 1, int32_t xrows = 0) {
     using namespace tsplat::gn;
     if (!x || !ln_w || !ln_b || !n_out || rows <= 0 || (ls && !y) || nslab < 1) return TSPLAT_EINVAL;
+    if (xrows == 0) xrows = rows;
+    if (xrows < 0 || rows % xrows || (xrows != rows && !x_out)) return TSPLAT_EINVAL;
     if (y && !x_out) return TSPLAT_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid((rows + kThreads / kWave - 1) / (kThreads / kWave));
 #define TSPLAT_RLN(V)                                                                                   \
     hipLaunchKernelGGL((residual_ln_kernel<V, TY, TN>), grid, dim3(kThreads), 0, stream, x, y, ls, ln_w, ln_b, \
-                       x_out, n_out, rows, ln_eps, nslab)
+                       x_out, n_out, rows, ln_eps, nslab, xrows)
     switch (dim) {
         case 256: TSPLAT_RLN(1); break;
         case 512: TSPLAT_RLN(2); break;
@@ -622,6 +625,15 @@ extern "C" int tsplat_residual_ln_slabs_fwd(const float* x, const float* y, int3
                                             float* n_out, int32_t rows, int32_t dim, void* stream_) {
     if (!y) return TSPLAT_EINVAL;
     return residual_ln_launch<float, float>(x, y, ls, ln_w, ln_b, ln_eps, x_out, n_out, rows, dim, stream_, nslab);
+}
+
+extern "C" int tsplat_residual_ln_slabs_bcast_fwd(const float* x, int32_t x_rows, const float* y, int32_t nslab,
+                                                  const float* ls, const float* ln_w, const float* ln_b,
+                                                  float ln_eps, float* x_out, float* n_out, int32_t rows,
+                                                  int32_t dim, void* stream_) {
+    if (!y || x_rows <= 0) return TSPLAT_EINVAL;
+    return residual_ln_launch<float, float>(x, y, ls, ln_w, ln_b, ln_eps, x_out, n_out, rows, dim, stream_, nslab,
+                                            x_rows);
 }
 
 extern "C" int tsplat_residual_ln_bf16_fwd(const float* x, const void* y, const float* ls, const float* ln_w,

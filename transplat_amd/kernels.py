@@ -630,11 +630,27 @@ def residual_ln(x, y, ls, norm, bf16_out: bool = False):
     norm: an nn.LayerNorm (weight, bias, eps); ls: LayerScale gamma or None. A bf16 y, or
     bf16_out, selects the bf16 form (y read and LN written in bf16; x fp32 either way). y with one
     leading dimension more than x is the split-K slabs of gemm_x3 (summed in order,
-    tsplat_residual_ln_slabs_fwd)."""
+    tsplat_residual_ln_slabs_fwd); with slabs, an x whose first dimension is 1 is one [rows, d] residual
+    repeated over the slabs' first dimension (tsplat_residual_ln_slabs_bcast_fwd; x_out has the slabs'
+    shape)."""
     lib = _lib.load()
     d = x.shape[-1]
     xf = _f32(x)
     rows = xf.numel() // d
+    if (y is not None and y.dim() == x.dim() + 1 and x.dim() >= 2 and x.shape[0] == 1 and y.shape[1] != 1
+            and tuple(y.shape[2:]) == tuple(x.shape[1:])):
+        if y.dtype != torch.float32 or bf16_out:
+            raise ValueError(f"residual_ln: slabs {tuple(y.shape)} for x {tuple(x.shape)}")
+        yf = y.contiguous()
+        x_out = torch.empty(y.shape[1:], dtype=torch.float32, device=x.device)
+        n_out = torch.empty_like(x_out)
+        rc = lib.tsplat_residual_ln_slabs_bcast_fwd(_lib.ptr(xf), rows, _lib.ptr(yf), y.shape[0],
+                                                    _lib.ptr(_f32(ls)) if ls is not None else None,
+                                                    _lib.ptr(_f32(norm.weight)), _lib.ptr(_f32(norm.bias)),
+                                                    float(norm.eps), _lib.ptr(x_out), _lib.ptr(n_out),
+                                                    x_out.numel() // d, d, _lib.stream_ptr(x.device))
+        _lib.check(rc, "tsplat_residual_ln_slabs_bcast_fwd")
+        return x_out, n_out
     if y is not None and y.dim() == x.dim() + 1:
         if y.dtype != torch.float32 or bf16_out or tuple(y.shape[1:]) != tuple(x.shape):
             raise ValueError(f"residual_ln: slabs {tuple(y.shape)} for x {tuple(x.shape)}")
@@ -1387,17 +1403,20 @@ GEMM_LOG = None  # list: (m, n, k, ksplit) per launch when set (bench.py's roofl
 
 def gemm_x3_ok(x, weight) -> bool:
     """True when gemm_x3 takes F.linear(x, weight) in the current mode: bf16x3 dense mode, fp32 on
-    the GPU, k and n multiples of 4."""
+    the GPU, k and n multiples of 4. weight [n, k], or [n, ...] read as [n, k] (a 1x1 or
+    kernel = stride convolution weight)."""
     if not (_GEMM_X3 and _DENSE == "bf16x3" and x.is_cuda and x.dtype == torch.float32
             and weight.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")):
         return False
-    n, k = weight.shape
+    n = weight.shape[0]
+    k = weight.numel() // n
     return k % 4 == 0 and n % 4 == 0 and x.shape[-1] == k
 
 
 def _pack_gemm(weight):
     lib = _lib.load()
-    n, k = weight.shape
+    n = weight.shape[0]
+    k = weight.numel() // n
     wf = _f32(weight)
     wp = torch.empty(int(lib.tsplat_gemm_x3_pack_bytes(n, k)), dtype=torch.uint8, device=weight.device)
     _lib.check(lib.tsplat_gemm_x3_pack(_lib.ptr(wf), _lib.ptr(wp), n, k, _lib.stream_ptr(weight.device)),
@@ -1427,9 +1446,10 @@ def gemm_ksplit(m: int, n: int, k: int) -> int:
 def gemm_x3(x, weight, bias=None, act: str = "none", ksplit: int = 1):
     """act(x W^T + bias) on the split-bf16 GEMM (tsplat_gemm_x3_fwd); ksplit > 1 returns the [ksplit,
     *x.shape[:-1], n] partial slabs (bias in slab 0) for residual_ln to sum; ksplit 0: gemm_ksplit's
-    choice (1 with an activation)."""
+    choice (1 with an activation). weight [n, k] or [n, ...] (see gemm_x3_ok)."""
     lib = _lib.load()
-    n, k = weight.shape
+    n = weight.shape[0]
+    k = weight.numel() // n
     xf = _f32(x)
     m = xf.numel() // k
     if ksplit == 0:
@@ -1756,6 +1776,44 @@ def interpolate_bilinear_ac(x, size):
                                              _lib.stream_ptr(x.device))
     _lib.check(rc, "tsplat_resize_bilinear_nchw_fwd")
     return y
+
+
+# Depth-Anything's glue as HIP kernels, one A/B knob each ("0": the PyTorch launches): images -> patch
+# matrix -> patch projection on gemm_x3; the depth tail
+DA_PATCH = os.environ.get("TSPLAT_DA_PATCH", "1") != "0"
+DA_TAIL = os.environ.get("TSPLAT_DA_TAIL", "1") != "0"
+
+
+def da_patches(images, mean, std, grid, patch: int):
+    """images [..., 3, h, w] fp32 -> the patch matrix [n (1 + gh gw), 3 patch^2] of the images
+    normalised with mean / std ([3] device tensors), reordered to channels (2, 0, 1) and resized to
+    (gh patch, gw patch) with align_corners; row 0 of every image zeros (tsplat_da_patches_fwd)."""
+    lib = _lib.load()
+    h, w = images.shape[-2:]
+    gh, gw = int(grid[0]), int(grid[1])
+    xf = _f32(images)
+    n = xf.numel() // (3 * h * w)
+    out = torch.empty((n * (1 + gh * gw), 3 * patch * patch), dtype=torch.float32, device=images.device)
+    rc = lib.tsplat_da_patches_fwd(_lib.ptr(xf), _lib.ptr(_f32(mean)), _lib.ptr(_f32(std)), _lib.ptr(out), n, h, w, gh,
+                                   gw, patch, _lib.stream_ptr(images.device))
+    _lib.check(rc, "tsplat_da_patches_fwd")
+    return out
+
+
+def depth_norm(x, size):
+    """x [n, h, w] fp32 -> [n, size] = (d - min d) / (max d - min d) per image, d =
+    interpolate_bilinear_ac(relu(x), size) (tsplat_depth_norm_fwd: two launches)."""
+    lib = _lib.load()
+    n, h, w = x.shape
+    ho, wo = int(size[0]), int(size[1])
+    xf = _f32(x)
+    resized = torch.empty((n, ho, wo), dtype=torch.float32, device=x.device)
+    out = torch.empty_like(resized)
+    partials = torch.empty((n, int(lib.tsplat_depth_norm_blocks(ho, wo)), 2), dtype=torch.float32, device=x.device)
+    rc = lib.tsplat_depth_norm_fwd(_lib.ptr(xf), _lib.ptr(resized), _lib.ptr(partials), _lib.ptr(out), n, h, w, ho, wo,
+                                   _lib.stream_ptr(x.device))
+    _lib.check(rc, "tsplat_depth_norm_fwd")
+    return out
 
 
 def sh_rotation(rotations, d_sh: int):

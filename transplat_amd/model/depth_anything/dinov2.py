@@ -193,6 +193,46 @@ class DinoVisionTransformer(nn.Module):
         x = torch.cat((self.cls_token.expand(x.shape[0], -1, -1).to(x.dtype), x), dim=1)
         return x + self.interpolate_pos_encoding(x, w, h).to(x.dtype)
 
+    def patches_ok(self, images) -> bool:
+        """Whether prepare_tokens_patches takes these images (bf16x3 dense mode, fp32 on the GPU, the
+        fused block chain with a plain first LayerNorm)."""
+        proj = self.patch_embed.proj
+        return (kernels.DA_PATCH and images.is_cuda and images.dtype == torch.float32
+                and isinstance(self.patch_embed.norm, nn.Identity) and type(self.blocks[0].norm1) is nn.LayerNorm
+                and self.embed_dim in (256, 512, 768, 1024) and proj.bias is not None
+                and kernels.gemm_x3_ok(images.new_empty((0, proj.weight[0].numel())), proj.weight)
+                and self._fused_ok(self.cls_token))
+
+    def _token_base(self, gh: int, gw: int):
+        """[1, 1 + N, D]: what every image's tokens start from besides the patch products -- row 0
+        cls_token + pos[0], row n pos[n] + the projection's bias. Constant per weights and grid: cached
+        on the versions of the three parameters (pos through interpolate_pos_encoding's own cache)."""
+        p = self.patch_size
+        like = self.cls_token.expand(1, 1 + gh * gw, self.embed_dim)  # shape / dtype / device only
+        pos = self.interpolate_pos_encoding(like, gh * p, gw * p)
+        bias = self.patch_embed.proj.bias
+        key = (id(pos), self.cls_token.data_ptr(), self.cls_token._version, bias.data_ptr(), bias._version)
+        cached = getattr(self, "_base_cache", None)
+        if cached is not None and cached[0] == key and cached[1] is pos:
+            return cached[2]
+        with torch.no_grad():
+            base = pos.detach().float().clone()
+            base[:, :1] += self.cls_token.detach()
+            base[:, 1:] += bias.detach()
+        self._base_cache = (key, pos, base)
+        return base
+
+    def prepare_tokens_patches(self, patches, n_img: int, gh: int, gw: int):
+        """prepare_tokens + the first block's norm1 from the patch matrix of kernels.da_patches
+        ([n_img (1 + N), 3 p p], class-token rows zero): the projection on the split-bf16 GEMM (its
+        split-K slabs; no bias) and x = base + sum of slabs, h = norm1(x) in one launch. The zero rows
+        make the class token's row of x exactly cls_token + pos[0]. -> (x, h), each [n_img, 1 + N, D]."""
+        slabs = kernels.gemm_x3(patches, self.patch_embed.proj.weight, None, ksplit=0)
+        if slabs.dim() == 2:
+            slabs = slabs[None]
+        slabs = slabs.view(slabs.shape[0], n_img, 1 + gh * gw, self.embed_dim)
+        return kernels.residual_ln(self._token_base(gh, gw), slabs, None, self.blocks[0].norm1)
+
     def _fused_ok(self, x) -> bool:
         # fp32, or bf16 autocast (the linears then read the bf16 LayerNorm outputs directly)
         autocast = torch.is_autocast_enabled(x.device.type)
@@ -201,16 +241,18 @@ class DinoVisionTransformer(nn.Module):
         return (ok_dtype and x.shape[-1] in (256, 512, 768, 1024)
                 and all(isinstance(m, (LayerScale, nn.Identity)) for b in self.blocks for m in (b.ls1, b.ls2)))
 
-    def _blocks_fused(self, x, take, norm: bool, on_output=None):
+    def _blocks_fused(self, x, take, norm: bool, on_output=None, h=None):
         """The block chain with every pre-norm residual step x = x + ls(y), h = norm_next(x) as ONE
-        kernel (kernels.residual_ln) instead of mul + add + LayerNorm launches; same math."""
+        kernel (kernels.residual_ln) instead of mul + add + LayerNorm launches; same math. `h`: the
+        first block's norm1(x), if the caller has it (prepare_tokens_patches)."""
         gamma = lambda m: m.gamma if isinstance(m, LayerScale) else None
         blocks = self.blocks
         # bf16 autocast: the residual stream stays fp32 (as x + ls * y promotes it under autocast)
         # and the normalised rows are handed to the bf16 linears as bf16
         bf = torch.is_autocast_enabled(x.device.type)
         x = x.float()
-        _, h = kernels.residual_ln(x, None, None, blocks[0].norm1, bf16_out=bf)
+        if h is None:
+            _, h = kernels.residual_ln(x, None, None, blocks[0].norm1, bf16_out=bf)
         outputs = []
         for i, blk in enumerate(blocks):
             x, h2 = kernels.residual_ln(x, blk.attn(h, slabs=True), gamma(blk.ls1), blk.norm2, bf16_out=bf)
@@ -227,14 +269,19 @@ class DinoVisionTransformer(nn.Module):
         return outputs
 
     def get_intermediate_layers(self, x, n=4, reshape=False, return_class_token=False, norm=True,
-                                on_output=None):
+                                on_output=None, tokens=None):
         """`on_output(k, tokens)` (not in the reference) is called as soon as the k-th taken layer's
         normed tokens [B, 1 + N, C] exist, so a consumer can start on them while the later blocks
-        run (DepthAnythingV2.forward forks the DPT reassemble branches this way)."""
-        x = self.prepare_tokens(x)
+        run (DepthAnythingV2.forward forks the DPT reassemble branches this way). `tokens` (not in
+        the reference): prepare_tokens_patches' (x, h) in place of the images x."""
         take = range(len(self.blocks) - n, len(self.blocks)) if isinstance(n, int) else n
-        if self._fused_ok(x):
-            outputs = self._blocks_fused(x, take, norm, on_output)
+        h = None
+        if tokens is not None:
+            x, h = tokens
+        else:
+            x = self.prepare_tokens(x)
+        if h is not None or self._fused_ok(x):
+            outputs = self._blocks_fused(x, take, norm, on_output, h=h)
         else:
             outputs = []
             for i, blk in enumerate(self.blocks):

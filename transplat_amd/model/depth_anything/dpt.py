@@ -200,9 +200,10 @@ class DPTHead(nn.Module):
         x = self.resize_layers[i](self.projects[i](x))
         return getattr(self.scratch, f"layer{i + 1}_rn")(x)
 
-    def forward(self, out_features, patch_h, patch_w, rn=None):
+    def forward(self, out_features, patch_h, patch_w, rn=None, raw_tail: bool = False):
         """`rn` (not in the reference): branch outputs already computed by `reassemble` (None
-        entries are computed here)."""
+        entries are computed here). `raw_tail`: the depth may come back WITHOUT
+        output_conv2's last ReLU (the bf16x3 NCHW route only); the caller applies ReLU either way."""
         self.prepare(out_features[0][0].is_cuda)
         rn = list(rn) if rn is not None else [None] * len(out_features)
         for i, x in enumerate(out_features):
@@ -215,11 +216,14 @@ class DPTHead(nn.Module):
         path_2 = s.refinenet2(path_3, layer_2_rn, size=layer_1_rn.shape[2:])
         path_1 = s.refinenet1(path_2, layer_1_rn)
         final_out = s.output_conv1(path_1)
-        out_feature = final_out.clone().detach()
+        # nothing below writes final_out in place (_resize allocates its result): no copy needed
+        out_feature = final_out.detach() if kernels.DA_TAIL else final_out.clone().detach()
         final_out = _resize(final_out, {"size": (int(patch_h * 14), int(patch_w * 14))}, True)
         oc = s.output_conv2
         if _nchw3() and final_out.is_contiguous() and kernels.conv3x3_wino_ok(final_out, oc[0].weight, vs_miopen=True):
             h = kernels.conv3x3_wino(final_out, oc[0].weight, oc[0].bias, act="relu")
+            if raw_tail and isinstance(oc[3], nn.ReLU) and isinstance(oc[4], nn.Identity):
+                return oc[2](h), out_feature  # the ReLUs are the caller's
             return oc[4](oc[3](oc[2](h))), out_feature
         if (_DPT_EPI and final_out.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
                 and final_out.is_cuda and final_out.is_contiguous(memory_format=torch.channels_last)):
@@ -239,10 +243,21 @@ class DepthAnythingV2(nn.Module):
         self.depth_head = DPTHead(self.pretrained.embed_dim, features, use_bn, out_channels=out_channels,
                                   use_clstoken=use_clstoken)
 
-    def forward(self, x):
-        patch_h, patch_w = x.shape[-2] // 14, x.shape[-1] // 14
+    def forward(self, x, patches=None, raw_depth: bool = False):
+        """x: the images [B, 3, H, W]. Not in the reference: `patches` = (patch matrix of
+        kernels.da_patches, B, patch_h, patch_w) in place of x (x is then ignored); `raw_depth`: the
+        depth comes back as the [B, 1, H, W] map with its trailing ReLUs possibly still to apply
+        (kernels.depth_norm applies ReLU on load; it is idempotent)."""
+        if patches is not None:
+            pm, n_img, patch_h, patch_w = patches
+            tokens = self.pretrained.prepare_tokens_patches(pm, n_img, patch_h, patch_w)
+            is_cuda = True
+        else:
+            patch_h, patch_w = x.shape[-2] // 14, x.shape[-1] // 14
+            tokens = None
+            is_cuda = x.is_cuda
         head = self.depth_head
-        head.prepare(x.is_cuda)
+        head.prepare(is_cuda)
         n_take = len(self.intermediate_layer_idx[self.encoder])
         pending = {}
 
@@ -257,8 +272,11 @@ class DepthAnythingV2(nn.Module):
 
         with stage(None, "da_dinov2"):  # diagnostic sub-stage marks (TSPLAT_MARKS / TSPLAT_ROCTX)
             features = self.pretrained.get_intermediate_layers(x, self.intermediate_layer_idx[self.encoder],
-                                                               return_class_token=True, on_output=on_output)
+                                                               return_class_token=True, on_output=on_output,
+                                                               tokens=tokens)
         rn = [streams.join(pending[k]) if k in pending else None for k in range(n_take)]
         with stage(None, "da_dpt"):
-            depth, out_features = head(features, patch_h, patch_w, rn=rn)
+            depth, out_features = head(features, patch_h, patch_w, rn=rn, raw_tail=raw_depth)
+        if raw_depth:
+            return depth, out_features
         return F.relu(depth).squeeze(1), out_features

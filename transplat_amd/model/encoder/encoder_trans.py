@@ -176,11 +176,24 @@ class EncoderTrans(Encoder[EncoderTransCfg]):
             with bench("encoder_3_depth_anything"), torch.no_grad(), self._dense():
                 # channel order (2, 0, 1) as the reference, by slicing: a list index would be a
                 # pageable host-to-device copy, which is not allowed inside hipGraph capture
-                da_images = self.normalize_images(images)
-                da_images = torch.cat((da_images[:, :, 2:3], da_images[:, :, 0:2]), dim=2)
-                da_images = da_images.reshape(b * v, 3, h, w)
-                da_images = kernels.interpolate_bilinear_ac(da_images, (252, 252))
-                da_depth, out_feature = self.da_model(da_images)
+                dino = self.da_model.pretrained
+                # the depth tail as two launches (kernels.depth_norm) from the head's last 1x1 map
+                tail = kernels.DA_TAIL and kernels.split_mode() and images.is_cuda and images.dtype == torch.float32
+                if kernels.split_mode() and dino.patches_ok(images):
+                    # normalise + reorder + resize + unfold in one launch, straight into the patch
+                    # projection's GEMM operand
+                    g = 252 // dino.patch_size
+                    pm = kernels.da_patches(images, self.img_mean, self.img_std, (g, g), dino.patch_size)
+                    da_depth, out_feature = self.da_model(None, patches=(pm, b * v, g, g), raw_depth=tail)
+                else:
+                    da_images = self.normalize_images(images)
+                    da_images = torch.cat((da_images[:, :, 2:3], da_images[:, :, 0:2]), dim=2)
+                    da_images = da_images.reshape(b * v, 3, h, w)
+                    da_images = kernels.interpolate_bilinear_ac(da_images, (252, 252))
+                    da_depth, out_feature = self.da_model(da_images, raw_depth=tail)
+                if tail:  # ReLU, resize to (h, w), per-view min / max, (d - min) / (max - min)
+                    da_depth = kernels.depth_norm(da_depth.float().reshape(b * v, *da_depth.shape[-2:]), (h, w))
+                    return da_depth.view(b, v, 1, h, w), out_feature.float()
                 da_depth = kernels.interpolate_bilinear_ac(da_depth[None].float().contiguous(), (h, w))
                 da_depth = da_depth.view(b, v, 1, h, w).flatten(2)
                 # per-view min / max in two aminmax stages (rows of w, then the h row results): the

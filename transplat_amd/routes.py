@@ -63,7 +63,10 @@ _HIP = {
     "tsplat_layer_norm128_fwd": ("norms (HIP)", None),
     "tsplat_residual_ln_fwd": ("norms (HIP)", "fp32"),
     "tsplat_residual_ln_slabs_fwd": ("norms (HIP)", "fp32"),
+    "tsplat_residual_ln_slabs_bcast_fwd": ("norms (HIP)", "fp32"),
     "tsplat_residual_ln_bf16_fwd": ("norms (HIP)", "bf16 I/O, fp32 statistics"),
+    "tsplat_da_patches_fwd": ("Depth-Anything glue (HIP)", "fp32"),
+    "tsplat_depth_norm_fwd": ("Depth-Anything glue (HIP)", "fp32"),
     "tsplat_gaussian_adapter_fwd": ("gaussian adapter (HIP)", "fp32"),
     "tsplat_sh_rotation_fwd": ("gaussian adapter (HIP)", "fp32"),
     "tsplat_raster_fwd": ("rasterizer (HIP)", "fp32"),
@@ -71,7 +74,7 @@ _HIP = {
 }
 _ORDER = ("window attention", "transformer linears (HIP)", "GEMMs (HIP)", "3x3 convs (HIP Winograd)", "direct convs (HIP)",
           "DINOv2 attention (HIP)", "U-Net attention (HIP)", "library GEMMs (hipBLASLt)", "library convs (MIOpen)",
-          "correlation (HIP)", "norms (HIP)", "gaussian adapter (HIP)", "rasterizer (HIP)")
+          "correlation (HIP)", "norms (HIP)", "Depth-Anything glue (HIP)", "gaussian adapter (HIP)", "rasterizer (HIP)")
 _GEMMS = {"mm", "addmm", "bmm", "baddbmm", "addbmm", "_scaled_mm"}
 _CONVS = {"convolution", "_convolution", "cudnn_convolution", "miopen_convolution", "convolution_overrideable",
           "conv2d", "conv_transpose2d", "miopen_convolution_transpose"}
