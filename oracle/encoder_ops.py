@@ -3,7 +3,9 @@
 Each function has the exact signature of its gfx950 counterpart in transplat_amd/kernels.py so a
 test can run the surrounding module code on the CPU with these in place (monkeypatched), and the
 GPU tests compare the HIP ops with these on identical inputs. Pinned by tests/golden/*.npz
-(generated from the reference modules, see tests/golden/gen_golden.py).
+(generated from the reference modules, see tests/golden/gen_golden.py). The correlation ops
+(calculate_grid, uv_coarse, uv_cross, msda) also run in float64 on the widened fp32 inputs
+(dtype=torch.float64), the reference of tests/test_corr_shapes.py.
 """
 from __future__ import annotations
 
@@ -89,12 +91,16 @@ def window_attention(q, k, v, h: int, w: int, num_splits: int, with_shift: bool,
 
 
 # --------------------------------------------------------------------- correlation (C2-C9)
-def calculate_grid(intr, pose, disp, h: int, w: int):
+def calculate_grid(intr, pose, disp, h: int, w: int, dtype=None):
     """Projection grid (reference depth_predictor_trans.py:11-57): pixel (x, y) at depth 1/disp
-    of camera n lands at uv in the other camera; normalised 2u/(W-1) - 1. -> [N, D, HW, 2]."""
+    of camera n lands at uv in the other camera; normalised 2u/(W-1) - 1. -> [N, D, HW, 2].
+    dtype (torch.float64): the inputs are widened before the first operation (the inverse of the
+    intrinsics included) and everything runs in that type; None is the fp32 form."""
     n, d = disp.shape
     ys, xs = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
     pts = torch.stack([xs, ys, torch.ones_like(xs)], 0).float().reshape(3, -1)  # [3, HW]
+    if dtype is not None:
+        intr, pose, disp, pts = intr.to(dtype), pose.to(dtype), disp.to(dtype), pts.to(dtype)
     depth = 1.0 / disp  # [N, D]
     cam = torch.inverse(intr) @ pts  # [N, 3, HW]
     rot = pose[:, :3, :3] @ cam  # [N, 3, HW]
@@ -128,7 +134,7 @@ def bilinear_zero_corners(img, x, y):
     hh, ww, c = img.shape
     x0 = torch.floor(x)
     y0 = torch.floor(y)
-    out = torch.zeros((*x.shape, c))
+    out = torch.zeros((*x.shape, c), dtype=img.dtype)
     for dy in (0, 1):
         for dx in (0, 1):
             xi = x0 + dx
@@ -138,71 +144,94 @@ def bilinear_zero_corners(img, x, y):
             xc = xi.clamp(0, ww - 1).long()
             yc = yi.clamp(0, hh - 1).long()
             val = img[yc, xc]
-            out = out + torch.where(ok[..., None], wgt[..., None] * val, torch.zeros(()))
+            out = out + torch.where(ok[..., None], wgt[..., None] * val, torch.zeros((), dtype=img.dtype))
     return out
 
 
-def _ref3d(intr, pose, disp, h, w, b):
+def _sampler(dtype):
+    """The bilinear sampler of a correlation op: grid_sample in the fp32 form, the explicit corners
+    in a widened one."""
+    return bilinear_zero if dtype is None else bilinear_zero_corners
+
+
+def _ref3d(intr, pose, disp, h, w, b, dtype=None):
     """ref_3d of UVTransformerEncoder (reference utils/encoder.py:57-59) in (b v) order,
     normalised to [0, 1] as grid / 2 + 0.5 -> [B*2, HW, D, 2]."""
-    grid = calculate_grid(intr, pose, disp, h, w)  # [(v b), D, HW, 2]
+    grid = calculate_grid(intr, pose, disp, h, w, dtype)  # [(v b), D, HW, 2]
     d = disp.shape[1]
     r = grid.reshape(2, b, d, h * w, 2).permute(1, 0, 3, 2, 4).reshape(b * 2, h * w, d, 2)
     return r / 2 + 0.5
 
 
-def uv_coarse(feat, intr, pose, disp, h: int, w: int):
+def uv_coarse(feat, intr, pose, disp, h: int, w: int, dtype=None):
     """UVCoarseAttention core (reference attention.py:468-551 with calculate_grid): for query
     (b, v) pixel p and depth d, sample the OTHER view's feature at ref_3d and dot with the own
-    feature, / sqrt(C).  feat [B, 2, HW, C] -> [B*2, HW, D]."""
+    feature, / sqrt(C).  feat [B, 2, HW, C] -> [B*2, HW, D].
+    dtype=torch.float64: the same operation on the widened fp32 inputs, sampled with the explicit
+    four corners (no grid_sample), returned in float64; None is the fp32 form."""
     b, _, hw, c = feat.shape
-    ref = _ref3d(intr, pose, disp, h, w, b)
+    if dtype is not None:
+        feat = feat.to(dtype)
+    ref = _ref3d(intr, pose, disp, h, w, b, dtype)
     d = disp.shape[1]
-    out = torch.empty((b * 2, hw, d))
+    out = torch.empty((b * 2, hw, d), dtype=dtype or torch.float32)
+    sample = _sampler(dtype)
     for bi in range(b):
         for vi in range(2):
             other = feat[bi, 1 - vi].reshape(h, w, c)
             r = ref[bi * 2 + vi]
             for q0 in range(0, hw, 512):
                 sl = slice(q0, q0 + 512)
-                s = bilinear_zero(other, r[sl, :, 0] * w - 0.5, r[sl, :, 1] * h - 0.5)  # [q, D, C]
+                s = sample(other, r[sl, :, 0] * w - 0.5, r[sl, :, 1] * h - 0.5)  # [q, D, C]
                 out[bi * 2 + vi, sl] = (s * feat[bi, vi][sl, None, :]).sum(-1) / math.sqrt(c)
     return out
 
 
-def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
+def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int, dtype=None):
     """UVCrossAttention core (reference attention.py:329-416): per (query, depth) 4 points at
     ref_3d + offset / (W, H), softmax weights over the points, sampled from the OTHER view's
     value_proj output, then mean over channels of (sample * own key).
-    value, key [B, 2, HW, C]; offsets [B*2, HW, D*P*2]; logits [B*2, HW, D*P] -> [B*2, HW, D]."""
+    value, key [B, 2, HW, C]; offsets [B*2, HW, D*P*2]; logits [B*2, HW, D*P] -> [B*2, HW, D].
+    dtype=torch.float64: the same operation on the widened fp32 inputs (softmax included), sampled
+    with the explicit four corners, returned in float64; None is the fp32 form."""
     b, _, hw, c = value.shape
     d = disp.shape[1]
     p = logits.shape[-1] // d
-    ref = _ref3d(intr, pose, disp, h, w, b)
+    if dtype is not None:
+        value, key, offsets, logits = value.to(dtype), key.to(dtype), offsets.to(dtype), logits.to(dtype)
+    ref = _ref3d(intr, pose, disp, h, w, b, dtype)
     off = offsets.reshape(b * 2, hw, d, p, 2)
     wts = torch.softmax(logits.reshape(b * 2, hw, d, p), -1)
-    out = torch.empty((b * 2, hw, d))
+    out = torch.empty((b * 2, hw, d), dtype=dtype or torch.float32)
+    sample = _sampler(dtype)
+    # [chunk, D, P, C] samples at a time: 256 queries in fp32; the corner form holds a few such
+    # arrays at once, so its chunk keeps each near 64 MB
+    chunk = 256 if dtype is None else max(1, 65536 // (d * p))
     for bi in range(b):
         for vi in range(2):
             n = bi * 2 + vi
             other = value[bi, 1 - vi].reshape(h, w, c)
-            for q0 in range(0, hw, 256):  # chunked: [256, D, P, C] samples at a time
-                sl = slice(q0, q0 + 256)
-                loc = ref[n][sl, :, None, :] + off[n][sl] / torch.tensor([w, h], dtype=torch.float32)
-                s = bilinear_zero(other, loc[..., 0] * w - 0.5, loc[..., 1] * h - 0.5)  # [q, D, P, C]
+            for q0 in range(0, hw, chunk):
+                sl = slice(q0, q0 + chunk)
+                loc = ref[n][sl, :, None, :] + off[n][sl] / torch.tensor([w, h], dtype=dtype or torch.float32)
+                s = sample(other, loc[..., 0] * w - 0.5, loc[..., 1] * h - 0.5)  # [q, D, P, C]
                 s = (s * wts[n][sl][..., None]).sum(2)
                 out[n, sl] = (s * key[bi, vi][sl, None, :]).mean(-1)
     return out
 
 
-def msda(value, loc, weights, h: int, w: int):
+def msda(value, loc, weights, h: int, w: int, dtype=None):
     """Single-level single-head MSDA (mmcv ms_deform_attn_forward semantics): value [N, HW, C],
-    loc [N, Q, P, 2] in [0, 1], weights [N, Q, P] -> [N, Q, C]."""
+    loc [N, Q, P, 2] in [0, 1], weights [N, Q, P] -> [N, Q, C].
+    dtype=torch.float64: on the widened inputs with the explicit four corners; None: fp32."""
     n, hw, c = value.shape
+    if dtype is not None:
+        value, loc, weights = value.to(dtype), loc.to(dtype), weights.to(dtype)
+    sample = _sampler(dtype)
     out = []
     for i in range(n):
         img = value[i].reshape(h, w, c)
-        s = bilinear_zero(img, loc[i, ..., 0] * w - 0.5, loc[i, ..., 1] * h - 0.5)  # [Q, P, C]
+        s = sample(img, loc[i, ..., 0] * w - 0.5, loc[i, ..., 1] * h - 0.5)  # [Q, P, C]
         out.append((s * weights[i][..., None]).sum(1))
     return torch.stack(out)
 

@@ -22,15 +22,17 @@ from transplat_amd import synthetic as S  # noqa: E402
 GOLD = Path(__file__).resolve().parent / "golden"
 
 
-def _cams(b, hw):
-    """(v b)-ordered pixel intrinsics, relative poses and 128 disparities as the reference's
-    prepare_feat_proj_data_lists builds them for the synthetic context views."""
+def _cams(b, hw, depths=128):
+    """(v b)-ordered pixel intrinsics, relative poses and `depths` disparities as the reference's
+    prepare_feat_proj_data_lists builds them for the synthetic context views; hw: one side of a
+    square map, or (h, w) for the native intrinsics of a non-square one."""
     from transplat_amd.model.encoder.matching.depth_predictor_trans import prepare_feat_proj_data_lists
 
-    ctx = S.make_batch(b, image_shape=(hw, hw))["context"]
-    feats = torch.zeros((b, 2, 1, hw, hw))
+    h, w = hw if isinstance(hw, tuple) else (hw, hw)
+    ctx = S.make_batch(b, image_shape=(h, w))["context"]
+    feats = torch.zeros((b, 2, 1, h, w))
     _, intr, poses, disp = prepare_feat_proj_data_lists(feats, ctx["intrinsics"], ctx["extrinsics"], ctx["near"],
-                                                        ctx["far"], 128)
+                                                        ctx["far"], depths)
     return intr, poses[0], disp.flatten(1)
 
 
@@ -135,11 +137,11 @@ def test_uv_coarse_kernel(device, monkeypatch, hw, b, variant):
     assert (out - ref).abs().max().item() < 1e-4
 
 
-def _rotated_cams(b, hw, seed, depth_slice):
+def _rotated_cams(b, hw, seed, depth_slice=lambda d: d, depths=128):
     """_cams with the relative pose turned by a random rotation of up to ~0.35 rad and shifted, so
     epipolar segments run diagonally, leave the image and re-enter the sampling window part-way,
     and the depth count is changed (S = 1, 3 slices of 64 samples)."""
-    intr, pose, disp = _cams(b, hw)
+    intr, pose, disp = _cams(b, hw, depths)
     g = torch.Generator().manual_seed(seed)
     pose = pose.clone()
     for i in range(pose.shape[0]):
