@@ -578,7 +578,7 @@ int tsplat_conv3x3_wino_bf16x3_ex_fwd(const float* const* srcs, const int32_t* c
  * unet.py at model_channels = 32), where the Winograd form's per-block prologue / epilogue dominate.
  * w_packed = the direct kernels' split-bf16 A operand [ceil(c_out / 32)][9][ceil(c_in / 16)][hi, lo]
  * [64 lanes][8] (as tsplat_conv2d_bf16x3_fwd). Requires width % 4 == 0, 16-B aligned sources,
- * c_out <= 64, c_in <= 128 (else TSPLAT_EINVAL); tsplat_conv3x3_few_form() returns 0 for shapes it
+ * y and residuals, c_out <= 64, c_in <= 128 (else TSPLAT_EINVAL); tsplat_conv3x3_few_form() returns 0 for shapes it
  * does not take and otherwise its launch form (10 * rows per block + 32-channel blocks per workgroup). */
 int32_t tsplat_conv3x3_few_form(int32_t batch, int32_t c_in, int32_t height, int32_t width, int32_t c_out);
 int tsplat_conv3x3_few_bf16x3_fwd(const float* const* srcs, const int32_t* chans, int32_t n_src,

@@ -836,7 +836,7 @@ def test_conv3x3_few_kernel(device, n, chans, co, h, w, act, relu_in, nres):
 @pytest.mark.gpu
 def test_conv3x3_few_route_matches_kernel(device):
     """kernels.conv3x3_wino in the bf16x3 mode takes the direct few-channel kernel for a refine-U-Net
-    shape (same bits as the C-ABI call above would give), and the Winograd one with TSPLAT_CONV_FEW off;
+    shape (same bits as the C-ABI call above would give), and the Winograd one with kernels._FEW off;
     both within the bf16x3 bound of float64."""
     from transplat_amd import kernels as K
 
@@ -855,6 +855,43 @@ def test_conv3x3_few_route_matches_kernel(device):
     s = ref.abs().max().item()
     assert (y_few.double() - ref).abs().max().item() / s < 2e-5
     assert (y_w.double() - ref).abs().max().item() / s < 2e-5
+
+
+@pytest.mark.gpu
+def test_conv3x3_few_route_leaves_misaligned_residual_to_winograd(device):
+    """The few-channel kernel moves the residuals as float4: kernels.conv3x3_wino sends a residual
+    that is a 4-byte-offset view (same values) to the Winograd kernel instead of raising, with the
+    bits the Winograd route gives for the aligned residual; the aligned one takes the few-channel
+    kernel (routes.record names the entry points' categories)."""
+    from transplat_amd import kernels as K
+    from transplat_amd import routes
+
+    shape = (2, 32, 256, 256)
+    x = seeded(shape, 174).to(device)
+    wt = (seeded((32, 32, 3, 3), 175) / 17.0).to(device)
+    b = seeded((32,), 176).to(device)
+    res = seeded(shape, 177).to(device)
+    buf = torch.empty(res.numel() + 1, device=device)
+    off = buf[1:].view(shape)
+    off.copy_(res)
+    assert res.data_ptr() % 16 == 0 and off.data_ptr() % 16 == 4 and off.is_contiguous()
+    few, wino = ("direct convs (HIP)", "bf16x3"), ("3x3 convs (HIP Winograd)", "bf16x3")
+    with K.dense_precision("bf16x3"):
+        with routes.record() as r_al:
+            K.conv3x3_wino(x, wt, b, residual=res)
+        with routes.record() as r_off:
+            y_off = K.conv3x3_wino(x, wt, b, residual=off)
+        with routes.record() as r_off2:
+            y_off2 = K.conv3x3_wino(x, wt, b, residual=res, residual2=off)
+        K._FEW = False
+        try:
+            y_w = K.conv3x3_wino(x, wt, b, residual=res)
+            y_w2 = K.conv3x3_wino(x, wt, b, residual=res, residual2=res)
+        finally:
+            K._FEW = True
+    assert r_al.calls == {few: 1}
+    assert r_off.calls == {wino: 1} and r_off2.calls == {wino: 1}
+    assert torch.equal(y_off, y_w) and torch.equal(y_off2, y_w2)
 
 
 @pytest.mark.gpu

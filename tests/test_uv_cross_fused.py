@@ -104,3 +104,26 @@ def test_uv_cross_fused_rejects_bad_arguments():
     assert lib.tsplat_uv_cross_pack_fwd(p, p, 1, 4, 4, 64, None) == einval
     assert lib.tsplat_uv_cross_pack_bytes(1, 64, 64) == 2 * 4096 * 512
     assert lib.tsplat_uv_cross_pack_bytes(1, 6, 10) == 2 * 64 * 512
+
+
+def test_conv3x3_few_rejects_misaligned_output_and_residuals():
+    """tsplat_conv3x3_few_bf16x3_fwd moves y, residual and residual2 as float4: a pointer that is not
+    16-byte aligned is TSPLAT_EINVAL before anything is launched (CPU host), on a shape the kernel
+    takes (2 x 32 -> 32 at 256^2, form 41) with every other argument valid."""
+    from transplat_amd import _lib
+
+    lib = _lib.load()
+    buf = (ctypes.c_float * 64)()
+    p = (ctypes.cast(buf, ctypes.c_void_p).value + 15) // 16 * 16  # never dereferenced: every call is rejected
+    srcs = ctypes.cast((ctypes.c_void_p * 1)(p), ctypes.c_void_p)
+    chans = ctypes.cast((ctypes.c_int32 * 1)(32), ctypes.c_void_p)
+    assert lib.tsplat_conv3x3_few_form(2, 32, 256, 256, 32) == 41
+
+    def few(y=p, residual=None, residual2=None):
+        return lib.tsplat_conv3x3_few_bf16x3_fwd(srcs, chans, 1, p, p, residual, residual2, y, 2, 256, 256, 32, 0, 0,
+                                                 None)
+
+    for off in (4, 8, 12):
+        assert few(y=p + off) == -1
+        assert few(residual=p + off) == -1
+        assert few(residual=p, residual2=p + off) == -1

@@ -39,7 +39,7 @@ K.conv2d_direct = orig
 rows = []
 s = torch.cuda.Stream()
 prec = K.dense_precision(dense) if dense in ("bf16x3",) else torch.no_grad()
-prec.__enter__()  # the step's dense mode (bf16x3: the split-bf16 direct kernel unless TSPLAT_CONV_X3=0)
+prec.__enter__()  # the step's dense mode (bf16x3: the split-bf16 direct kernel)
 for key, a in args.items():
     with torch.cuda.stream(s):
         for _ in range(3):

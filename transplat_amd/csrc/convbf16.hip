@@ -27,8 +27,6 @@
 // current chunk's 9 NT MFMAs. Epilogue: bias + act in fp32 -> bf16 tile [co][pixel] in LDS -> 16-B
 // row stores.
 #include <math.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "common.h"
 #include "mfma.h"
@@ -51,8 +49,7 @@ struct Args {
     int up;                              // 1: sources are [h / 2, w_ / 2], nearest-upsampled on load
     int tiles_x, tiles_y;
     int wg_target;  // workgroups per launch (all co blocks): a few per CU
-    int occ4;       // bf16 sources: the occupancy-4 register allocation (default; C3 1057 vs 1042 views/s)
-    int big;        // 3x3 with c_in * c_out >= TSPLAT_CONVBF16_BIG (default 96 * 96) and >= 192 workgroups:
+    int big;        // 3x3 with c_in * c_out >= 96 * 96 and >= 192 workgroups:
                     // the register-blocked form (C3 1019 -> 1062 views/s, profiles/r3/convbf16)
 };
 
@@ -188,8 +185,8 @@ __device__ __forceinline__ void transpose8(const uint4 (&in)[8], uint4 (&out)[8]
     }
 }
 
-// OCC: waves per SIMD the register allocation targets (2: no spills; 4, the default for bf16
-// sources: more workgroups per CU to hide the staging loads' latency; same-box C3 1057 vs 1042
+// OCC: waves per SIMD the register allocation targets (2: no spills; 4, for bf16 sources in the
+// small form: more workgroups per CU to hide the staging loads' latency; same-box C3 1057 vs 1042
 // views/s, profiles/r3/ab_r3d)
 // SRC: 0 bf16 sources, 1 fp32 sources, 2 ragged / mixed (load_block_ragged)
 // WCT x NT: 32-channel co tiles x 32-pixel column tiles per wave. (1, 2) = the small form, LDS
@@ -384,10 +381,9 @@ static void launch_tw(const Args& a, int src_mode, hipStream_t stream) {
         hipLaunchKernelGGL((conv_bf16_kernel<TW, CT, KS, 2, 2, WCT, NT>), grid, dim3(kThreads), 0, stream, b);
     else if (src_mode == 1)
         hipLaunchKernelGGL((conv_bf16_kernel<TW, CT, KS, 1, 2, WCT, NT>), grid, dim3(kThreads), 0, stream, b);
-    else if (a.occ4 && WCT == 1)
-        hipLaunchKernelGGL((conv_bf16_kernel<TW, CT, KS, 0, 4, WCT, NT>), grid, dim3(kThreads), 0, stream, b);
     else
-        hipLaunchKernelGGL((conv_bf16_kernel<TW, CT, KS, 0, 2, WCT, NT>), grid, dim3(kThreads), 0, stream, b);
+        hipLaunchKernelGGL((conv_bf16_kernel<TW, CT, KS, 0, WCT == 1 ? 4 : 2, WCT, NT>), grid, dim3(kThreads), 0,
+                           stream, b);
 }
 
 template <int CT, int KS>
@@ -447,18 +443,11 @@ extern "C" int tsplat_conv2d_bf16_fwd(const void* const* srcs, const int32_t* sr
     a.co = c_out;
     a.act = act;
     a.up = upsample;
-    {
-        const char* e = getenv("TSPLAT_CONVBF16_WGS");  // A/B knob: workgroups per launch
-        const char* o = getenv("TSPLAT_CONVBF16_OCC");  // "2": the spill-free allocation (A/B knob)
-        a.occ4 = !(o && !strcmp(o, "2"));
-        a.wg_target = e ? std::max(1, atoi(e)) : (a.occ4 ? 256 * 4 : 256 * 2);
-        const char* bg = getenv("TSPLAT_CONVBF16_BIG");  // A/B knob: c_in * c_out threshold, 0 = off
-        const long big_min = bg ? atol(bg) : 96L * 96L;
-        // ... and only with enough 512-pixel tiles to fill the CUs (16 x 128 -> 128 at 32^2: 64
-        // workgroups, 51 vs 25 us in the small form; at 64^2: 256, 79 vs 97 us for 256 -> 128)
-        const long wgs = ((long)batch * height * width + 511) / 512 * ((c_out + 63) / 64);
-        a.big = big_min > 0 && (long)ci * c_out >= big_min && wgs >= 192;
-    }
+    a.wg_target = 256 * 4;
+    // ... and only with enough 512-pixel tiles to fill the CUs (16 x 128 -> 128 at 32^2: 64
+    // workgroups, 51 vs 25 us in the small form; at 64^2: 256, 79 vs 97 us for 256 -> 128)
+    const long wgs = ((long)batch * height * width + 511) / 512 * ((c_out + 63) / 64);
+    a.big = (long)ci * c_out >= 96L * 96L && wgs >= 192;
     hipStream_t stream = (hipStream_t)stream_;
     const int f32 = ragged ? 2 : src_f32[0];  // loader mode
     if (ksize == 3) {

@@ -21,8 +21,6 @@
 // product, fp32 accumulation). Epilogue: + bias, activation, + residual(s), NCHW stores (32
 // consecutive pixels per register and half-wave). ReLU-on-load and multi-source (concatenated) input
 // as the Winograd kernel has them.
-#include <stdlib.h>
-
 #include "common.h"
 #include "mfma.h"
 #include "prof.h"
@@ -50,7 +48,6 @@ struct Args {
     int act;             // 0 none, 1 ReLU, 2 GELU (erf)
     int relu_in;
     int rb, cb;          // row / column blocks per image
-    int abl;             // diagnostics only (TSPLAT_FEW_ABL): 1 no input loads, 2 no MFMAs, 4 no stores
 };
 
 // plane of input channel c (concatenated sources), or null past the last channel; the source loop is
@@ -75,7 +72,7 @@ __device__ __forceinline__ const float* plane(const Args& a, int img, int c) {
 // uint4), loaded after the region is staged (the staging registers are dead then; the co-resident
 // workgroup covers their latency), so the LDS holds just the image and two workgroups share a CU.
 // (Measured against A staged in LDS with one workgroup per CU: 20.9 vs 24.1 us for 2 x 32 -> 32 at
-// 256^2, tools/few_sweep.sh, profiles/r6/few_sweep.log.)
+// 256^2, profiles/r6/few_sweep.log.)
 template <int TR, int CB>
 __global__ void __launch_bounds__(256, 2) conv_kernel(Args a) {
     constexpr int R = TR + 2;                 // region rows
@@ -125,7 +122,7 @@ __global__ void __launch_bounds__(256, 2) conv_kernel(Args a) {
             const size_t po = (size_t)min(max(y, 0), a.h - 1) * a.w + min(max(x, 0), a.w - 4);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const bool ok = in && c0 + j < a.ci && !(a.abl & 1);
+                const bool ok = in && c0 + j < a.ci;
                 const float* p = sPlane[min(c0 + j, kMaxCi - 1)] + po;
                 // global address space: a pointer read from LDS would otherwise be a flat load, which
                 // also counts against the LDS counter
@@ -174,7 +171,6 @@ __global__ void __launch_bounds__(256, 2) conv_kernel(Args a) {
         }
         __syncthreads();
         // 18 k-steps (tap, 16-channel chunk), unrolled: A from registers, B from LDS
-        if (a.abl & 2) continue;
 #pragma unroll
         for (int ks = 0; ks < 18; ++ks) {
             const int tap = ks >> 1, gl = ks & 1;
@@ -198,13 +194,9 @@ __global__ void __launch_bounds__(256, 2) conv_kernel(Args a) {
     // epilogue: register r of lane (n, h) = output channel 8 (r >> 2) + 4 h + (r & 3) of the wave's
     // block, pixel n of the segment
     const size_t hw = (size_t)a.h * a.w;
-    if (a.abl & 4) {
-        if (acc[0][0] == 12345.0f) a.y[0] = acc[UPW - 1][15];  // keep the accumulators live
-        return;
-    }
     // output tile through LDS (the input image is dead after the last MFMA): sOut[co][row][64 px],
     // then 16-B stores of whole 64-pixel rows (dword stores of 32-pixel runs, 64 per wave, ran at
-    // ~1 TB/s: TSPLAT_FEW_ABL=4 measured the store phase at half the kernel)
+    // ~1 TB/s: with the stores ablated the store phase measured half the kernel)
     constexpr int CO = 32 * CB;
     static_assert(CO * TR * kCols * 4 <= 2 * HL * 2, "output tile fits the input image's LDS");
     float* sOut = reinterpret_cast<float*>(sIn);
@@ -258,10 +250,6 @@ extern "C" int32_t tsplat_conv3x3_few_form(int32_t n, int32_t ci, int32_t h, int
     if (n <= 0 || ci <= 0 || h <= 0 || w <= 0 || co <= 0 || w % 4 || co > 64 || ci > convfew::kMaxCi) return 0;
     const long cbk = (w + convfew::kCols - 1) / convfew::kCols;
     if (co > 32) return 22;
-    if (const char* e = getenv("TSPLAT_FEW_TR")) {  // A/B knob: 4 or 2 rows per block
-        const int tr = atoi(e);
-        if (tr == 4 || tr == 2) return tr * 10 + 1;
-    }
     return (long)n * ((h + 3) / 4) * cbk >= 256 ? 41 : 21;
 }
 
@@ -271,6 +259,9 @@ extern "C" int tsplat_conv3x3_few_bf16x3_fwd(const float* const* srcs, const int
                                              int32_t co, int32_t act, int32_t relu_in, void* stream_) {
     using namespace tsplat::convfew;
     if (!srcs || !chans || nsrc <= 0 || nsrc > kMaxSrc || !packed || !y || act < 0 || act > 2) return TSPLAT_EINVAL;
+    // the kernel moves y and the residuals as float4, like the sources below
+    for (const float* p : {(const float*)y, residual, residual2})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return TSPLAT_EINVAL;
     Args a;
     int ci = 0;
     for (int q = 0; q < kMaxSrc; ++q) {
@@ -297,7 +288,6 @@ extern "C" int tsplat_conv3x3_few_bf16x3_fwd(const float* const* srcs, const int
     a.cot = (co + 31) / 32;
     a.act = act;
     a.relu_in = relu_in != 0;
-    a.abl = getenv("TSPLAT_FEW_ABL") ? atoi(getenv("TSPLAT_FEW_ABL")) : 0;
     const int tr = form / 10, cb = form % 10;
     a.rb = (h + tr - 1) / tr;
     a.cb = (w + kCols - 1) / kCols;

@@ -137,12 +137,14 @@ uv_coarse_kernel(Geo g, const float* __restrict__ feat, const float* __restrict_
 constexpr int kDedupWaves = 4;
 constexpr int kDedupMaxS = 4;  // D <= 256
 
-// WPE: waves per SIMD the register budget is sized for (5: 82 VGPRs, 1,280 of the production
-// launch's 2,048 workgroups resident; 6: 80 VGPRs with 2 spilled, 1,536 resident)
+// WPE: waves per SIMD the register budget is sized for (5: 1,280 of the production launch's 2,048
+// workgroups resident; 6: 1,536). Across the phases a sample keeps its cell's index, 4 in-map bits and the
+// two bilinear fractions, not four corner indices and weights: D = 128 takes 74 VGPRs at either budget,
+// D <= 192 78, without spills; only D <= 256 at 6 spills (20 bytes per lane)
 template <int S, int WPE>
 __global__ void __launch_bounds__(kDedupWaves * 64, WPE)
 uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const float* __restrict__ cams,
-                       const float* __restrict__ disp, float* __restrict__ out, int diag) {
+                       const float* __restrict__ disp, float* __restrict__ out) {
     extern __shared__ unsigned smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = blockIdx.y;
@@ -175,8 +177,9 @@ uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const floa
     // 1. samples -> bilinear corners (mmcv zero padding), marked in the bitmap. A corner that the
     //    previous depth sample (lane - 1, or lane 63 of the previous slice) also touches is not
     //    re-marked: consecutive samples share most corners, and same-word LDS atomics serialise.
-    int cidx[S][4];
-    float cw[S][4];
+    int cbase[S];       // y0 * W + x0 of the sample's cell (its corners: + W per row, + 1 per column)
+    unsigned cin = 0u;  // 4 bits per sample: which corners are inside the map
+    float fr[S][2];     // (ly, lx): the corner weights are formed from them where they are used
     const float fw = (float)g.W, fh = (float)g.H;
     float ray[3];
     pixel_ray(c, (float)(pc % g.W), (float)(pc / g.W), ray);
@@ -184,11 +187,9 @@ uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const floa
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const int d = lane + 64 * s;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            cidx[s][k] = -1;
-            cw[s][k] = 0.f;
-        }
+        cbase[s] = 0;
+        unsigned m = 0u;
+        fr[s][0] = fr[s][1] = 0.f;
         int y0 = 0, x0 = 0, cell = -1;
         if (active && d < g.D) {
             float xim, yim;
@@ -198,11 +199,13 @@ uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const floa
                 y0 = (int)fy;
                 x0 = (int)fx;
                 const int y1 = y0 + 1, x1 = x0 + 1;
-                const float ly = yim - fy, lx = xim - fx, hy = 1.0f - ly, hx = 1.0f - lx;
-                if (y0 >= 0 && x0 >= 0) { cidx[s][0] = y0 * g.W + x0; cw[s][0] = hy * hx; }
-                if (y0 >= 0 && x1 <= g.W - 1) { cidx[s][1] = y0 * g.W + x1; cw[s][1] = hy * lx; }
-                if (y1 <= g.H - 1 && x0 >= 0) { cidx[s][2] = y1 * g.W + x0; cw[s][2] = ly * hx; }
-                if (y1 <= g.H - 1 && x1 <= g.W - 1) { cidx[s][3] = y1 * g.W + x1; cw[s][3] = ly * lx; }
+                fr[s][0] = yim - fy;
+                fr[s][1] = xim - fx;
+                cbase[s] = y0 * g.W + x0;
+                if (y0 >= 0 && x0 >= 0) m |= 1u;
+                if (y0 >= 0 && x1 <= g.W - 1) m |= 2u;
+                if (y1 <= g.H - 1 && x0 >= 0) m |= 4u;
+                if (y1 <= g.H - 1 && x1 <= g.W - 1) m |= 8u;
                 cell = (y0 + 1) * (g.W + 2) + (x0 + 1);  // y0, x0 >= -1
             }
         }
@@ -214,15 +217,15 @@ uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const floa
         const int py0 = pcell >= 0 ? pcell / (g.W + 2) - 1 : -100, px0 = pcell >= 0 ? pcell % (g.W + 2) - 1 : -100;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int ci = cidx[s][k];
-            if (ci < 0) continue;
+            if (!((m >> k) & 1u)) continue;
+            const int ci = cbase[s] + (k >> 1) * g.W + (k & 1);
             const int yy = y0 + (k >> 1), xx = x0 + (k & 1);
             const bool seen = yy >= py0 && yy <= py0 + 1 && xx >= px0 && xx <= px0 + 1;
             if (!seen) atomicOr(&bm[ci >> 5], 1u << (ci & 31));
         }
+        cin |= m << (4 * s);
     }
     __syncthreads();
-    if (diag == 1) { if (active) out[((size_t)n * HW + p) * g.D + lane] = (float)bm[lane] + key[0].x; return; }
 
     // 2. rank the distinct corners. Lane l holds word wb + l; the non-empty words are visited two
     //    at a time (a uniform loop over the ballot of non-empty words): half-wave h takes the h-th
@@ -252,7 +255,6 @@ uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const floa
         }
     }
     __syncthreads();
-    if (diag == 2) { if (active) out[((size_t)n * HW + p) * g.D + lane] = (float)list[lane] + key[0].x; return; }
 
     // 3. one dot per distinct corner: 8 lanes per corner (each load instruction covers a full
     //    128-B line of 8 rows), 8 corners per pass, the next pass's rows in flight
@@ -290,7 +292,6 @@ uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const floa
         }
     }
     __syncthreads();
-    if (diag == 3) { if (active) out[((size_t)n * HW + p) * g.D + lane] = dots[lane]; return; }
     if (!active) return;
 
     // 4. each sample = its corners' weighted dots (rank = word prefix + popcount below the bit)
@@ -301,13 +302,15 @@ uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const floa
         const int d = lane + 64 * s;
         if (d >= g.D) continue;
         float val = 0.f;
+        const float ly = fr[s][0], lx = fr[s][1], hy = 1.0f - ly, hx = 1.0f - lx;
+        const float cw[4] = {hy * hx, hy * lx, ly * hx, ly * lx};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int ci = cidx[s][k];
-            if (ci < 0) continue;
+            if (!((cin >> (4 * s + k)) & 1u)) continue;
+            const int ci = cbase[s] + (k >> 1) * g.W + (k & 1);
             const unsigned wd = bm[ci >> 5];
             const int rank = (int)pre[ci >> 5] + __popc(wd & ((1u << (ci & 31)) - 1u));
-            val += cw[s][k] * dots[rank];
+            val += cw[k] * dots[rank];
         }
         o[d] = val * inv_sqrt_c;
     }
@@ -830,12 +833,10 @@ extern "C" int tsplat_uv_coarse_fwd(const float* feat, const float* cams, const 
     const size_t lds = (size_t)kDedupWaves * (2 * nw + 8 * depths) * sizeof(unsigned);
     const int S = (depths + 63) / 64;
     TSPLAT_PROF_BEGIN(prof::kUvCoarse, stream);
-    const char* denv = getenv("TSPLAT_CORR_DIAG");  // diagnostic builds: stop after phase 1 / 2 / 3
-    const int diag = denv ? atoi(denv) : 0;
     const char* env = getenv("TSPLAT_UV_COARSE_DIRECT");  // A/B switch: the sample-then-dot kernel
     const char* benv = getenv("TSPLAT_UV_COARSE_BITMAP");  // A/B switch: the round-2 bitmap dedup kernel
     const size_t run_lds = (size_t)kRunWaves * run_lds_words(depths) * sizeof(int);
-    if (S <= kDedupMaxS && run_lds <= 64 * 1024 && !(env && env[0] == '1') && !(benv && benv[0] == '1') && !diag) {
+    if (S <= kDedupMaxS && run_lds <= 64 * 1024 && !(env && env[0] == '1') && !(benv && benv[0] == '1')) {
         const dim3 grid(ceil_div(hw, kRunWaves), 2 * batch), block(kRunWaves * 64);
         const char* renv = getenv("TSPLAT_CORR_RUN_WPE");
         const bool w8 = !renv || atoi(renv) != 6;
@@ -863,10 +864,10 @@ extern "C" int tsplat_uv_coarse_fwd(const float* feat, const float* cams, const 
     do {                                                                                                         \
         if (w6)                                                                                                  \
             hipLaunchKernelGGL((uv_coarse_dedup_kernel<SS, 6>), grid, block, lds, stream, g, nw, feat, cams, disp, \
-                               out, diag);                                                                       \
+                               out);                                                                             \
         else                                                                                                     \
             hipLaunchKernelGGL((uv_coarse_dedup_kernel<SS, 5>), grid, block, lds, stream, g, nw, feat, cams, disp, \
-                               out, diag);                                                                       \
+                               out);                                                                             \
     } while (0)
         switch (S) {
             case 1: TSPLAT_UVC(1); break;

@@ -527,9 +527,8 @@ static int launch_linear(tsplat::linear::Args a, void* stream_) {
     const bool tall = (long long)((M + 63) / 64) * (N / kBN) >= 256;
     const dim3 g64((M + 63) / 64, N / kBN), g32((M + 31) / 32, N / kBN);
     // 128-row blocks (each W fragment feeds two accumulators: half the W staging and split work per
-    // row) where they still make >= 512 workgroups (C3's 65,536-row layers); TSPLAT_LIN128=0: off
-    static const bool lin128 = !getenv("TSPLAT_LIN128") || atoi(getenv("TSPLAT_LIN128")) != 0;
-    const bool tall128 = lin128 && (long long)((M + 127) / 128) * (N / kBN) >= 512;
+    // row) where they still make >= 512 workgroups (C3's 65,536-row layers)
+    const bool tall128 = (long long)((M + 127) / 128) * (N / kBN) >= 512;
     if ((flags & kBf16x3) && tall128) {
         hipLaunchKernelGGL((linear_f32_kernel<128, false, true>), dim3((M + 127) / 128, N / kBN), dim3(kThreads), 0,
                            stream, a);

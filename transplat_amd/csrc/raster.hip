@@ -1079,10 +1079,8 @@ static int raster_run(const tsplat_raster_desc* d, const float* means, const flo
         p.diag = e ? atoi(e) : 0;
         const char* s = getenv("TSPLAT_RASTER_SORT");
         p.count_sort = !(s && !strcmp(s, "bitonic"));
-        // rotation per view: about T / 3 tiles, rounded to whole rows (TSPLAT_RASTER_ROT=0: off)
-        const char* r = getenv("TSPLAT_RASTER_ROT");
-        const int rows = (p.tiles_y + 1) / 3;
-        p.view_rot = (r && !strcmp(r, "0")) ? 0 : rows * p.tiles_x;
+        // rotation per view: about T / 3 tiles, rounded to whole rows
+        p.view_rot = (p.tiles_y + 1) / 3 * p.tiles_x;
     }
     if (3 * p.M > kMaxShFloats || p.vps > 32) return TSPLAT_EINVAL;
     // scatter keeps 3 T uint32 of per-tile counters in LDS: up to gfx950's 160 KB per workgroup

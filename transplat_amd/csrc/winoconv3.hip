@@ -831,10 +831,8 @@ static int pick_form(int n, int th, int tw, int co) {
     // 256^2 refine U-Net levels, profiles/r5/late/wino3_forms_p5.log: 32 -> 32 at 256^2 141.6 vs 164.7
     // us, 64 -> 32 217.8 vs 250.0, 32 -> 32 at 128^2 39.0 vs 44.1; at b = 1's 1024 blocks it loses,
     // 25.2 vs 23.8); the launcher falls back to form 1 where it does not apply
-    static const bool p5 = !getenv("TSPLAT_WINO3_P5") || atoi(getenv("TSPLAT_WINO3_P5")) != 0;  // A/B knob
-    if (p5 && co <= 32 && wg32 >= 2048) return 5;
-    static const bool f6 = !getenv("TSPLAT_WINO3_F6") || atoi(getenv("TSPLAT_WINO3_F6")) != 0;  // A/B knob
-    if (f6 && co % 64 == 0 && wg6 >= 150 && wg6 <= 320) return 6;
+    if (co <= 32 && wg32 >= 2048) return 5;
+    if (co % 64 == 0 && wg6 >= 150 && wg6 <= 320) return 6;
     if (co > 32 && wg64 > 128) return 4;
     return wg32 <= 256 ? 2 : 1;
 }
@@ -926,9 +924,8 @@ extern "C" int tsplat_conv3x3_wino_bf16x3_ex_fwd(const float* const* srcs, const
     }
     // a 64-wide form over an output whose last 64-channel block is at most half used (the gaussian
     // head's 168 -> 84: 44 of 128 columns padding): the full 64-channel blocks on it, the rest as
-    // 32 x 32 blocks (TSPLAT_WINO3_TAIL=0: off)
-    static const bool tail = !getenv("TSPLAT_WINO3_TAIL") || atoi(getenv("TSPLAT_WINO3_TAIL")) != 0;
-    if (form == 4 && tail && co > 64 && co % 64 != 0 && co % 64 <= 32) {
+    // 32 x 32 blocks
+    if (form == 4 && co > 64 && co % 64 != 0 && co % 64 <= 32) {
         launch<2, 2, 1>(a, blocks, staged, stream, ev.start, nullptr, co / 64);
         if (!geometry(32)) return TSPLAT_EINVAL;
         a.cob_base = (co / 64) * 2;

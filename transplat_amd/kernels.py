@@ -146,7 +146,7 @@ def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
     b, _, hw, c = value.shape
     d = disp.shape[1]
     p = logits.shape[-1] // d
-    if value.dtype == torch.bfloat16 and value.is_cuda and _UV_TABLE_BF16:
+    if value.dtype == torch.bfloat16 and value.is_cuda:
         # bf16 dense mode: value is a bf16 linear output, so value^T is exact in bf16 and the table
         # G = key value^T can run on bf16 MFMA with fp32 accumulation and output: key split as
         # key_hi + key_lo (two bf16 halves, residual error ~2^-17 relative) and both halves taken
@@ -163,7 +163,7 @@ def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
         # bf16x3 dense mode: the same split-bf16 products computed and gathered on chip, no table
         return uv_cross_fused(value, key, intr, pose, disp, offsets, logits, h, w)
     elif _DENSE == "bf16x3" and value.is_cuda and c % 4 == 0:
-        # TSPLAT_UV_FUSED=0 (or C != 128): the table in split-bf16 precision as ONE hipBLASLt bf16 GEMM with K = 3C,
+        # _UV_FUSED off (or C != 128): the table in split-bf16 precision as ONE hipBLASLt bf16 GEMM with K = 3C,
         # [key_hi | key_hi | key_lo] x [val_hi | val_lo | val_hi]^T, fp32 output (47 vs 83 us for the
         # fp32 bmm at b = 1, and vs 104 us on tsplat_linear_bf16x3_fwd, profiles/r4/split_gemm2.log;
         # <= 3 * 2^-18 relative per product)
@@ -296,24 +296,20 @@ _ACTS = {"none": 0, "silu": 1, "gelu": 2, "relu": 3}
 _AFFINE_ID: dict = {}
 
 
-_NO_CONV_EPI = os.environ.get("TSPLAT_NO_CONV_EPI", "")  # A/B timing knob only: "all" or a site name
-
-
-def conv_bias_act(conv, x, act: str = "none", residual=None, site: str = "", extra=()):
+def conv_bias_act(conv, x, act: str = "none", residual=None, extra=()):
     """conv(x) + bias -> act [-> + residual (-> relu for "relu")] with the bias, activation and
     residual in ONE pass after the bias-free MIOpen convolution (tsplat_bias_act_fwd). Under bf16
     autocast (config C3's dense layers) or for outputs the kernel's float4 layout cannot take, the
     module's own forward and PyTorch activations run instead (dense-layer glue, same math).
     Used on the depth predictor's full-resolution conv -> GELU -> conv heads (+0.4 % e2e); on the
-    DPT ResidualConvUnits the bias-free convolutions measured 3 % slower end to end (A/B with
-    TSPLAT_NO_CONV_EPI=<site>), so those keep the module path."""
+    DPT ResidualConvUnits the bias-free convolutions measured 3 % slower end to end, so those keep
+    the module path."""
     if not x.is_cuda:
         raise RuntimeError("transplat HIP ops need device tensors (no CPU path)")
-    if (residual is None and act in _ACTS and _NO_CONV_EPI not in ("all", site)
-            and getattr(conv, "padding_mode", "zeros") == "zeros"
+    if (residual is None and act in _ACTS and getattr(conv, "padding_mode", "zeros") == "zeros"
             and conv_bf16_ok(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, extra)):
         return conv_bf16(x, conv.weight, conv.bias, act, extra)  # bf16 autocast: bias + act fused
-    fused = (not torch.is_autocast_enabled("cuda") and x.dtype == torch.float32 and _NO_CONV_EPI not in ("all", site)
+    fused = (not torch.is_autocast_enabled("cuda") and x.dtype == torch.float32
              and getattr(conv, "padding_mode", "zeros") == "zeros")
     if (fused and residual is None and act in _WINO_ACT
             and conv3x3_wino_ok(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, extra,
@@ -360,12 +356,8 @@ def instance_norm(x, eps: float, act: str = "none", residual=None):
     return group_norm(x, c, w, b, eps, act, residual)
 
 
-_BF16_NORMS = os.environ.get("TSPLAT_BF16_NORMS", "1") != "0"  # A/B knob: bf16-I/O norm kernels (C3)
-_CAT_RES = os.environ.get("TSPLAT_GN_CAT_RES", "1") != "0"  # A/B knob: concatenated residuals read in place
-BF16_NORMS = _BF16_NORMS
-_UV_TABLE_BF16 = os.environ.get("TSPLAT_UV_TABLE_BF16", "1") != "0"  # A/B knob: split-bf16 table GEMM (C3)
-# A/B knob: the fused fine cross correlation (uv_cross_fused) in the bf16x3 dense mode; 0 = the table route
-_UV_FUSED = os.environ.get("TSPLAT_UV_FUSED", "1") != "0"
+# the fused fine cross correlation (uv_cross_fused) in the bf16x3 dense mode; False = the table route
+_UV_FUSED = True
 
 
 def group_norm(x, num_groups: int, weight, bias, eps: float, act: str = "none", residual=None, pre_bias=None):
@@ -380,7 +372,7 @@ def group_norm(x, num_groups: int, weight, bias, eps: float, act: str = "none", 
     bf16 = False
     if isinstance(residual, (tuple, list)):
         r1, r2 = residual
-        if not (_CAT_RES and x.dtype == torch.float32 and r1.dtype == r2.dtype == torch.float32 and x.is_cuda):
+        if not (x.dtype == torch.float32 and r1.dtype == r2.dtype == torch.float32 and x.is_cuda):
             return group_norm(x, num_groups, weight, bias, eps, act, torch.cat([r1, r2], dim=1), pre_bias)
         r1, r2 = r1.contiguous(), r2.contiguous()
         if (r1.shape[0] != n or r2.shape[0] != n or r1.shape[1] + r2.shape[1] != c or r1.shape[2:] != x.shape[2:]
@@ -388,7 +380,7 @@ def group_norm(x, num_groups: int, weight, bias, eps: float, act: str = "none", 
             raise ValueError(f"residual parts {tuple(r1.shape)} + {tuple(r2.shape)} != input {tuple(x.shape)}")
         entry, res = "tsplat_group_norm_cat_res_fwd", (_lib.ptr(r1), _lib.ptr(r2), r1.shape[1])
     else:
-        bf16 = x.dtype == torch.bfloat16 and x.is_cuda and _BF16_NORMS
+        bf16 = x.dtype == torch.bfloat16 and x.is_cuda
         if bf16 and residual is not None and residual.dtype != torch.bfloat16:
             # the module path rounds the norm's output to bf16 (GroupNorm32 casts back to x's dtype)
             # and then promotes bf16 + fp32 to fp32: keep the fp32 residual stream un-narrowed
@@ -411,13 +403,12 @@ def group_norm(x, num_groups: int, weight, bias, eps: float, act: str = "none", 
 
 _LIN_GELU, _LIN_LN, _LIN_RES, _LIN_SPLIT, _LIN_BIAS, _LIN_GELU_IN = 1, 2, 4, 8, 16, 32
 _LIN_RES_PRE_LN, _LIN_RELU_IN, _LIN_BF16X3, _LIN_X_BF16, _LIN_OUT_BF16 = 64, 128, 256, 512, 1024
-# the fused transformer linears' products in bf16x3 inside dense_precision("bf16x3") (the kernel's
-# split-bf16 form, flag 256); TSPLAT_LINF3=0 keeps them exact fp32 in that mode
-_LINF3 = os.environ.get("TSPLAT_LINF3", "1") == "1"
 
 
 def _lin_precision_flag() -> int:
-    return _LIN_BF16X3 if _LINF3 and _DENSE == "bf16x3" else 0
+    """The fused transformer linears' products run in bf16x3 inside dense_precision("bf16x3") (the
+    kernel's split-bf16 form, flag 256)."""
+    return _LIN_BF16X3 if _DENSE == "bf16x3" else 0
 
 
 def _lin_route(flags: int) -> str:
@@ -429,7 +420,7 @@ def _lin_route(flags: int) -> str:
 def fused_linear(x1, weight, x2=None, bias=None, gelu: bool = False, ln=None, residual=None, split: bool = False,
                  gelu_in: bool = False, relu_in: bool = False, res_pre_ln: bool = False, out_dtype=torch.float32):
     """epilogue([x1 | x2] weight^T) in one exact-fp32 MFMA launch (tsplat_linear_f32_fwd; bf16x3
-    products inside dense_precision("bf16x3"), see _LINF3):
+    products inside dense_precision("bf16x3")):
     (+ bias) -> (exact GELU) -> (LayerNorm with ln = (gamma, beta, eps), N = 128) -> (+ residual);
     gelu_in / relu_in apply exact GELU / ReLU to the input first (the producing layer's activation,
     N = 128); res_pre_ln adds the residual before the LayerNorm (post-norm: LN(y + residual)).
@@ -475,11 +466,6 @@ def fused_linear(x1, weight, x2=None, bias=None, gelu: bool = False, ln=None, re
     if split:
         return [t.reshape(*lead, 128) for t in out.unbind(0)]
     return out.reshape(*lead, n)
-
-
-# bf16x3 window attention (tsplat_win_attn_x3_*) as the "auto" attention of the bf16x3 dense mode
-# (see auto_attention); TSPLAT_ATTN_X3=0 keeps the exact-fp32 kernel in that mode
-_ATTN_X3 = os.environ.get("TSPLAT_ATTN_X3", "1") == "1"
 
 
 def split_kv_bf16x3(k, v):
@@ -564,11 +550,8 @@ def attention_merge(q, k, v, h: int, w: int, num_splits: int, with_shift: bool, 
         # layer ask fused_linear for them; fp32 ones are rounded here), the bf16 MFMA kernel with the
         # cross pairing as a key-batch shift, the bf16 message widened by the merge projection's load
         qb, kb, vb = q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16)
-        if not _BF16IO and kv_shift:
-            kb, vb = torch.roll(kb, -kv_shift, dims=0), torch.roll(vb, -kv_shift, dims=0)
-            kv_shift = 0
         msg = window_attention(qb, kb, vb, h, w, num_splits, with_shift, kv_shift=kv_shift)
-        return fused_linear(msg if _BF16IO else msg.float(), merge_weight, ln=ln, residual=residual)
+        return fused_linear(msg, merge_weight, ln=ln, residual=residual)
     ks = int(lib.tsplat_win_attn_split(b, h, w, m, num_splits)) if fp32 and c == 128 else 0
     if ks <= 1:
         if kv_shift:
@@ -578,21 +561,11 @@ def attention_merge(q, k, v, h: int, w: int, num_splits: int, with_shift: bool, 
     return _merge_partials(lib, q, k, v, h, w, num_splits, with_shift, merge_weight, ln, residual, kv_shift, m, None)
 
 
-# bf16 operands / outputs of the fused linear and the key-batch shift of the bf16 attention instead of
-# cast / roll launches around them (C3 as stated); TSPLAT_LIN_BF16IO=0 restores the casts (A/B knob)
-_BF16IO = os.environ.get("TSPLAT_LIN_BF16IO", "1") == "1"
-
-
 def attention_bf16_ready(h: int, w: int, num_splits: int) -> bool:
     """True when attention_merge runs the bf16 window attention for this window shape (attention
     precision "bf16", window pixels a multiple of 128): the layer's q / k / v projections may then
     be written in bf16 directly (fused_linear out_dtype)."""
     return _ATTN == "bf16" and ((h // num_splits) * (w // num_splits)) % 128 == 0
-
-
-def projections_bf16(h: int, w: int, num_splits: int) -> bool:
-    """True when a transformer layer should ask fused_linear for bf16 q / k / v (see _BF16IO)."""
-    return _BF16IO and attention_bf16_ready(h, w, num_splits)
 
 
 def _merge_partials(lib, q, k, v, h, w, num_splits, with_shift, merge_weight, ln, residual, kv_shift, m, kv_x3):
@@ -662,7 +635,7 @@ def residual_ln(x, y, ls, norm, bf16_out: bool = False):
                                               _lib.ptr(x_out), _lib.ptr(n_out), rows, d, _lib.stream_ptr(x.device))
         _lib.check(rc, "tsplat_residual_ln_slabs_fwd")
         return x_out, n_out
-    if _BF16_NORMS and (bf16_out or (y is not None and y.dtype == torch.bfloat16)):
+    if bf16_out or (y is not None and y.dtype == torch.bfloat16):
         yb = y.to(torch.bfloat16).contiguous() if y is not None else None
         x_out = torch.empty_like(xf) if y is not None else xf
         n_out = torch.empty(xf.shape, dtype=torch.bfloat16, device=xf.device)
@@ -761,18 +734,13 @@ def ssim(gt, pred):
 # up to _MHA_X3_ROWS tokens per call: same-box C2 (2 x 325 tokens) 446.9 / 447.8 vs 445.6 / 445.5
 # views/s with the exact-fp32 kernel, but C3 (16 x 325) 900.1 / 899.8 vs 903.4 / 902.1 -- there the
 # split pass over the 48 MB qkv costs what the cheaper products save (profiles/r5/late/ab_mha_x3.txt).
-# TSPLAT_MHA_X3=0 keeps the exact-fp32 kernel in that mode (A/B knob)
-_MHA_X3 = os.environ.get("TSPLAT_MHA_X3", "1") == "1"
 _MHA_X3_ROWS = 2048
-
-
-_MHA_PRESPLIT = os.environ.get("TSPLAT_MHA_PRESPLIT", "1") == "1"  # A/B knob (DINOv2 qkv -> split output)
 
 
 def mha_x3_ok(rows: int) -> bool:
     """True when DINOv2's qkv GEMM hands the bf16x3 attention pre-split operands (mha's default
     precision in the current mode is bf16x3 for `rows` = B * N tokens)."""
-    return _MHA_PRESPLIT and _MHA_X3 and _DENSE == "bf16x3" and rows <= _MHA_X3_ROWS
+    return _DENSE == "bf16x3" and rows <= _MHA_X3_ROWS
 
 
 def mha_presplit(qkv_split, heads: int, scale: float):
@@ -792,14 +760,14 @@ def mha(qkv, heads: int, scale: float, bias=None, precision: str | None = None):
     """Multi-head self-attention from the qkv projection output [B, N, 3 * heads * 64] ->
     [B, N, heads * 64] (tsplat_mha_f32_fwd; no permute copies). bias: the projection's bias when
     qkv was computed without it (tsplat_mha_bias_f32_fwd folds it in). precision "bf16x3" (default:
-    the dense mode's, see _MHA_X3) runs tsplat_mha_x3_fwd."""
+    the dense mode's, see _MHA_X3_ROWS) runs tsplat_mha_x3_fwd."""
     lib = _lib.load()
     b, n, c3 = qkv.shape
     d = c3 // (3 * heads)
     x = _f32(qkv)
     out = torch.empty((b, n, heads * d), dtype=torch.float32, device=qkv.device)
     if precision is None:
-        precision = "bf16x3" if _MHA_X3 and _DENSE == "bf16x3" and b * n <= _MHA_X3_ROWS else "fp32"
+        precision = "bf16x3" if _DENSE == "bf16x3" and b * n <= _MHA_X3_ROWS else "fp32"
     if precision == "bf16x3":
         ws = torch.empty(int(lib.tsplat_mha_x3_workspace_bytes(b, n, heads, d)), dtype=torch.uint8, device=x.device)
         _lib.check(lib.tsplat_mha_x3_fwd(_lib.ptr(x), _lib.ptr(_f32(bias)) if bias is not None else None,
@@ -818,27 +786,25 @@ def mha(qkv, heads: int, scale: float, bias=None, precision: str | None = None):
 # Which convolutions go to tsplat_conv2d_f32_fwd: "auto" (the latency-bound ones, see
 # conv2d_direct_ok), "off" (always MIOpen), "all" (every shape the kernel takes; tests / A/B)
 _CONV_MODE = os.environ.get("TSPLAT_CONV", "auto")
-_CONV_KSPLIT = int(os.environ.get("TSPLAT_CONV_KSPLIT", "0"))  # tuning override (tools/bench_conv.py)
 _CONV_MAX_FLOP = 1.5e9  # above this MIOpen's kernels are as fast or faster (tools/bench_conv.py)
-_SMALL_MAP_DIRECT = os.environ.get("TSPLAT_CONV_SMALLMAP", "1") == "1"
 # 1x1 launch shape: grid cap in waves and minimum ci pairs per wave. Same-box A/B (round-2 session script ab_conv1.sh, pruned in round 5):
 # 16384 / 8 reads 338.98 / 338.99 views/s vs 337.91 / 337.58 for the 3x3 rule (4096 / 16); 8192 / 16
 # and 16384 / 4 sit in between
-_CONV1_WAVES = int(os.environ.get("TSPLAT_CONV1_WAVES", "16384"))
-_CONV1_PAIRS = int(os.environ.get("TSPLAT_CONV1_PAIRS", "8"))
+_CONV1_WAVES = 16384
+_CONV1_PAIRS = 8
 # the same for 3x3 (round-2 session script ab_conv3.sh, pruned in round 5, same box: 8192 / 2 reads 340.3 / 339.7 views/s vs 339.3 /
 # 339.2 at 4096 / 2; 16384 / 1 and 8192 / 1 in between)
-_CONV3_WAVES = int(os.environ.get("TSPLAT_CONV3_WAVES", "8192"))
-_CONV3_PAIRS = int(os.environ.get("TSPLAT_CONV3_PAIRS", "2"))
+_CONV3_WAVES = 8192
+_CONV3_PAIRS = 2
 # Split of each tile's ci pairs over workgroups (tsplat_conv2d_f32_zsplit_fwd) for few-tile maps:
 # doubled while the grid stays within one round of 16-wave workgroups (one per CU) and every wave
 # keeps more than _ZSPLIT_MIN pairs (3x3; 1x1: 4x that). A 32 x 32 tile's workgroup loads the
 # weights of its 32 output channels over the whole reduction, so on few-tile maps the per-CU ingest
 # of those weights, not the MFMAs, sets the time: splitting the reduction over more CUs divides it.
-# TSPLAT_CONV_ZSPLIT=0 turns it off, =N caps it at N.
-_ZSPLIT = int(os.environ.get("TSPLAT_CONV_ZSPLIT", "-1"))
-_ZSPLIT_WGS = int(os.environ.get("TSPLAT_CONV_ZSPLIT_WGS", "256"))
-_ZSPLIT_MIN = int(os.environ.get("TSPLAT_CONV_ZSPLIT_MIN", "1"))  # 4 / 2 / 1: C2 413.4 / 415.8 / 417.3 (profiles/r5/ab_zsplit.txt)
+# _ZSPLIT = 0 turns it off, N > 0 caps it at N, -1 leaves it uncapped.
+_ZSPLIT = -1
+_ZSPLIT_WGS = 256
+_ZSPLIT_MIN = 1  # 4 / 2 / 1: C2 413.4 / 415.8 / 417.3 (profiles/r5/ab_zsplit.txt)
 # arrival counters of the zsplit launches: one zeroed slab per device, handed out in rotating ranges
 # (each launch leaves its range at zero again), so launches in flight on concurrent streams never share
 # a counter while the slab holds more tiles than the launches of one step
@@ -878,7 +844,7 @@ def _wave_split(tiles: int, work: int, max_waves: int, per_wave: int) -> int:
 
 def _zsplit_factor(tiles: int, more) -> int:
     """Workgroups per output tile of a zsplit launch (1 = no split): doubled from z while the grid
-    stays within _ZSPLIT_WGS workgroups, the _ZSPLIT knob allows 2 z and `more(z)` (the site's rule
+    stays within _ZSPLIT_WGS workgroups, _ZSPLIT allows 2 z and `more(z)` (the site's rule
     for the work every wave keeps) holds."""
     if _ZSPLIT == 0:
         return 1
@@ -933,14 +899,9 @@ def conv2d_direct_ok(x, weight, stride: int = 1, padding=None, c2: int = 0, upsa
     flop = 2.0 * npx * co * ci * k * k
     # (since the batch loads are scheduled ahead of the MFMAs, the few-tile / long-reduction 3x3s
     # -- 2 x 256 -> 128 at 16^2 -- also beat MIOpen: 23.5 vs 25.7 us, bench_conv.py)
-    if _SMALL_MAP_DIRECT and npx <= 512:
+    if npx <= 512:
         return True  # tiny maps with long reductions (the DPT's 768 -> 768 stride-2 at 18^2, 1.7 GFLOP)
     return flop <= _CONV_MAX_FLOP
-
-
-# the direct convolutions in the bf16x3 dense mode on split-bf16 MFMA (tsplat_conv2d_bf16x3_fwd) instead of
-# exact fp32; TSPLAT_CONV_X3=0 keeps them exact (A/B knob)
-_CONV_X3 = os.environ.get("TSPLAT_CONV_X3", "1") == "1"
 
 
 def _pack_conv_x3(weight):
@@ -1016,7 +977,7 @@ def conv2d_direct(x1, weight, bias=None, stride: int = 1, x2=None, upsample: boo
     hv, wv = (2 * h, 2 * w) if upsample else (h, w)
     hout, wout = (hv + 2 * (k // 2) - k) // stride + 1, (wv + 2 * (k // 2) - k) // stride + 1
     y = torch.empty((n, co, hout, wout), dtype=torch.float32, device=x1.device)
-    if _CONV_X3 and split_mode() and conv_x3_wins(n * hout * wout, c1 + c2, co, k):
+    if split_mode() and conv_x3_wins(n * hout * wout, c1 + c2, co, k):
         return _conv2d_direct_x3(lib, a, b, c1, c2, weight, bias, n, h, w, co, k, stride, upsample, y)
     # waves per 32 x 32 tile: the ci pairs split over up to 16 waves (>= 2 pairs of a 3x3 each while
     # the grid stays <= 8192 waves; >= 8 pairs of a 1x1 each up to 16384 waves: its waves are short,
@@ -1024,7 +985,7 @@ def conv2d_direct(x1, weight, bias=None, stride: int = 1, x2=None, upsample: boo
     tiles = ((n * hout * wout + 31) // 32) * ((co + 31) // 32)
     pairs = ci // 2
     cap, min_pairs = (_CONV3_WAVES, _CONV3_PAIRS) if k == 3 else (_CONV1_WAVES, _CONV1_PAIRS)
-    ksplit = _CONV_KSPLIT or _wave_split(tiles, pairs, cap, min_pairs)
+    ksplit = _wave_split(tiles, pairs, cap, min_pairs)
     zsplit = conv_zsplit(tiles, pairs, ksplit, k) if ksplit == 16 else 1
     pb = _f32(bias) if bias is not None else None
     part = cnt = None
@@ -1101,9 +1062,6 @@ def conv3x3_wino_ok(x, weight, stride=1, padding=1, dilation=1, groups=1, extra=
             and (ci <= 192 or groups_ >= 256))
 
 
-_ENC_DIRECT = os.environ.get("TSPLAT_ENC_DIRECT", "1") != "0"  # A/B knob for conv2d_forward's direct route
-
-
 def conv2d_forward(mod, x):
     """nn.Conv2d.forward (installed on the encoder's Conv2d modules by install_conv2d_dispatch):
     the 3x3s that conv3x3_wino_ok admits on the Winograd kernel, the latency-bound 1x1 / 3x3
@@ -1115,13 +1073,13 @@ def conv2d_forward(mod, x):
         if conv3x3_wino_ok(x, mod.weight, mod.stride, mod.padding, mod.dilation, mod.groups, vs_miopen=True):
             return conv3x3_wino(x, mod.weight, mod.bias)
         st, pad = _square(mod.stride), _square(mod.padding)
-        if (_ENC_DIRECT and st > 0 and x.is_contiguous() and x.dtype == torch.float32
+        if (st > 0 and x.is_contiguous() and x.dtype == torch.float32
                 and conv2d_direct_ok(x, mod.weight, st, mod.padding)):
             return conv2d_direct(x, mod.weight, mod.bias, st)
         y = _conv2d_x3_libfree(x, mod.weight, mod.bias, mod.stride, mod.padding)
         if y is not None:
             return y
-        if (_LIBFREE and st > 0 and _square(mod.kernel_size) > 3 and pad >= 0 and x.is_cuda
+        if (st > 0 and _square(mod.kernel_size) > 3 and pad >= 0 and x.is_cuda
                 and x.dtype == torch.float32 and mod.weight.dtype == torch.float32
                 and not torch.is_autocast_enabled("cuda")):
             return conv_unfold_gemm(x, mod.weight, mod.bias, st, pad)
@@ -1131,11 +1089,8 @@ def conv2d_forward(mod, x):
 # Convolutions the encoder used to leave on MIOpen (round 5): the UniMatch CNN's 7x7 stride-2 stem
 # and the DPT's transposed convolutions (kernel = stride). MIOpen picks their algorithms by timing
 # (cudnn.benchmark), so their bits could differ from process to process; these forms are exact fp32
-# and fixed. TSPLAT_CONV_LIBFREE=0 keeps them on MIOpen (A/B knob).
-_LIBFREE = os.environ.get("TSPLAT_CONV_LIBFREE", "1") == "1"
-# bf16x3 mode: every remaining Conv2d on the split-bf16 Winograd / direct kernels (TSPLAT_CONV_LIBFREE_X3=0:
-# the shapes above the latency-bound range stay on MIOpen, the A/B knob)
-_LIBFREE_X3 = os.environ.get("TSPLAT_CONV_LIBFREE_X3", "1") == "1"
+# and fixed. In the bf16x3 mode every remaining Conv2d runs on the split-bf16 Winograd / direct kernels
+# (_conv2d_x3_libfree).
 
 
 def conv_unfold_gemm(x, weight, bias, stride: int, padding: int):
@@ -1174,7 +1129,7 @@ def conv_transpose_forward(mod, x):
     """nn.ConvTranspose2d.forward (installed by install_conv2d_dispatch): kernel = stride, no padding
     -> conv_transpose_direct; anything else through MIOpen."""
     st = _square(mod.stride)
-    if (_LIBFREE and _square(mod.kernel_size) == st > 0 and _square(mod.padding) == 0 and mod.groups == 1
+    if (_square(mod.kernel_size) == st > 0 and _square(mod.padding) == 0 and mod.groups == 1
             and _square(mod.output_padding) == 0 and _square(mod.dilation) == 1 and x.is_cuda
             and x.dtype == torch.float32 and mod.weight.dtype == torch.float32 and x.shape[1] % 2 == 0
             and not torch.is_autocast_enabled("cuda")):
@@ -1187,8 +1142,8 @@ def _conv2d_x3_libfree(x, weight, bias, stride, padding):
     Winograd for the 3x3 / stride-1 ones up to 256 input channels, the direct kernel for the rest --
     per shape within ~1.4x of MIOpen either way, 1.26 vs 1.28 ms over C3's 18 such calls
     (tools/c3_libconv.py, profiles/r6/c3_libconv.log), and no library convolution left. None when
-    the shape is not one of those (or TSPLAT_CONV_LIBFREE_X3=0, or another mode)."""
-    if not (_LIBFREE_X3 and split_mode() and x.is_cuda and x.dim() == 4 and x.is_contiguous()
+    the shape is not one of those (or in another mode)."""
+    if not (split_mode() and x.is_cuda and x.dim() == 4 and x.is_contiguous()
             and x.dtype == torch.float32 and weight.dim() == 4):
         return None
     st = _square(stride)
@@ -1233,14 +1188,6 @@ _DENSE = "fp32"
 _DENSE_MODES = ("fp32", "bf16x3")
 
 
-# bf16x3 mode's OTHER library fp32 GEMMs (the ones linear_xf32 below does not admit): with
-# TSPLAT_XF32=1 the whole dense_precision("bf16x3") block runs with torch's allow_tf32, which on
-# gfx950 selects hipBLASLt's emulated-xf32 kernels (fp32 in / out, bf16 MFMA; tools/bench_xf32.py
-# measures their error next to the split kernels'). Off by default; independently of it, the linears
-# linear_xf32_ok admits (on by default, TSPLAT_LINX) always run under allow_tf32 -- see linear_xf32.
-_XF32 = os.environ.get("TSPLAT_XF32", "0") == "1"
-
-
 class dense_precision:
     """Context manager: the dense-layer precision mode inside the block (see _DENSE)."""
 
@@ -1253,7 +1200,9 @@ class dense_precision:
         global _DENSE
         self.prev, _DENSE = _DENSE, self.mode
         self.prev_tf32 = torch.backends.cuda.matmul.allow_tf32
-        torch.backends.cuda.matmul.allow_tf32 = _XF32 and self.mode == "bf16x3"
+        # the block's library fp32 GEMMs stay exact: torch's allow_tf32 selects hipBLASLt's emulated-xf32
+        # kernels on gfx950 (tools/bench_xf32.py measures their error), which only linear_xf32 asks for
+        torch.backends.cuda.matmul.allow_tf32 = False
         return self
 
     def __exit__(self, *exc):
@@ -1278,11 +1227,8 @@ ATTN_MODES = ("fp32", "bf16x3", "bf16")
 
 
 def auto_attention(dense_dtype: str) -> str:
-    """The attention precision "auto" means beside `dense_dtype` (TSPLAT_ATTN_X3=0: exact fp32
-    attention in the bf16x3 dense mode, the A/B knob)."""
-    if dense_dtype == "bf16":
-        return "bf16"
-    return "bf16x3" if dense_dtype == "bf16x3" and _ATTN_X3 else "fp32"
+    """The attention precision "auto" means beside `dense_dtype`."""
+    return dense_dtype if dense_dtype in ("bf16", "bf16x3") else "fp32"
 
 
 class attention_precision:
@@ -1353,10 +1299,9 @@ def linear_bf16x3(x, weight, bias=None, act: str = "none", cache: bool = True):
 # current stream beside the backbone branch's library GEMMs on the side stream), hipGraph replays of
 # the C2 step were NOT the eager step: 1-3 of 4 replays moved 0.6-4 % of the pixels by up to 4e-2
 # (tools/graph_vs_eager.py, profiles/r6/graph_vs_eager.log), with every library GEMM exact fp32 8 of
-# 8 replays were bit-identical to eager. TSPLAT_LINX=1 restores the route (A/B only);
-# TSPLAT_LINX_SIDE=0 with it keeps it off the side streams (measured: still racing).
-_LINX = os.environ.get("TSPLAT_LINX", "0") == "1"
-_LINX_SIDE = os.environ.get("TSPLAT_LINX_SIDE", "1") == "1"
+# 8 replays were bit-identical to eager. _LINX = True restores the route (tests of linear_xf32 only);
+# keeping it off the side streams as well measured still racing.
+_LINX = False
 
 
 def linear_xf32_ok(x, weight) -> bool:
@@ -1366,11 +1311,6 @@ def linear_xf32_ok(x, weight) -> bool:
         return False
     n, k = weight.shape
     m = x.numel() // max(k, 1)
-    if not _LINX_SIDE:
-        from . import streams
-
-        if streams._is_side(torch.cuda.current_stream(x.device)):
-            return False
     return n % 4 == 0 and ((n >= 1024 and m >= 512) or (m >= 4096 and n >= 512))
 
 
@@ -1395,9 +1335,7 @@ def linear_xf32(x, weight, bias=None, act: str = "none"):
 
 
 # Hand-written split-bf16 GEMM (tsplat_gemm_x3_fwd) for the bf16x3 mode's DINOv2 linears (round 6):
-# replaces hipBLASLt's exact-fp32 / emulated-xf32 GEMMs there. TSPLAT_GEMM_X3=0: the library path.
-_GEMM_X3 = os.environ.get("TSPLAT_GEMM_X3", "1") == "1"
-_GEMM_KSPLIT = int(os.environ.get("TSPLAT_GEMM_KSPLIT", "0"))  # 0: auto
+# replaces hipBLASLt's exact-fp32 / emulated-xf32 GEMMs there.
 GEMM_LOG = None  # list: (m, n, k, ksplit) per launch when set (bench.py's roofline)
 
 
@@ -1405,7 +1343,7 @@ def gemm_x3_ok(x, weight) -> bool:
     """True when gemm_x3 takes F.linear(x, weight) in the current mode: bf16x3 dense mode, fp32 on
     the GPU, k and n multiples of 4. weight [n, k], or [n, ...] read as [n, k] (a 1x1 or
     kernel = stride convolution weight)."""
-    if not (_GEMM_X3 and _DENSE == "bf16x3" and x.is_cuda and x.dtype == torch.float32
+    if not (_DENSE == "bf16x3" and x.is_cuda and x.dtype == torch.float32
             and weight.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")):
         return False
     n = weight.shape[0]
@@ -1433,8 +1371,6 @@ def gemm_ksplit(m: int, n: int, k: int) -> int:
     """Split-K factor: the tile grid (64-row x 128-column blocks) filled up to one workgroup per CU
     (256; a 257th workgroup doubles a CU's share: DINOv2 fc2 at 3 splits 17.3 us, at 4 21.5,
     profiles/r6/gemm/), every split at least two 64-deep chunks."""
-    if _GEMM_KSPLIT > 0:
-        return _GEMM_KSPLIT
     tiles = -(-m // 64) * -(-n // 128)
     nchunk = -(-k // 64)
     s = max(1, min(nchunk // 2, 256 // tiles))
@@ -1472,7 +1408,7 @@ def gemm_x3(x, weight, bias=None, act: str = "none", ksplit: int = 1):
 
 def linear_forward(mod, x):
     """nn.Linear.forward (installed by install_linear_dispatch): in dense_precision("bf16x3") the fp32
-    linears run on the split-bf16 GEMM (gemm_x3; linear_xf32 instead if its A/B knob admits them, and
+    linears run on the split-bf16 GEMM (gemm_x3; linear_xf32 instead if _LINX admits them, and
     F.linear below 64 rows); everything else is F.linear."""
     if linear_xf32_ok(x, mod.weight):
         return linear_xf32(x, mod.weight, mod.bias)
@@ -1513,20 +1449,21 @@ def wino_pack_weight_bf16x3(weight):
 
 
 # bf16x3 3x3s of few-channel full-resolution maps on the direct kernel tsplat_conv3x3_few_bf16x3_fwd
-# instead of the Winograd one (TSPLAT_CONV_FEW=0: Winograd everywhere, the A/B knob): <= 32 outputs from
+# instead of the Winograd one (_FEW = False: Winograd everywhere): <= 32 outputs from
 # <= 64 inputs over >= 2 x 256^2 pixels, where it measured faster (2 x 32 -> 32 at 256^2 20.9 vs 25.3 us,
 # 64 -> 32 32.1 vs 35.3, 38 -> 32 26.7 vs 29.6; at 64 outputs or 128^2 maps it only ties:
 # profiles/r6/few_sweep.log)
-_FEW = os.environ.get("TSPLAT_CONV_FEW", "1") != "0"
-FEW_MIN_PX = int(os.environ.get("TSPLAT_CONV_FEW_MIN_PX", str(2 * 256 * 256)))
-FEW_MAX_CI = int(os.environ.get("TSPLAT_CONV_FEW_MAX_CI", "64"))
-FEW_MAX_CO = int(os.environ.get("TSPLAT_CONV_FEW_MAX_CO", "32"))
+_FEW = True
+FEW_MIN_PX = 131072
+FEW_MAX_CI = 64
+FEW_MAX_CO = 32
 
 
-def _few_ok(srcs, n: int, h: int, w: int, co: int) -> bool:
+def _few_ok(srcs, n: int, h: int, w: int, co: int, others=()) -> bool:
+    """others: the output and the residuals, which the kernel also moves as float4 (16-byte aligned)."""
     ci = sum(t.shape[1] for t in srcs)
     return (_FEW and co <= FEW_MAX_CO and ci <= FEW_MAX_CI and n * h * w >= FEW_MIN_PX and w % 4 == 0
-            and all(t.data_ptr() % 16 == 0 for t in srcs)
+            and all(t.data_ptr() % 16 == 0 for t in (*srcs, *others) if t is not None)
             and int(_lib.load().tsplat_conv3x3_few_form(n, ci, h, w, co)) != 0)
 
 
@@ -1571,7 +1508,7 @@ def conv3x3_wino(x, weight, bias=None, act: str = "none", extra=(), precision: s
         for r in res:
             if r is not None and tuple(r.shape) != tuple(y.shape):
                 raise ValueError(f"residual {tuple(r.shape)} != output {tuple(y.shape)}")
-        if _few_ok(srcs, n, h, w, co):
+        if _few_ok(srcs, n, h, w, co, (y, *res)):
             # few-channel full-resolution maps: the direct split-bf16 kernel (csrc/convfew.hip)
             rc = lib.tsplat_conv3x3_few_bf16x3_fwd(
                 ptrs, chans, len(srcs), _lib.ptr(conv_pack_weight_x3(weight)), _lib.ptr(pb), _lib.ptr(res[0]),
@@ -1590,8 +1527,7 @@ def conv3x3_wino(x, weight, bias=None, act: str = "none", extra=(), precision: s
 
 
 # bf16 implicit-GEMM 3x3 / 1x1 convolution (tsplat_conv2d_bf16_fwd) for the convolutions that run
-# under bf16 autocast (config C3); "0" = MIOpen (A/B knob)
-_CONV_BF16 = os.environ.get("TSPLAT_CONV_BF16", "1") != "0"
+# under bf16 autocast (config C3)
 
 
 def _pack_conv_bf16(weight):
@@ -1620,7 +1556,7 @@ def conv_bf16_ok(x, weight, stride=1, padding=None, dilation=1, groups=1, extra=
     tsplat_conv2d_bf16_fwd: 3x3 / padding 1 or 1x1 / padding 0, stride 1, NCHW contiguous fp32 or
     bf16 sources (any channel counts, dtypes may differ) with the convolved width a multiple of 8, at
     most 4 sources; up = optional nearest 2x upsample read in place."""
-    if (not _CONV_BF16 or not x.is_cuda or not torch.is_autocast_enabled("cuda")
+    if (not x.is_cuda or not torch.is_autocast_enabled("cuda")
             or torch.get_autocast_dtype("cuda") != torch.bfloat16 or len(extra) > 3):
         return False
     for t in (x, *extra):
@@ -1778,12 +1714,7 @@ def interpolate_bilinear_ac(x, size):
     return y
 
 
-# Depth-Anything's glue as HIP kernels, one A/B knob each ("0": the PyTorch launches): images -> patch
-# matrix -> patch projection on gemm_x3; the depth tail
-DA_PATCH = os.environ.get("TSPLAT_DA_PATCH", "1") != "0"
-DA_TAIL = os.environ.get("TSPLAT_DA_TAIL", "1") != "0"
-
-
+# Depth-Anything's glue as HIP kernels: images -> patch matrix -> patch projection on gemm_x3; the depth tail
 def da_patches(images, mean, std, grid, patch: int):
     """images [..., 3, h, w] fp32 -> the patch matrix [n (1 + gh gw), 3 patch^2] of the images
     normalised with mean / std ([3] device tensors), reordered to channels (2, 0, 1) and resized to

@@ -197,7 +197,7 @@ class DinoVisionTransformer(nn.Module):
         """Whether prepare_tokens_patches takes these images (bf16x3 dense mode, fp32 on the GPU, the
         fused block chain with a plain first LayerNorm)."""
         proj = self.patch_embed.proj
-        return (kernels.DA_PATCH and images.is_cuda and images.dtype == torch.float32
+        return (images.is_cuda and images.dtype == torch.float32
                 and isinstance(self.patch_embed.norm, nn.Identity) and type(self.blocks[0].norm1) is nn.LayerNorm
                 and self.embed_dim in (256, 512, 768, 1024) and proj.bias is not None
                 and kernels.gemm_x3_ok(images.new_empty((0, proj.weight[0].numel())), proj.weight)
@@ -241,7 +241,7 @@ class DinoVisionTransformer(nn.Module):
         return (ok_dtype and x.shape[-1] in (256, 512, 768, 1024)
                 and all(isinstance(m, (LayerScale, nn.Identity)) for b in self.blocks for m in (b.ls1, b.ls2)))
 
-    def _blocks_fused(self, x, take, norm: bool, on_output=None, h=None):
+    def _blocks_fused(self, x, take, norm: bool, h=None):
         """The block chain with every pre-norm residual step x = x + ls(y), h = norm_next(x) as ONE
         kernel (kernels.residual_ln) instead of mul + add + LayerNorm launches; same math. `h`: the
         first block's norm1(x), if the caller has it (prepare_tokens_patches)."""
@@ -264,16 +264,10 @@ class DinoVisionTransformer(nn.Module):
                     outputs.append(x)
                 else:  # the last block's step already produced self.norm(x)
                     outputs.append(h if last else kernels.residual_ln(x, None, None, self.norm, bf16_out=bf)[1])
-                if on_output is not None:
-                    on_output(len(outputs) - 1, outputs[-1])
         return outputs
 
-    def get_intermediate_layers(self, x, n=4, reshape=False, return_class_token=False, norm=True,
-                                on_output=None, tokens=None):
-        """`on_output(k, tokens)` (not in the reference) is called as soon as the k-th taken layer's
-        normed tokens [B, 1 + N, C] exist, so a consumer can start on them while the later blocks
-        run (DepthAnythingV2.forward forks the DPT reassemble branches this way). `tokens` (not in
-        the reference): prepare_tokens_patches' (x, h) in place of the images x."""
+    def get_intermediate_layers(self, x, n=4, reshape=False, return_class_token=False, norm=True, tokens=None):
+        """`tokens` (not in the reference): prepare_tokens_patches' (x, h) in place of the images x."""
         take = range(len(self.blocks) - n, len(self.blocks)) if isinstance(n, int) else n
         h = None
         if tokens is not None:
@@ -281,15 +275,13 @@ class DinoVisionTransformer(nn.Module):
         else:
             x = self.prepare_tokens(x)
         if h is not None or self._fused_ok(x):
-            outputs = self._blocks_fused(x, take, norm, on_output, h=h)
+            outputs = self._blocks_fused(x, take, norm, h=h)
         else:
             outputs = []
             for i, blk in enumerate(self.blocks):
                 x = blk(x)
                 if i in take:
                     outputs.append(self.norm(x) if norm else x)
-                    if on_output is not None:
-                        on_output(len(outputs) - 1, outputs[-1])
         class_tokens = [o[:, 0] for o in outputs]
         outputs = [o[:, 1:] for o in outputs]
         if return_class_token:

@@ -4,44 +4,33 @@ as the reference forward does; parameter names match (`depth_head.{projects,resi
 scratch.{layer*_rn,refinenet*,output_conv*}}`)."""
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 
-from ... import kernels, streams
+from ... import kernels
 from .dinov2 import DINOv2
 
 # The token maps enter the DPT as channels-last views (permute of [B, N, C]); the whole conv chain
 # then runs MIOpen's NHWC kernels, measured ~4% faster end-to-end than an NCHW copy up front. The
 # conv weights are laid out channels-last once (first forward) so torch stops re-laying them out
-# on every call.
-_DPT_CL_WEIGHTS = os.environ.get("TSPLAT_DPT_CL_WEIGHTS", "1") != "0"
-# Opt-in: "1" runs the latency-bound DPT convolutions (ResidualConvUnits <= 36^2, out_convs) as the
-# channels-last direct kernel (kernels.conv2d_nhwc, ReLU / bias / residual fused), "rcu" only the
-# units. Measured 2.0 % ("1") and 1.3 % ("rcu") SLOWER end to end than MIOpen's NHWC kernels: the
-# kernel's pixel-per-lane B gathers touch 32 cache lines per load on a channels-last map. Default
-# "0" (MIOpen) until the operand is staged through LDS.
-_DPT_DIRECT = os.environ.get("TSPLAT_DPT_DIRECT", "0")
-# conv epilogues (bias + ReLU, bias + residuals) fused after the MIOpen convolutions; "0" = A/B off
-_DPT_EPI = os.environ.get("TSPLAT_DPT_EPI", "1") != "0"
-# Opt-in "1": the reassemble branches of ViT layers 1-3 forked onto a side stream while the later
-# blocks run (needs streams.enabled). Measured SLOWER end to end (profiles/r3/ab_r3c: C2 332 vs
-# 356 views/s, C3 849 vs 887): the branches' MIOpen convolutions take CUs from the critical path
-# (DINOv2 blocks and the backbone beside them) rather than filling idle ones. Round 6 (hand-written
-# DINOv2 GEMMs): still slower, 444.7 vs 487.6 views/s same box (profiles/r6/ab_c2_dpt_hoist.txt).
-_DPT_HOIST = os.environ.get("TSPLAT_DPT_HOIST", "0") == "1"
+# on every call. The convolutions stay on MIOpen with their epilogues (bias + ReLU, bias + residuals)
+# fused after them: as the channels-last direct kernel (kernels.conv2d_nhwc) the latency-bound ones
+# (ResidualConvUnits <= 36^2, out_convs) measured 2.0 % SLOWER end to end, the units alone 1.3 %: its
+# pixel-per-lane B gathers touch 32 cache lines per load on a channels-last map.
+# The reassemble branches run after the last ViT block: forked onto a side stream while the later
+# blocks run they measured SLOWER end to end (profiles/r3/ab_r3c: C2 332 vs 356 views/s, C3 849 vs
+# 887): the branches' MIOpen convolutions take CUs from the critical path (DINOv2 blocks and the
+# backbone beside them) rather than filling idle ones. Round 6 (hand-written DINOv2 GEMMs): still
+# slower, 444.7 vs 487.6 views/s same box (profiles/r6/ab_c2_dpt_hoist.txt).
 # bf16x3 dense mode (kernels.dense_precision): the head runs on NCHW maps instead, so its 3x3
 # convolutions take the bf16x3 Winograd kernel with the ResidualConvUnit glue fused (ReLU on load,
-# bias, + x, + the fusion block's skip: two launches per unit) and the 1x1s the direct kernel;
-# "0" = the channels-last MIOpen chain in that mode too (A/B knob).
-_DPT_NCHW3 = os.environ.get("TSPLAT_DPT_NCHW3", "1") != "0"
+# bias, + x, + the fusion block's skip: two launches per unit) and the 1x1s the direct kernel.
 
 
 def _nchw3() -> bool:
-    return _DPT_NCHW3 and kernels.split_mode()
+    return kernels.split_mode()
 
 
 def _resize(x, modifier: dict, align_corners: bool):
@@ -50,10 +39,10 @@ def _resize(x, modifier: dict, align_corners: bool):
     interpolation kernel."""
     # (bilinear upsampling runs in fp32 under autocast: a bf16 map is widened first, as autocast
     # itself would, and then takes the kernel instead of torch's NHWC kernel, 88 us per call at C3)
-    if (_DPT_EPI and align_corners and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] % 4 == 0
+    if (align_corners and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] % 4 == 0
             and torch.is_autocast_enabled("cuda") and x.is_contiguous(memory_format=torch.channels_last)):
         x = x.float().contiguous(memory_format=torch.channels_last)
-    if (_DPT_EPI and align_corners and x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0
+    if (align_corners and x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0
             and x.is_contiguous(memory_format=torch.channels_last)):
         if "size" in modifier:
             size = modifier["size"]
@@ -61,7 +50,7 @@ def _resize(x, modifier: dict, align_corners: bool):
             sf = modifier["scale_factor"]
             size = (int(x.shape[-2] * sf), int(x.shape[-1] * sf))
         return kernels.resize_bilinear_nhwc(x, size)
-    if _DPT_EPI and align_corners and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous():
+    if align_corners and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous():
         # NCHW fp32 (the head's final resize; every config, fp32 included -- test_depth_anything_gpu
         # covers it in fp32): PyTorch's generic NCHW kernel took 0.87 ms per call at C3's batch 8
         if "size" in modifier:
@@ -85,7 +74,7 @@ class ResidualConvUnit(nn.Module):
         self.activation = activation
 
     def _epilogue_ok(self, x) -> bool:
-        return (_DPT_EPI and not self.bn and isinstance(self.activation, nn.ReLU) and x.dtype == torch.float32
+        return (not self.bn and isinstance(self.activation, nn.ReLU) and x.dtype == torch.float32
                 and self.conv1.weight.dtype == torch.float32 and x.shape[1] % 4 == 0
                 and not torch.is_autocast_enabled("cuda"))
 
@@ -98,18 +87,11 @@ class ResidualConvUnit(nn.Module):
             out = kernels.conv3x3_wino(x, self.conv1.weight, self.conv1.bias, relu_in=True)
             return kernels.conv3x3_wino(out, self.conv2.weight, self.conv2.bias, relu_in=True, residual=x,
                                         residual2=skip)
-        if _DPT_DIRECT == "0" and self._epilogue_ok(x):
+        if self._epilogue_ok(x):
             # bias-free MIOpen convs with bias + ReLU / bias + residual(s) fused after each:
             # 3 glue launches per unit instead of 5 (6 with the fusion block's add)
             out = kernels.conv_nhwc_epilogue(self.conv1, self.activation(x), "relu")
             return kernels.conv_nhwc_epilogue(self.conv2, out, "none", x, skip)
-        if (_DPT_DIRECT != "0" and not self.bn and isinstance(self.activation, nn.ReLU)
-                and kernels.conv2d_nhwc_ok(x, self.conv1.weight)):
-            # latency-bound levels (<= 36^2): ReLU-on-load, bias and the residual fused into the
-            # channels-last direct convolution, two launches for the unit
-            out = kernels.conv2d_nhwc(x, self.conv1.weight, self.conv1.bias, relu_in=True)
-            y = kernels.conv2d_nhwc(out, self.conv2.weight, self.conv2.bias, residual=x, relu_in=True)
-            return y if skip is None else skip + y
         out = self.conv1(self.activation(x))
         if self.bn:
             out = self.bn1(out)
@@ -140,8 +122,6 @@ class FeatureFusionBlock(nn.Module):
         else:
             modifier = {"size": size}
         output = _resize(output, modifier, self.align_corners)
-        if _DPT_DIRECT == "1" and kernels.conv2d_nhwc_ok(output, self.out_conv.weight):
-            return kernels.conv2d_nhwc(output, self.out_conv.weight, self.out_conv.bias)
         return self.out_conv(output)
 
 
@@ -187,7 +167,7 @@ class DPTHead(nn.Module):
         self._cl_done = True
 
     def prepare(self, is_cuda: bool):
-        if _DPT_CL_WEIGHTS and not getattr(self, "_cl_done", False) and is_cuda and not _nchw3():
+        if not getattr(self, "_cl_done", False) and is_cuda and not _nchw3():
             self._channels_last_weights()
 
     def reassemble(self, i, x, patch_h, patch_w):
@@ -200,16 +180,12 @@ class DPTHead(nn.Module):
         x = self.resize_layers[i](self.projects[i](x))
         return getattr(self.scratch, f"layer{i + 1}_rn")(x)
 
-    def forward(self, out_features, patch_h, patch_w, rn=None, raw_tail: bool = False):
-        """`rn` (not in the reference): branch outputs already computed by `reassemble` (None
-        entries are computed here). `raw_tail`: the depth may come back WITHOUT
-        output_conv2's last ReLU (the bf16x3 NCHW route only); the caller applies ReLU either way."""
+    def forward(self, out_features, patch_h, patch_w, raw_tail: bool = False):
+        """`raw_tail` (not in the reference): the depth may come back WITHOUT output_conv2's last
+        ReLU (the bf16x3 NCHW route only); the caller applies ReLU either way."""
         self.prepare(out_features[0][0].is_cuda)
-        rn = list(rn) if rn is not None else [None] * len(out_features)
-        for i, x in enumerate(out_features):
-            if rn[i] is None:
-                rn[i] = self.reassemble(i, x[0], patch_h, patch_w)
-        layer_1_rn, layer_2_rn, layer_3_rn, layer_4_rn = rn
+        layer_1_rn, layer_2_rn, layer_3_rn, layer_4_rn = [self.reassemble(i, x[0], patch_h, patch_w)
+                                                          for i, x in enumerate(out_features)]
         s = self.scratch
         path_4 = s.refinenet4(layer_4_rn, size=layer_3_rn.shape[2:])
         path_3 = s.refinenet3(path_4, layer_3_rn, size=layer_2_rn.shape[2:])
@@ -217,7 +193,7 @@ class DPTHead(nn.Module):
         path_1 = s.refinenet1(path_2, layer_1_rn)
         final_out = s.output_conv1(path_1)
         # nothing below writes final_out in place (_resize allocates its result): no copy needed
-        out_feature = final_out.detach() if kernels.DA_TAIL else final_out.clone().detach()
+        out_feature = final_out.detach()
         final_out = _resize(final_out, {"size": (int(patch_h * 14), int(patch_w * 14))}, True)
         oc = s.output_conv2
         if _nchw3() and final_out.is_contiguous() and kernels.conv3x3_wino_ok(final_out, oc[0].weight, vs_miopen=True):
@@ -225,7 +201,7 @@ class DPTHead(nn.Module):
             if raw_tail and isinstance(oc[3], nn.ReLU) and isinstance(oc[4], nn.Identity):
                 return oc[2](h), out_feature  # the ReLUs are the caller's
             return oc[4](oc[3](oc[2](h))), out_feature
-        if (_DPT_EPI and final_out.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
+        if (final_out.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
                 and final_out.is_cuda and final_out.is_contiguous(memory_format=torch.channels_last)):
             # conv -> ReLU as conv + (bias, ReLU) epilogue; the 1-channel tail stays on the modules
             h = kernels.conv_nhwc_epilogue(oc[0], final_out, "relu")
@@ -258,25 +234,13 @@ class DepthAnythingV2(nn.Module):
             is_cuda = x.is_cuda
         head = self.depth_head
         head.prepare(is_cuda)
-        n_take = len(self.intermediate_layer_idx[self.encoder])
-        pending = {}
-
-        def on_output(k, tokens):
-            # branches 1-3 start on a side stream as soon as their ViT layer exists and overlap the
-            # remaining blocks; the last one has nothing left to overlap and runs inline
-            if k + 1 < n_take and _DPT_HOIST and streams.enabled(tokens.device):
-                pending[k] = streams.fork(tokens.device, head.reassemble, k, tokens[:, 1:], patch_h, patch_w,
-                                          slot=1)
-
         from ...misc.benchmarker import stage
 
         with stage(None, "da_dinov2"):  # diagnostic sub-stage marks (TSPLAT_MARKS / TSPLAT_ROCTX)
             features = self.pretrained.get_intermediate_layers(x, self.intermediate_layer_idx[self.encoder],
-                                                               return_class_token=True, on_output=on_output,
-                                                               tokens=tokens)
-        rn = [streams.join(pending[k]) if k in pending else None for k in range(n_take)]
+                                                               return_class_token=True, tokens=tokens)
         with stage(None, "da_dpt"):
-            depth, out_features = head(features, patch_h, patch_w, rn=rn, raw_tail=raw_depth)
+            depth, out_features = head(features, patch_h, patch_w, raw_tail=raw_depth)
         if raw_depth:
             return depth, out_features
         return F.relu(depth).squeeze(1), out_features

@@ -2,8 +2,6 @@
 (reference src/model/encoder/backbone/backbone_multiview.py:14-133)."""
 from __future__ import annotations
 
-import os
-
 import torch
 from einops import rearrange
 
@@ -16,8 +14,6 @@ _IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
 _POSITION_CACHE: dict = {}
-# the views' camera encodings in one call + the tiled window position ("0": per view, the A/B knob)
-_BATCHED = os.environ.get("TSPLAT_BB_BATCHED", "1") == "1"
 
 
 def _window_position(x, feature_channels):
@@ -91,7 +87,7 @@ class BackboneMultiview(torch.nn.Module):
         cnn = torch.stack(cur_features_list, dim=1)  # [b, v, C, h, w]
         cnn_features = cnn if return_cnn_features else None
         b, v = cnn.shape[:2]
-        if _BATCHED and attn_splits > 1 and cnn.shape[-2] % attn_splits == 0 and cnn.shape[-1] % attn_splits == 0:
+        if attn_splits > 1 and cnn.shape[-2] % attn_splits == 0 and cnn.shape[-1] % attn_splits == 0:
             # all views in one camera-encoder call (per-sample ops: the same per view as the
             # reference's loop, reference :105-108) and the tiled window position added once
             enc = self.cam_param_encoder(cnn.flatten(0, 1), img2world.flatten(0, 1))

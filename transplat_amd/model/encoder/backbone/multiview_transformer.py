@@ -7,8 +7,6 @@ AV, merge, roll back) is ONE gfx950 kernel call (transplat_amd.kernels.window_at
 """
 from __future__ import annotations
 
-import os
-
 import torch
 from torch import nn
 
@@ -75,7 +73,7 @@ class TransformerLayer(nn.Module):
                 _, kv_x3 = K.linear_kv_x3(target, self._cat_weights(("k_proj", "v_proj")), 0)
         else:
             # bf16 window attention (C3 as stated): the projections written in bf16 directly
-            od = torch.bfloat16 if K.projections_bf16(height, width, attn_num_splits) else torch.float32
+            od = torch.bfloat16 if K.attention_bf16_ready(height, width, attn_num_splits) else torch.float32
             if target is source:
                 query, key, value = K.fused_linear(source, self._cat_weights(("q_proj", "k_proj", "v_proj")),
                                                    split=True, out_dtype=od)
@@ -130,7 +128,7 @@ class TransformerLayer(nn.Module):
 
     def _ln128_ok(self, source) -> bool:
         return (self.dim == 128 and source.is_cuda and torch.is_autocast_enabled(source.device.type)
-                and torch.get_autocast_dtype(source.device.type) == torch.bfloat16 and kernels.BF16_NORMS)
+                and torch.get_autocast_dtype(source.device.type) == torch.bfloat16)
 
 
 class TransformerBlock(nn.Module):
@@ -159,9 +157,6 @@ class TransformerBlock(nn.Module):
         # between blocks, :624-628), its queries from the self-attention output
         y = self.self_attn._forward_fused(x, x, height, width, attn_num_splits)
         return self.cross_attn_ffn._forward_fused(y, x, height, width, attn_num_splits, kv_shift=kv_shift)
-
-
-_ONE_COPY = os.environ.get("TSPLAT_MVT_ONE_COPY", "1") == "1"  # A/B knob for the single-copy output
 
 
 def stacked_views(features):
@@ -220,8 +215,6 @@ class MultiViewFeatureTransformer(nn.Module):
                 x = layer.forward_pair(x, h, w, attn_num_splits, kv_shift=b)
             # both views' NCHW maps in ONE permute copy, as views of a [b, v, c, h, w] tensor (the
             # backbone stacks them without another copy, see stacked_views)
-            if not _ONE_COPY:
-                return [f.view(b, h, w, c).permute(0, 3, 1, 2).contiguous() for f in x.chunk(chunks=2, dim=0)]
             stacked = x.view(2, b, h, w, c).permute(1, 0, 4, 2, 3).contiguous()
             return list(stacked.unbind(1))
         concat0, concat1 = batch_features(multi_view_features)

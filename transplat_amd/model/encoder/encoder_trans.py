@@ -9,8 +9,6 @@ kernels), Gaussian adapter (e3nn-free SH rotation). No host synchronisation betw
 """
 from __future__ import annotations
 
-import os
-
 from contextlib import nullcontext
 from dataclasses import dataclass, field
 from typing import List, Literal, Optional
@@ -80,21 +78,6 @@ class EncoderTransCfg:
     # else exact fp32; kernels.auto_attention), "fp32", "bf16x3" or "bf16" (config C3 as
     # BASELINE.json states it: bf16 attention beside fp32-class dense layers).
     attn_dtype: str = "auto"
-
-
-# camera-only prep of the depth predictor and the adapter on the backbone's branch
-# (TSPLAT_CAM_HOIST=0: computed where it is used, the A/B knob)
-_CAM_HOIST = os.environ.get("TSPLAT_CAM_HOIST", "1") == "1"
-# the depth predictor's backbone-only first part on the backbone's branch ("1"; default "0": after the
-# join). Round 6: with it on the branch, hipGraph replays of the step were not the eager step (the
-# encoder's Gaussians moved in 4-8 of 12 replays, means by up to 17; tools/enc_graph_race.py,
-# profiles/r6/graph_race.log), with it after the join 0 of 32. The coarse correlation kernel itself
-# is deterministic beside a busy stream and in two-stream graphs, and reads nothing outside its
-# inputs (tools/coarse_stress.py, tools/coarse_oob.py); the hazard is in the branch arrangement,
-# whose cause was not pinned down. Cost: C2 ~1 % (486.6 vs 490.9 views/s same box).
-_DP_BEGIN_SIDE = os.environ.get("TSPLAT_DP_BEGIN_SIDE", "0") == "1"
-# Depth-Anything on the side stream and the backbone on the current one (A/B; with TSPLAT_SIDE_PRIO)
-_DA_SIDE = os.environ.get("TSPLAT_DA_SIDE", "0") == "1"
 
 
 class EncoderTrans(Encoder[EncoderTransCfg]):
@@ -178,7 +161,7 @@ class EncoderTrans(Encoder[EncoderTransCfg]):
                 # pageable host-to-device copy, which is not allowed inside hipGraph capture
                 dino = self.da_model.pretrained
                 # the depth tail as two launches (kernels.depth_norm) from the head's last 1x1 map
-                tail = kernels.DA_TAIL and kernels.split_mode() and images.is_cuda and images.dtype == torch.float32
+                tail = kernels.split_mode() and images.is_cuda and images.dtype == torch.float32
                 if kernels.split_mode() and dino.patches_ok(images):
                     # normalise + reorder + resize + unfold in one launch, straight into the patch
                     # projection's GEMM operand
@@ -214,42 +197,31 @@ class EncoderTrans(Encoder[EncoderTransCfg]):
                 tf, cf = self.backbone(images, attn_splits=self.cfg.multiview_trans_attn_split,
                                        return_cnn_features=True, img2world=img2world)
             # the backbone's branch finishes well before Depth-Anything: its slack takes the camera prep
-            cams = camera_consts(intrinsics, extrinsics, near, far) if _CAM_HOIST else (None, None)
-            return tf.float(), cf.float(), cams
+            return tf.float(), cf.float(), camera_consts(intrinsics, extrinsics, near, far)
 
-        # Stages 2 and 3 read only the context images, and the depth predictor's first part (its
-        # feature lists and the coarse correlation layer) reads only the backbone's outputs and the
-        # cameras: on a GPU, the backbone, the camera prep and that first part run on a side stream
-        # (transplat_amd/streams.py; captured into the step's hipGraph as a parallel branch) beside
-        # Depth-Anything -- together shorter than it. Both are chains of small launches (DINOv2's
-        # M = 650 GEMMs, the MVT's 256-workgroup kernels) that leave CUs idle on their own.
+        # Stages 2 and 3 read only the context images: on a GPU, the backbone and the camera prep run
+        # on a side stream (transplat_amd/streams.py; captured into the step's hipGraph as a parallel
+        # branch) beside Depth-Anything -- together shorter than it. Both are chains of small launches
+        # (DINOv2's M = 650 GEMMs, the MVT's 256-workgroup kernels) that leave CUs idle on their own.
         # Depth-Anything stays on the current stream: the other arrangement (it on the side stream,
         # the backbone here) measured 1 % slower, its DPT then losing CUs to the MVT (C2 426 vs 430
-        # views/s same box, profiles/r5/ab_da_side.txt); and a fork from a side stream inside hipGraph
-        # capture crashes HIP's capture_end, so the depth predictor's projection fork waits for the
-        # current stream.
-        def dp_begin(tf, cf, dp_cams, fork_projection):
-            with bench("encoder_4_depth_predictor"), self._dense():
-                return self.depth_predictor.begin(tf, context["intrinsics"], context["extrinsics"], context["near"],
-                                                  context["far"], cnn_features=cf, benchmarker=benchmarker,
-                                                  cams=dp_cams, fork_projection=fork_projection)
-
-        def backbone_branch(*ctx):
-            tf, cf, cams = backbone(*ctx)
-            begun = dp_begin(tf, cf, cams[0], not streams.enabled(device)) if _DP_BEGIN_SIDE else None
-            return tf, cf, cams, begun
-
-        ctx = (context["image"], context["intrinsics"], context["extrinsics"], context["near"], context["far"])
-        if _DA_SIDE:  # A/B arrangement: Depth-Anything on the side stream, the backbone here
-            da = streams.fork(device, depth_anything, context["image"])
-            trans_features, cnn_features, (dp_cams, adapter_cams), begun = backbone_branch(*ctx)
-            da_depth, out_feature = streams.join(da)
-        else:
-            bb = streams.fork(device, backbone_branch, *ctx)
-            da_depth, out_feature = depth_anything(context["image"])
-            trans_features, cnn_features, (dp_cams, adapter_cams), begun = streams.join(bb)
-        if begun is None:
-            begun = dp_begin(trans_features, cnn_features, dp_cams, True)
+        # views/s same box, profiles/r5/ab_da_side.txt).
+        # The depth predictor's backbone-only first part (its feature lists and the coarse correlation
+        # layer) runs after the join. Round 6: with it on the backbone's branch, hipGraph replays of
+        # the step were not the eager step (the encoder's Gaussians moved in 4-8 of 12 replays, means
+        # by up to 17; profiles/r6/graph_race.log), after the join 0 of 32. The coarse correlation
+        # kernel itself is deterministic beside a busy stream and in two-stream graphs, and reads
+        # nothing outside its inputs (tools/coarse_stress.py, tools/coarse_oob.py); the hazard is in
+        # the branch arrangement, whose cause was not pinned down. Cost: C2 ~1 % (486.6 vs 490.9
+        # views/s same box).
+        bb = streams.fork(device, backbone, context["image"], context["intrinsics"], context["extrinsics"],
+                          context["near"], context["far"])
+        da_depth, out_feature = depth_anything(context["image"])
+        trans_features, cnn_features, (dp_cams, adapter_cams) = streams.join(bb)
+        with bench("encoder_4_depth_predictor"), self._dense():
+            begun = self.depth_predictor.begin(trans_features, context["intrinsics"], context["extrinsics"],
+                                               context["near"], context["far"], cnn_features=cnn_features,
+                                               benchmarker=benchmarker, cams=dp_cams)
         dino_feature = out_feature.view(b, v, *out_feature.shape[1:])
 
         extra_info = {"images": rearrange(context["image"], "b v c h w -> (v b) c h w"), "scene_names": scene_names}

@@ -42,8 +42,7 @@ def _conv_gelu_conv(seq: nn.Sequential, x, extra=()):
     Winograd path the concatenation is read in place and bias / GELU are its epilogue)."""
     if not (len(seq) == 3 and isinstance(seq[1], nn.GELU) and seq[1].approximate == "none"):
         return seq(torch.cat([x, *extra], dim=1) if extra else x)
-    return kernels.conv_bias_act(seq[2], kernels.conv_bias_act(seq[0], x, "gelu", site="head", extra=extra),
-                                 site="head")
+    return kernels.conv_bias_act(seq[2], kernels.conv_bias_act(seq[0], x, "gelu", extra=extra))
 
 
 @torch.autocast("cuda", enabled=False)
@@ -226,13 +225,10 @@ class DepthPredictorTrans(nn.Module):
         proj_feat_in_fullres = _conv_upsample_gelu(self.upsampler, torch.cat((feat01, cnn_features), dim=1))
         return proj_feat_in_fullres, self.proj_feature(proj_feat_in_fullres)
 
-    def begin(self, features, intrinsics, extrinsics, near, far, cnn_features=None, benchmarker=None, cams=None,
-              fork_projection=True):
+    def begin(self, features, intrinsics, extrinsics, near, far, cnn_features=None, benchmarker=None, cams=None):
         """The part of forward that reads only the backbone's outputs and the cameras -- 4a's feature
         lists, the full-resolution projection (forked beside the cost volume) and, for two views,
-        the coarse correlation layer -- so that the encoder can run it on the backbone's branch while
-        Depth-Anything is still computing; forward(begun=...) continues from it. fork_projection=False
-        (inside a forked branch, which must not fork again under capture): forward forks it."""
+        the coarse correlation layer; forward(begun=...) continues from it."""
         b, v, c, h, w = features.shape
 
         # the reference's stage tags (depth_predictor_trans.py:320-456) as roctx ranges
@@ -245,14 +241,13 @@ class DepthPredictorTrans(nn.Module):
             feat01 = feat_comb_lists[0]
             # the full-resolution feature projection runs on a side stream beside the cost volume
             # (matching, refine U-Net, depth head: a chain of 64^2 launches), transplat_amd/streams.py
-            proj = (streams.fork(features.device, self._projection, feat01, cnn_features) if fork_projection
-                    else (feat01, cnn_features))
+            proj = streams.fork(features.device, self._projection, feat01, cnn_features)
         coarse = None
         if v == 2:
             with stage(None, "dp_coarse"):  # diagnostic sub-stage mark
                 coarse = self.coarse_two(intr_curr, pose_curr_lists[0], disp_candi_curr, features)
         return {"lists": (intr_curr, pose_curr_lists, disp_candi_curr), "feat01": feat01, "proj": proj,
-                "proj_forked": fork_projection, "coarse": coarse}
+                "coarse": coarse}
 
     def forward(self, features, intrinsics, extrinsics, near, far, gaussians_per_pixel=1, deterministic=True,
                 extra_info=None, cnn_features=None, da_depth=None, dino_feature=None, benchmarker=None, cams=None,
@@ -262,8 +257,6 @@ class DepthPredictorTrans(nn.Module):
             begun = self.begin(features, intrinsics, extrinsics, near, far, cnn_features, benchmarker, cams)
         intr_curr, pose_curr_lists, disp_candi_curr = begun["lists"]
         feat01, proj = begun["feat01"], begun["proj"]
-        if not begun["proj_forked"]:
-            proj = streams.fork(features.device, self._projection, *proj)
         if da_depth is not None:
             da_depth = rearrange(da_depth, "b v ... -> (v b) ...")
         if dino_feature is not None:

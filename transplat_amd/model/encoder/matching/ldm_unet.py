@@ -14,7 +14,6 @@ that follow it in the reference's module chain (kernels.group_norm).
 from __future__ import annotations
 
 import math
-import os
 
 import torch
 import torch.nn.functional as F
@@ -24,7 +23,6 @@ from torch import nn
 from .... import kernels
 
 _ACT_OF = {nn.SiLU: "silu", nn.GELU: "gelu"}
-_GEMM_1X1 = os.environ.get("TSPLAT_UNET_GEMM1X1", "1") != "0"  # A/B knob
 
 
 def gn_act(norm: nn.GroupNorm, x, act: str = "none", residual=None, pre_bias=None):
@@ -32,11 +30,6 @@ def gn_act(norm: nn.GroupNorm, x, act: str = "none", residual=None, pre_bias=Non
     x's dtype (GroupNorm32 semantics: the reference normalises in float and casts back)."""
     y = kernels.group_norm(x, norm.num_groups, norm.weight, norm.bias, norm.eps, act, residual, pre_bias)
     return y.type(x.dtype)
-
-
-# the output blocks' skip concatenation read in place by both ResBlock convolutions in the bf16x3
-# mode (round 6; TSPLAT_UNET_CAT_FREE=0: materialised once, the A/B knob)
-_CAT_FREE = os.environ.get("TSPLAT_UNET_CAT_FREE", "1") == "1"
 
 
 def _direct(conv: nn.Module, x, x2=None, upsample: bool = False) -> bool:
@@ -82,7 +75,7 @@ def conv(conv: nn.Module, x, x2=None, upsample: bool = False, bias: bool = True)
     if isinstance(conv, nn.Conv2d) and kernels.conv3x3_wino_ok(x, conv.weight, conv.stride, conv.padding,
                                                                conv.dilation, conv.groups):
         return kernels.conv3x3_wino(x, conv.weight, b)
-    if (_GEMM_1X1 and isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+    if (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
             and conv.groups == 1
             and conv.padding == (0, 0) and x.is_cuda and x.dtype == torch.float32 and conv.weight.dtype == torch.float32
             and not torch.is_autocast_enabled("cuda")):
@@ -166,10 +159,11 @@ class ResBlock(nn.Module):
                                 else nn.Conv2d(channels, self.out_channels, 1))
 
     def _concat_free(self, x, x2) -> bool:
-        """bf16x3 mode, a Winograd / few-channel in_layers conv: both convolutions read cat([x, x2])
-        in place (the 3x3 as a two-source launch, a 1x1 skip on the two-source direct kernel)."""
+        """bf16x3 mode, a Winograd / few-channel in_layers conv (the output blocks' skip concatenation,
+        round 6): both convolutions read cat([x, x2]) in place (the 3x3 as a two-source launch, a 1x1
+        skip on the two-source direct kernel)."""
         c, sk = self.in_layers[0], self.skip_connection
-        if not (_CAT_FREE and kernels.split_mode() and isinstance(c, nn.Conv2d)
+        if not (kernels.split_mode() and isinstance(c, nn.Conv2d)
                 and kernels.conv3x3_wino_ok(x, c.weight, c.stride, c.padding, c.dilation, c.groups, (x2,))):
             return False
         return isinstance(sk, nn.Identity) or (

@@ -15,8 +15,6 @@ Differences by design (MI355X):
 """
 from __future__ import annotations
 
-import os
-
 import math
 
 import torch
@@ -27,11 +25,6 @@ from ... import kernels
 
 _REF2D: dict = {}  # (h, w, dtype, device) -> [1, h*w, 2] reference points
 _WH: dict = {}     # (w, h, dtype, device) -> tensor([w, h])
-
-
-# the self-attention's projections + sampling glue as two launches (UVSelfAttention.core_raw);
-# TSPLAT_MSDA_RAW=0: the module chain (A/B knob)
-_MSDA_RAW = os.environ.get("TSPLAT_MSDA_RAW", "1") == "1"
 
 
 class UVSelfAttention(nn.Module):
@@ -101,7 +94,7 @@ class UVSelfAttention(nn.Module):
         return kernels.msda_raw(value, ow.view(query.shape[0], query.shape[1], 128), self.num_points, bev_h, bev_w)
 
     def raw_ok(self, query, query_pos) -> bool:
-        return (_MSDA_RAW and query_pos is not None and query.is_cuda and self.embed_dims <= 128
+        return (query_pos is not None and query.is_cuda and self.embed_dims <= 128
                 and 3 * self.num_points <= 128 and query.dtype == torch.float32)
 
     def forward(self, query, value, query_pos, ref_2d, bev_h: int, bev_w: int):
@@ -219,7 +212,7 @@ class UVTransformerEncoderLayer(nn.Module):
 
     def _ln128_ok(self, query) -> bool:
         return (self.embed_dims == 128 and query.is_cuda and torch.is_autocast_enabled(query.device.type)
-                and torch.get_autocast_dtype(query.device.type) == torch.bfloat16 and kernels.BF16_NORMS)
+                and torch.get_autocast_dtype(query.device.type) == torch.bfloat16)
 
     def _fused_ok(self, query) -> bool:
         ffn = self.ffns[0]
