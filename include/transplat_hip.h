@@ -214,6 +214,16 @@ int tsplat_uv_cross_fused_fwd(const void* packed, const float* key, const float*
                               const float* offsets, const float* logits, float* out, int32_t batch,
                               int32_t height, int32_t width, int32_t channels, int32_t depths, int32_t points,
                               void* stream);
+/* The same two with rows that are column ranges of wider buffers: value rows ld_value floats apart
+ * (>= 128, a multiple of 4), a query's offsets / logits rows ld_offsets / ld_logits floats apart
+ * (>= depths * points * 2 / depths * points; multiples of 4 when points == 4) -- the outputs of one
+ * GEMM over concatenated weights read in place. Same kernels, same arithmetic per element. */
+int tsplat_uv_cross_pack_ld_fwd(const float* value, int32_t ld_value, void* packed, int32_t batch, int32_t height,
+                                int32_t width, int32_t channels, void* stream);
+int tsplat_uv_cross_fused_ld_fwd(const void* packed, const float* key, const float* cams, const float* disp,
+                                 const float* offsets, int32_t ld_offsets, const float* logits, int32_t ld_logits,
+                                 float* out, int32_t batch, int32_t height, int32_t width, int32_t channels,
+                                 int32_t depths, int32_t points, void* stream);
 
 /* Single-level single-head multi-scale deformable attention (mmcv ms_deform_attn_forward with
  * num_levels = num_heads = 1): out[i, q] = sum_pt weights[i, q, pt] * bilinear(value[i],
@@ -453,6 +463,20 @@ int tsplat_linear_f32_attn_merge_fwd(const float* partials, int32_t batch, int32
  * cuda_splatting.py:93-96), Gauss-Jordan with partial pivoting, one thread per matrix. */
 int tsplat_small_inverse(const float* in, float* out, int32_t n, int32_t dim, void* stream);
 
+/* The correlation kernels' camera rows in one launch: cams [n, 30] = K^-1 (9, row-major), K (9),
+ * R = pose[:3, :3] (9), t = pose[:3, 3] (3) from intr [n, 3, 3] and pose [n, 4, 4] (fp32, contiguous),
+ * K^-1 by tsplat_small_inverse's arithmetic (the same bits). */
+int tsplat_pack_cameras_fwd(const float* intr, const float* pose, float* cams, int32_t n, void* stream);
+
+/* The squeeze-excite gate of cam_param_encoder (reference src/model/utils/cam_param_encoder.py:45-93)
+ * from the cameras alone: gate [views, 128] = sigmoid(w4 relu(w3 (w2 relu(w1 cam + b1) + b2) + b3) + b4)
+ * with cam [views, 16] (img2world), w1 [128, 16] / b1 = context_mlp.fc1 with the BatchNorm1d folded in,
+ * w2 = fc2, w3 / w4 = context_se.conv_reduce / conv_expand ([128, 128] row-major, 16-B aligned).
+ * Plain fp32 FMAs, one workgroup per view. in_features must be 16 and channels 128. */
+int tsplat_cam_gate_fwd(const float* cam, const float* w1, const float* b1, const float* w2, const float* b2,
+                        const float* w3, const float* b3, const float* w4, const float* b4, float* gate,
+                        int32_t views, int32_t in_features, int32_t channels, void* stream);
+
 /* Dense multi-head self-attention of the DINOv2 ViT-B encoder (exact fp32 MFMA), replacing
  * scaled_dot_product_attention + its permute / transpose copies in Attention.forward (reference
  * src/depth_anything_v2/dinov2_layers/attention.py): qkv [batch, tokens, 3, heads, head_dim] (the
@@ -527,6 +551,14 @@ int tsplat_conv2d_bf16x3_fwd(const float* x1, int32_t c1, const float* x2, int32
                              const float* bias, float* y, int32_t batch, int32_t height, int32_t width,
                              int32_t c_out, int32_t ksize, int32_t stride, int32_t upsample, int32_t ksplit,
                              int32_t zsplit, float* partials, int32_t* counters, void* stream);
+/* The 1x1 / stride-1 case of tsplat_conv2d_bf16x3_fwd on x * scale: scale [batch, c_in] (or NULL) multiplies
+ * every input channel of a sample in fp32 as the value is loaded, before the hi / lo split (the bits of a
+ * separate elementwise x * scale pass), and channel_last = 1 writes y as [batch, height * width, c_out] rows
+ * instead of NCHW (the bits of a permuted copy). w_packed, ksplit, zsplit, partials and counters as there. */
+int tsplat_conv1x1_bf16x3_scaled_fwd(const float* x, int32_t c_in, const float* scale, const void* w_packed,
+                                     const float* bias, float* y, int32_t batch, int32_t height, int32_t width,
+                                     int32_t c_out, int32_t channel_last, int32_t ksplit, int32_t zsplit,
+                                     float* partials, int32_t* counters, void* stream);
 
 /* 3x3 / stride 1 / padding 1 convolution as Winograd F(2x2, 3x3) on exact-fp32 MFMA (replaces the
  * nn.Conv2d(c_in, c_out, 3, 1, 1) calls of the depth predictor's full-resolution heads and U-Net
@@ -660,6 +692,11 @@ size_t tsplat_gemm_x3_pack_bytes(int32_t n, int32_t k);
 int tsplat_gemm_x3_pack(const float* w, void* wp, int32_t n, int32_t k, void* stream);
 int tsplat_gemm_x3_fwd(const float* x, const void* wp, const float* bias, float* out, int32_t m, int32_t n, int32_t k,
                        int32_t ksplit, int32_t act, void* stream);
+/* tsplat_gemm_x3_fwd on x = [x1 | x2] (x1 [m, k1], x2 [m, k2] fp32, rows contiguous, 16-B aligned; wp packed for
+ * k = k1 + k2) without the concatenation in memory: k1 % 64 == 0, so each 64-deep chunk is read from one source
+ * (TSPLAT_EINVAL otherwise); k2 % 4 == 0. The same kernel, the same products in the same order. */
+int tsplat_gemm_x3_cat_fwd(const float* x1, int32_t k1, const float* x2, int32_t k2, const void* wp, const float* bias,
+                           float* out, int32_t m, int32_t n, int32_t ksplit, int32_t act, void* stream);
 
 /* tsplat_residual_ln_fwd with the sub-layer output y given as nslab partial slabs [nslab, rows, dim]
  * (split-K GEMM output, tsplat_gemm_x3_fwd) summed in slab order before the LayerScale multiply. */

@@ -56,6 +56,8 @@ SIGNATURES = {
     "tsplat_uv_cross_pack_bytes": (ctypes.c_size_t, [_I32] * 3),
     "tsplat_uv_cross_pack_fwd": (ctypes.c_int, [_P, _P] + [_I32] * 4 + [_P]),
     "tsplat_uv_cross_fused_fwd": (ctypes.c_int, [_P] * 7 + [_I32] * 6 + [_P]),
+    "tsplat_uv_cross_pack_ld_fwd": (ctypes.c_int, [_P, _I32, _P] + [_I32] * 4 + [_P]),
+    "tsplat_uv_cross_fused_ld_fwd": (ctypes.c_int, [_P] * 5 + [_I32, _P, _I32, _P] + [_I32] * 6 + [_P]),
     "tsplat_msda_fwd": (ctypes.c_int, [_P] * 4 + [_I32] * 6 + [_P]),
     "tsplat_msda_raw_fwd": (ctypes.c_int, [_P, _P, _P] + [_I32] * 6 + [_P]),
     "tsplat_ms_deform_attn_fwd": (ctypes.c_int, [_P] * 6 + [_I32] * 8 + [_P]),
@@ -80,6 +82,8 @@ SIGNATURES = {
     "tsplat_ssim_fwd": (ctypes.c_int, [_P] * 4 + [_I32] * 3 + [_P]),
     "tsplat_raster_cameras": (ctypes.c_int, [_P] * 5 + [_I32] * 3 + [_P] * 7),
     "tsplat_small_inverse": (ctypes.c_int, [_P, _P, _I32, _I32, _P]),
+    "tsplat_pack_cameras_fwd": (ctypes.c_int, [_P, _P, _P, _I32, _P]),
+    "tsplat_cam_gate_fwd": (ctypes.c_int, [_P] * 10 + [_I32] * 3 + [_P]),
     "tsplat_mha_f32_fwd": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, ctypes.c_float, _P]),
     "tsplat_mha_bias_f32_fwd": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, ctypes.c_float, _P]),
     "tsplat_mha_x3_workspace_bytes": (ctypes.c_size_t, [_I32] * 4),
@@ -89,6 +93,7 @@ SIGNATURES = {
     "tsplat_conv2d_f32_fwd": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P] + [_I32] * 8 + [_P]),
     "tsplat_conv2d_f32_zsplit_fwd": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P] + [_I32] * 9 + [_P, _P, _P]),
     "tsplat_conv2d_bf16x3_fwd": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P] + [_I32] * 9 + [_P, _P, _P]),
+    "tsplat_conv1x1_bf16x3_scaled_fwd": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P] + [_I32] * 7 + [_P, _P, _P]),
     "tsplat_resize_bilinear_nhwc_fwd": (ctypes.c_int, [_P, _P] + [_I32] * 6 + [_P]),
     "tsplat_resize_bilinear_nchw_fwd": (ctypes.c_int, [_P, _P] + [_I32] * 5 + [_P]),
     "tsplat_upsample_bilinear_act_fwd": (ctypes.c_int, [_P, _P, _P] + [_I32] * 6 + [_P]),
@@ -98,6 +103,7 @@ SIGNATURES = {
     "tsplat_gemm_x3_pack_bytes": (ctypes.c_size_t, [_I32, _I32]),
     "tsplat_gemm_x3_pack": (ctypes.c_int, [_P, _P, _I32, _I32, _P]),
     "tsplat_gemm_x3_fwd": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "tsplat_gemm_x3_cat_fwd": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P] + [_I32] * 4 + [_P]),
     "tsplat_residual_ln_slabs_bcast_fwd": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P, ctypes.c_float, _P, _P, _I32,
                                                           _I32, _P]),
     "tsplat_da_patches_fwd": (ctypes.c_int, [_P] * 4 + [_I32] * 6 + [_P]),

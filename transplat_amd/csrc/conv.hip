@@ -36,6 +36,8 @@ struct Args {
     const float* wp;    // packed weights [cot][taps][cin/2][2][32]
     const float* bias;  // [cout] or null
     const float* res;   // residual added to the output (y's layout) or null
+    const float* scale; // conv_x3_kernel<.., SC = true>: [n, c1 + c2] factor of every input channel, or null
+    int cl_out;         // conv_x3_kernel<.., SC = true>: y is [n, hout wout, cout] rows
     float* y;           // [n, cout, hout, wout] (NHWC: [n, hout, wout, cout])
     float* part;        // zsplit > 1: [tiles][zsplit][1024] partial tiles
     int* cnt;           // zsplit > 1: [tiles] arrival counters (zero between launches)
@@ -255,7 +257,9 @@ __global__ void __launch_bounds__(1024) conv_f32_kernel(Args p) {
 // fragments, two 16-B loads), splits the 8 values into hi / lo bf16 and issues the 3 MFMAs. Weights
 // packed on the host as [co tile][tap][group][hi, lo][64 lanes][8] bf16 (lane l: cout 32 cot + (l & 31),
 // channels 16 g + 8 (l >> 5) + j; zero past cin / cout). Epilogue as the fp32 kernel's.
-template <int KS, int S, int UP, int NB>
+// SC: the input is x * scale[n][channel] (one fp32 multiply as a value is loaded, before the hi / lo
+// split: the bits of a separate elementwise pass), and y may be channel-last rows (p.cl_out).
+template <int KS, int S, int UP, int NB, bool SC = false>
 __global__ void __launch_bounds__(1024) conv_x3_kernel(Args p) {
     extern __shared__ float sred[];  // [ksplit][16][64]
     constexpr int T = KS * KS, PAD = KS / 2;
@@ -284,6 +288,7 @@ __global__ void __launch_bounds__(1024) conv_x3_kernel(Args p) {
     const int nu = units > gw ? (units - gw + gstride - 1) / gstride : 0;
     const float* x1 = p.x1 + (size_t)nb * p.c1 * hwi;
     const float* x2 = p.x2 ? p.x2 + (size_t)nb * p.c2 * hwi : p.x1;
+    const float* sc = SC && p.scale ? p.scale + (size_t)nb * ci : nullptr;
 
     floatx16 acc;
 #pragma unroll
@@ -318,7 +323,8 @@ __global__ void __launch_bounds__(1024) conv_x3_kernel(Args p) {
                 const int ch = 16 * g + 8 * h + j;
                 const int cc = min(ch, ci - 1);
                 const float* src = cc < p.c1 ? x1 + (size_t)cc * hwi : x2 + (size_t)(cc - p.c1) * hwi;
-                const float v = src[o];
+                float v = src[o];
+                if (SC && sc) v *= sc[cc];
                 const unsigned mb = (ok && tv && ch < ci) ? ~0u : 0u;
                 xv[k][j] = __uint_as_float(__float_as_uint(v) & mb);
             }
@@ -335,6 +341,12 @@ __global__ void __launch_bounds__(1024) conv_x3_kernel(Args p) {
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, bh, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bl, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bh, acc, 0, 0, 0);
+        }
+    }
+    if constexpr (SC) {
+        if (p.cl_out) {
+            tile_epilogue<true>(p, acc, sred);
+            return;
         }
     }
     tile_epilogue<false>(p, acc, sred);
@@ -470,11 +482,13 @@ extern "C" int tsplat_conv2d_f32_nhwc_fwd(const float* x, int32_t c_in, const fl
     return TSPLAT_OK;
 }
 
-extern "C" int tsplat_conv2d_bf16x3_fwd(const float* x1, int32_t c1, const float* x2, int32_t c2,
-                                        const void* w_packed, const float* bias, float* y, int32_t batch,
-                                        int32_t height, int32_t width, int32_t c_out, int32_t ksize, int32_t stride,
-                                        int32_t upsample, int32_t ksplit, int32_t zsplit, float* partials,
-                                        int32_t* counters, void* stream_) {
+// scaled: the 1x1 / stride-1 form with the per-(sample, channel) input factor and the channel-last
+// output option (tsplat_conv1x1_bf16x3_scaled_fwd); otherwise scale / cl_out are unused
+static int conv_x3_launch(const float* x1, int32_t c1, const float* x2, int32_t c2, const void* w_packed,
+                          const float* bias, float* y, int32_t batch, int32_t height, int32_t width, int32_t c_out,
+                          int32_t ksize, int32_t stride, int32_t upsample, int32_t ksplit, int32_t zsplit,
+                          float* partials, int32_t* counters, bool scaled, const float* scale, int32_t cl_out,
+                          void* stream_) {
     using namespace tsplat::conv;
     if (!x1 || !w_packed || !y || batch <= 0 || height <= 0 || width <= 0 || c_out <= 0) return TSPLAT_EINVAL;
     if (zsplit < 1 || zsplit > 64 || (zsplit > 1 && (!partials || !counters))) return TSPLAT_EINVAL;
@@ -492,6 +506,8 @@ extern "C" int tsplat_conv2d_bf16x3_fwd(const float* x1, int32_t c1, const float
     p.wp = (const float*)w_packed;
     p.bias = bias;
     p.y = y;
+    p.scale = scale;
+    p.cl_out = cl_out;
     p.c1 = c1;
     p.c2 = c2;
     p.cout = c_out;
@@ -525,7 +541,12 @@ extern "C" int tsplat_conv2d_bf16x3_fwd(const float* x1, int32_t c1, const float
         else if (nb == 4) hipLaunchKernelGGL((conv_x3_kernel<KS, S, UP, 4>), grid, block, lds, stream, p); \
         else hipLaunchKernelGGL((conv_x3_kernel<KS, S, UP, 2>), grid, block, lds, stream, p);             \
     } while (0)
-    if (ksize == 3 && stride == 1 && !upsample) TSPLAT_X3_LAUNCH(3, 1, 0);
+    if (scaled) {
+        if (nb == 1) hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 1, true>), grid, block, lds, stream, p);
+        else if (nb == 3) hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 3, true>), grid, block, lds, stream, p);
+        else if (nb == 4) hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 4, true>), grid, block, lds, stream, p);
+        else hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 2, true>), grid, block, lds, stream, p);
+    } else if (ksize == 3 && stride == 1 && !upsample) TSPLAT_X3_LAUNCH(3, 1, 0);
     else if (ksize == 3 && stride == 2) TSPLAT_X3_LAUNCH(3, 2, 0);
     else if (ksize == 3) TSPLAT_X3_LAUNCH(3, 1, 1);
     else if (stride == 1) TSPLAT_X3_LAUNCH(1, 1, 0);
@@ -534,4 +555,22 @@ extern "C" int tsplat_conv2d_bf16x3_fwd(const float* x1, int32_t c1, const float
     TSPLAT_PROF_END(tsplat::prof::kConv, stream);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
+}
+
+extern "C" int tsplat_conv2d_bf16x3_fwd(const float* x1, int32_t c1, const float* x2, int32_t c2,
+                                        const void* w_packed, const float* bias, float* y, int32_t batch,
+                                        int32_t height, int32_t width, int32_t c_out, int32_t ksize, int32_t stride,
+                                        int32_t upsample, int32_t ksplit, int32_t zsplit, float* partials,
+                                        int32_t* counters, void* stream_) {
+    return conv_x3_launch(x1, c1, x2, c2, w_packed, bias, y, batch, height, width, c_out, ksize, stride, upsample,
+                          ksplit, zsplit, partials, counters, false, nullptr, 0, stream_);
+}
+
+extern "C" int tsplat_conv1x1_bf16x3_scaled_fwd(const float* x, int32_t c_in, const float* scale, const void* w_packed,
+                                                const float* bias, float* y, int32_t batch, int32_t height,
+                                                int32_t width, int32_t c_out, int32_t channel_last, int32_t ksplit,
+                                                int32_t zsplit, float* partials, int32_t* counters, void* stream_) {
+    if (channel_last != 0 && channel_last != 1) return TSPLAT_EINVAL;
+    return conv_x3_launch(x, c_in, nullptr, 0, w_packed, bias, y, batch, height, width, c_out, 1, 1, 0, ksplit, zsplit,
+                          partials, counters, true, scale, channel_last, stream_);
 }

@@ -120,7 +120,9 @@ __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ w, 
 }
 
 struct Args {
-    const float* x;    // [m][k] fp32, rows contiguous
+    const float* x;    // [m][k] fp32, rows contiguous (CAT: [m][k1], the first k1 columns)
+    const float* x2;   // CAT: [m][k - k1], the columns from k1 on
+    int k1;            // CAT: a multiple of kBK, so every chunk comes from one source
     const uint4* w;    // packed W
     const float* bias; // [n] or null
     float* out;        // [ksplit][m][n]
@@ -133,6 +135,9 @@ struct Args {
     int mb, nb;        // row / column blocks
 };
 
+// CAT: x is [x | x2] along k without the concatenation in memory (per-chunk source select, as
+// linear.hip's stage_load); the products and their order are those of the materialised rows
+template <bool CAT>
 __global__ void __launch_bounds__(kThreads, 2 / KG) gemm_x3_kernel(Args a) {
     __shared__ __attribute__((aligned(16))) uint32_t smem[kSmemDw];
     // XCD-aware order: logical = (column block, split, row block) with the row block fastest; each XCD
@@ -158,12 +163,14 @@ __global__ void __launch_bounds__(kThreads, 2 / KG) gemm_x3_kernel(Args a) {
     const int st = c4 >> 2, sh = (c4 >> 1) & 1, jh = c4 & 1;
     int xoff[kXr];  // dword offset of this thread's hi pair in a buffer (lo at + kLoDw)
     const float* xrow[kXr];
+    const float* xrow2[kXr];  // CAT: the same rows of x2, offset so that column k1 of [x | x2] is its column 0
     bool rok[kXr];
 #pragma unroll
     for (int i = 0; i < kXr; ++i) {
         const int r = r0 + 16 * KG * i, gm = mbk * kBM + r;
         rok[i] = gm < a.m;
-        xrow[i] = a.x + (size_t)(rok[i] ? gm : 0) * a.k + 4 * c4;
+        xrow[i] = a.x + (size_t)(rok[i] ? gm : 0) * (CAT ? a.k1 : a.k) + 4 * c4;
+        if constexpr (CAT) xrow2[i] = a.x2 + (size_t)(rok[i] ? gm : 0) * (a.k - a.k1) + 4 * c4 - a.k1;
         const int slot = ((r & 31) + 32 * sh) ^ (2 * st + sh);
         xoff[i] = ((st * 2 + (r >> 5)) * 64 + slot) * 4 + 2 * jh;
     }
@@ -185,7 +192,8 @@ __global__ void __launch_bounds__(kThreads, 2 / KG) gemm_x3_kernel(Args a) {
         const bool kok = c * kBK + 4 * c4 < a.k;
 #pragma unroll
         for (int i = 0; i < kXr; ++i) {
-            const float* p = rok[i] && kok ? xrow[i] + c * kBK : reinterpret_cast<const float*>(&g_zero16);
+            const float* row = CAT && c * kBK >= a.k1 ? xrow2[i] : xrow[i];
+            const float* p = rok[i] && kok ? row + c * kBK : reinterpret_cast<const float*>(&g_zero16);
             const floatx4 v = *(gptr)p;
             xr[decltype(X)::value][i] = make_float4(v.x, v.y, v.z, v.w);
         }
@@ -388,16 +396,20 @@ extern "C" int tsplat_gemm_x3_pack(const float* w, void* wp, int32_t n, int32_t 
     return TSPLAT_OK;
 }
 
-extern "C" int tsplat_gemm_x3_fwd(const float* x, const void* wp, const float* bias, float* out, int32_t m, int32_t n,
-                                  int32_t k, int32_t ksplit, int32_t act, void* stream_) {
+// x2 null: x [m][k]; else [x | x2] with x [m][k1] and x2 [m][k - k1]
+static int gemm_x3_launch(const float* x, int k1, const float* x2, const void* wp, const float* bias, float* out, int m,
+                          int n, int k, int ksplit, int act, void* stream_) {
     if (!x || !wp || !out || m <= 0 || n <= 0 || k <= 0 || ksplit <= 0) return TSPLAT_EINVAL;
     // float4 rows: k and n multiples of 4, x / bias / out 16-B aligned
     if (k % 4 || n % 4 || ((uintptr_t)x & 15) || ((uintptr_t)out & 15) || (bias && ((uintptr_t)bias & 15)))
         return TSPLAT_EINVAL;
+    if (x2 && (k1 <= 0 || k1 >= k || k1 % kBK || ((uintptr_t)x2 & 15))) return TSPLAT_EINVAL;
     if (act < 0 || act > 2) return TSPLAT_EINVAL;
     if (act && ksplit > 1) return TSPLAT_EINVAL;  // the activation needs the whole sum
     Args a{};
     a.x = x;
+    a.x2 = x2;
+    a.k1 = x2 ? k1 : k;
     a.w = (const uint4*)wp;
     a.bias = bias;
     a.out = out;
@@ -416,8 +428,23 @@ extern "C" int tsplat_gemm_x3_fwd(const float* x, const void* wp, const float* b
     const long long grid = (long long)a.mb * a.nb * ksplit;
     if (grid > 0x7fffffff) return TSPLAT_EINVAL;
     TSPLAT_PROF_BEGIN(tsplat::prof::kGemmX3, (hipStream_t)stream_);
-    hipLaunchKernelGGL(gemm_x3_kernel, dim3((unsigned)grid), dim3(kThreads), 0, (hipStream_t)stream_, a);
+    if (x2)
+        hipLaunchKernelGGL(gemm_x3_kernel<true>, dim3((unsigned)grid), dim3(kThreads), 0, (hipStream_t)stream_, a);
+    else
+        hipLaunchKernelGGL(gemm_x3_kernel<false>, dim3((unsigned)grid), dim3(kThreads), 0, (hipStream_t)stream_, a);
     TSPLAT_PROF_END(tsplat::prof::kGemmX3, (hipStream_t)stream_);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
+}
+
+extern "C" int tsplat_gemm_x3_fwd(const float* x, const void* wp, const float* bias, float* out, int32_t m, int32_t n,
+                                  int32_t k, int32_t ksplit, int32_t act, void* stream_) {
+    return gemm_x3_launch(x, 0, nullptr, wp, bias, out, m, n, k, ksplit, act, stream_);
+}
+
+extern "C" int tsplat_gemm_x3_cat_fwd(const float* x1, int32_t k1, const float* x2, int32_t k2, const void* wp,
+                                      const float* bias, float* out, int32_t m, int32_t n, int32_t ksplit,
+                                      int32_t act, void* stream_) {
+    if (!x2 || k1 <= 0 || k2 <= 0 || k1 % kBK || k2 % 4) return TSPLAT_EINVAL;
+    return gemm_x3_launch(x1, k1, x2, wp, bias, out, m, n, k1 + k2, ksplit, act, stream_);
 }

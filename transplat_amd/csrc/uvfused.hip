@@ -61,17 +61,18 @@ __device__ __forceinline__ void split8(floatx4 a, floatx4 b, uint4& hi, uint4& l
     lo = make_uint4(l0.x, l0.y, l1.x, l1.y);
 }
 
-// value [maps, HW, 128] fp32 -> the packed B-fragment image (see the head of the file). One thread
-// per (padded pixel, 8-channel unit): 16 consecutive threads read one 512-B feature row.
+// value [maps, HW, 128] fp32 (rows ldv floats apart) -> the packed B-fragment image (see the head of
+// the file). One thread per (padded pixel, 8-channel unit): 16 consecutive threads read one 512-B
+// feature row.
 __global__ void __launch_bounds__(256)
-uv_cross_pack_kernel(const float* __restrict__ value, uint4* __restrict__ packed, int maps, int hw, int tiles) {
+uv_cross_pack_kernel(const float* __restrict__ value, int ldv, uint4* __restrict__ packed, int maps, int hw, int tiles) {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (size_t)maps * tiles * 32 * 16) return;
     const int u = (int)(t & 15);
     const size_t pp = t >> 4;  // padded pixel index over all maps
     const int map = (int)(pp / ((size_t)tiles * 32));
     const int pix = (int)(pp - (size_t)map * tiles * 32);
-    const float4* src = pix < hw ? reinterpret_cast<const float4*>(value + ((size_t)map * hw + pix) * kC + 8 * u)
+    const float4* src = pix < hw ? reinterpret_cast<const float4*>(value + ((size_t)map * hw + pix) * ldv + 8 * u)
                                  : g_zero32;
     const float4 a = src[0], b = src[1];
     uint4 hi, lo;
@@ -167,7 +168,8 @@ template <int PMAX>
 __global__ void __launch_bounds__(kFThreads)
 uv_cross_fused_kernel(Geo g, int P, const uint4* __restrict__ vpack, const float* __restrict__ key,
                       const float* __restrict__ cams, const float* __restrict__ disp,
-                      const float* __restrict__ offsets, const float* __restrict__ logits, float* __restrict__ out) {
+                      const float* __restrict__ offsets, int ld_off, const float* __restrict__ logits, int ld_lg,
+                      float* __restrict__ out) {
     constexpr int NPAIR = 32 / PMAX;                   // pairs per thread
     constexpr int kDChunk = NPAIR * kFThreads / kQ;    // depth candidates per pass over the bands
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -218,9 +220,10 @@ uv_cross_fused_kernel(Geo g, int P, const uint4* __restrict__ vpack, const float
             for (int j = 0; j < NPAIR; ++j) {
                 const int i = tid + kFThreads * j, q = i / dn, p = q0 + q;
                 const bool ok = i < pairs && p < HW;
-                // pairs past the block read pair 0 of the map (always there) and are dropped below
-                const size_t flat = ok ? ((size_t)n * HW + p) * g.D + d0 + (i - q * dn) : (size_t)n * HW * g.D;
-                load_pair<PMAX>(P, offsets + flat * P * 2, logits + flat * P, raw[j]);
+                // pairs past the block read pair 0 of the map (always there) and are dropped below;
+                // a query's rows of offsets / logits lie ld_off / ld_lg floats apart
+                const size_t row = (size_t)n * HW + (ok ? p : 0), dd = ok ? d0 + (i - q * dn) : 0;
+                load_pair<PMAX>(P, offsets + row * ld_off + dd * P * 2, logits + row * ld_lg + dd * P, raw[j]);
                 dv[j] = dsp[ok ? d0 + (i - q * dn) : 0];
             }
 #pragma unroll
@@ -339,30 +342,40 @@ extern "C" size_t tsplat_uv_cross_pack_bytes(int32_t batch, int32_t height, int3
     return (size_t)2 * batch * ceil_div((size_t)height * width, (size_t)32) * corr::kTileU4 * 16;
 }
 
-extern "C" int tsplat_uv_cross_pack_fwd(const float* value, void* packed, int32_t batch, int32_t height,
-                                        int32_t width, int32_t channels, void* stream_) {
+extern "C" int tsplat_uv_cross_pack_ld_fwd(const float* value, int32_t ld_value, void* packed, int32_t batch,
+                                           int32_t height, int32_t width, int32_t channels, void* stream_) {
     using namespace tsplat::corr;
-    if (!value || !packed || channels != kC || batch <= 0 || height <= 1 || width <= 1 ||
-        (size_t)height * width > (size_t)1 << 24 || (uintptr_t)value % 16 || (uintptr_t)packed % 16)
+    if (!value || !packed || channels != kC || batch <= 0 || height <= 1 || width <= 1 || ld_value < kC ||
+        ld_value % 4 || (size_t)height * width > (size_t)1 << 24 || (uintptr_t)value % 16 || (uintptr_t)packed % 16)
         return TSPLAT_EINVAL;
     const int hw = height * width, tiles = ceil_div(hw, 32), maps = 2 * batch;
     const size_t work = (size_t)maps * tiles * 32 * 16;
     hipLaunchKernelGGL(uv_cross_pack_kernel, dim3((unsigned)ceil_div(work, (size_t)256)), dim3(256), 0,
-                       (hipStream_t)stream_, value, (uint4*)packed, maps, hw, tiles);
+                       (hipStream_t)stream_, value, ld_value, (uint4*)packed, maps, hw, tiles);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
 }
 
-extern "C" int tsplat_uv_cross_fused_fwd(const void* packed, const float* key, const float* cams, const float* disp,
-                                         const float* offsets, const float* logits, float* out, int32_t batch,
-                                         int32_t height, int32_t width, int32_t channels, int32_t depths,
-                                         int32_t points, void* stream_) {
+extern "C" int tsplat_uv_cross_pack_fwd(const float* value, void* packed, int32_t batch, int32_t height,
+                                        int32_t width, int32_t channels, void* stream_) {
+    return tsplat_uv_cross_pack_ld_fwd(value, tsplat::corr::kC, packed, batch, height, width, channels, stream_);
+}
+
+extern "C" int tsplat_uv_cross_fused_ld_fwd(const void* packed, const float* key, const float* cams,
+                                            const float* disp, const float* offsets, int32_t ld_offsets,
+                                            const float* logits, int32_t ld_logits, float* out, int32_t batch,
+                                            int32_t height, int32_t width, int32_t channels, int32_t depths,
+                                            int32_t points, void* stream_) {
     using namespace tsplat::corr;
     if (!packed || !key || !cams || !disp || !offsets || !logits || !out || channels != kC || batch <= 0 ||
         height <= 1 || width <= 1 || depths <= 0 || points <= 0 || points > kMaxPoints ||
         (size_t)height * width > (size_t)1 << 24 || 2 * batch > 65535 ||
         (size_t)2 * batch * height * width * depths * points > (size_t)1 << 40 ||
         (uintptr_t)packed % 16 || (uintptr_t)key % 16 || (uintptr_t)offsets % 16 || (uintptr_t)logits % 16)
+        return TSPLAT_EINVAL;
+    // rows hold at least the depths x points entries; the 4-point kernel reads them as float4
+    if ((int64_t)ld_offsets < (int64_t)depths * points * 2 || (int64_t)ld_logits < (int64_t)depths * points ||
+        (points == 4 && (ld_offsets % 4 || ld_logits % 4)))
         return TSPLAT_EINVAL;
     Geo g{batch, height, width, depths};
     hipStream_t stream = (hipStream_t)stream_;
@@ -376,13 +389,23 @@ extern "C" int tsplat_uv_cross_fused_fwd(const void* packed, const float* key, c
     TSPLAT_PROF_BEGIN(prof::kUvCross, stream);
     if (points <= 4)
         hipLaunchKernelGGL(uv_cross_fused_kernel<4>, grid, dim3(kFThreads), kFusedLds, stream, g, points,
-                           (const uint4*)packed, key, cams, disp, offsets, logits, out);
+                           (const uint4*)packed, key, cams, disp, offsets, ld_offsets, logits, ld_logits, out);
     else
         hipLaunchKernelGGL(uv_cross_fused_kernel<8>, grid, dim3(kFThreads), kFusedLds, stream, g, points,
-                           (const uint4*)packed, key, cams, disp, offsets, logits, out);
+                           (const uint4*)packed, key, cams, disp, offsets, ld_offsets, logits, ld_logits, out);
     TSPLAT_PROF_END(prof::kUvCross, stream);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
+}
+
+extern "C" int tsplat_uv_cross_fused_fwd(const void* packed, const float* key, const float* cams, const float* disp,
+                                         const float* offsets, const float* logits, float* out, int32_t batch,
+                                         int32_t height, int32_t width, int32_t channels, int32_t depths,
+                                         int32_t points, void* stream_) {
+    if (depths <= 0 || depths > (1 << 24) || points <= 0 || points > tsplat::corr::kMaxPoints) return TSPLAT_EINVAL;
+    // contiguous rows; with 4 points depths * 4 and depths * 8 floats keep every row 16-byte aligned
+    return tsplat_uv_cross_fused_ld_fwd(packed, key, cams, disp, offsets, depths * points * 2, logits,
+                                        depths * points, out, batch, height, width, channels, depths, points, stream_);
 }
 
 #if TSPLAT_UVX_DIAG

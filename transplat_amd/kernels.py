@@ -77,6 +77,62 @@ def pack_cameras(intr: torch.Tensor, pose: torch.Tensor) -> torch.Tensor:
          pose[:, :3, 3].float()], dim=1).contiguous()
 
 
+def pack_cameras_fused(intr: torch.Tensor, pose: torch.Tensor) -> torch.Tensor:
+    """pack_cameras(intr, pose) of device tensors as one launch (tsplat_pack_cameras_fwd; the same
+    bits). It depends on the cameras only: the depth predictor's camera prep computes it once per
+    step and hands it to uv_coarse / uv_cross as cams_packed."""
+    lib = _lib.load()
+    intr, pose = _f32(intr).reshape(-1, 3, 3), _f32(pose).reshape(-1, 4, 4)
+    n = intr.shape[0]
+    if pose.shape[0] != n:
+        raise ValueError(f"{n} intrinsics for {pose.shape[0]} poses")
+    out = torch.empty((n, 30), dtype=torch.float32, device=intr.device)
+    _lib.check(lib.tsplat_pack_cameras_fwd(_lib.ptr(intr), _lib.ptr(pose), _lib.ptr(out), n, _lib.stream_ptr(intr.device)),
+               "tsplat_pack_cameras_fwd")
+    return out
+
+
+def _cams(intr, pose, cams_packed):
+    """The [N, 30] camera rows of a correlation call: the ones handed in, else pack_cameras."""
+    if cams_packed is None:
+        return pack_cameras(intr, pose)
+    if tuple(cams_packed.shape) != (intr.shape[0], 30) or cams_packed.dtype != torch.float32:
+        raise ValueError(f"cams_packed {tuple(cams_packed.shape)} for {intr.shape[0]} cameras")
+    return cams_packed.contiguous()
+
+
+def cam_gate(cam, w1, b1, w2, b2, w3, b3, w4, b4):
+    """sigmoid(w4 relu(w3 (w2 relu(w1 cam + b1) + b2) + b3) + b4): cam [views, 16] -> [views, 128], the
+    camera-parameter encoder's squeeze-excite gate in one launch (tsplat_cam_gate_fwd, plain fp32)."""
+    lib = _lib.load()
+    cam = _f32(cam)
+    views, k = cam.shape
+    c = w2.shape[0]
+    ws = [_f32(t.reshape(t.shape[0], -1)) for t in (w1, w2, w3, w4)]
+    bs = [_f32(t) for t in (b1, b2, b3, b4)]
+    if [tuple(t.shape) for t in ws] != [(c, k), (c, c), (c, c), (c, c)] or any(tuple(t.shape) != (c,) for t in bs):
+        raise ValueError("cam_gate: weights do not form a k -> c -> c -> c -> c chain")
+    out = torch.empty((views, c), dtype=torch.float32, device=cam.device)
+    _lib.check(lib.tsplat_cam_gate_fwd(_lib.ptr(cam), _lib.ptr(ws[0]), _lib.ptr(bs[0]), _lib.ptr(ws[1]), _lib.ptr(bs[1]),
+                                       _lib.ptr(ws[2]), _lib.ptr(bs[2]), _lib.ptr(ws[3]), _lib.ptr(bs[3]), _lib.ptr(out),
+                                       views, k, c, _lib.stream_ptr(cam.device)), "tsplat_cam_gate_fwd")
+    return out
+
+
+def _rows(t: torch.Tensor):
+    """(tensor, row stride in floats) of t [..., n] for a kernel that takes rows a fixed distance apart:
+    t itself where it is such a view of a wider fp32 buffer (a column range of a GEMM output: unit
+    stride along the last axis, every row the same 16-byte-aligned distance from the previous one),
+    else its contiguous fp32 copy."""
+    if t.dtype == torch.float32 and t.dim() >= 2 and t.stride(-1) == 1 and not t.is_contiguous():
+        ld = t.stride(-2)
+        uniform = all(t.shape[i] == 1 or t.stride(i) == t.stride(i + 1) * t.shape[i + 1] for i in range(t.dim() - 2))
+        if uniform and ld >= t.shape[-1] and ld % 4 == 0 and t.data_ptr() % 16 == 0:
+            return t, ld
+    t = _f32(t)
+    return t, t.shape[-1]
+
+
 def _win_attn_workspace_bytes(lib, family: str, b: int, h: int, w: int, m: int, num_splits: int) -> int:
     """Bytes of split-key partials the window attention of `family` ("fp32", "bf16" or "x3") writes for
     this launch shape (0: no key split). The bf16x3 kernels share the exact-fp32 kernels' plan."""
@@ -119,13 +175,14 @@ def window_attention(q, k, v, h: int, w: int, num_splits: int, with_shift: bool,
     return out
 
 
-def uv_coarse(feat, intr, pose, disp, h: int, w: int):
-    """Coarse correlation volume. feat [B, 2, HW, C] -> [B*2, HW, D] (see oracle.uv_coarse)."""
+def uv_coarse(feat, intr, pose, disp, h: int, w: int, *, cams_packed=None):
+    """Coarse correlation volume. feat [B, 2, HW, C] -> [B*2, HW, D] (see oracle.uv_coarse).
+    cams_packed: pack_cameras(intr, pose) where the caller already has it."""
     lib = _lib.load()
     b, _, hw, c = feat.shape
     d = disp.shape[1]
     feat = _f32(feat)
-    cams = pack_cameras(intr, pose)
+    cams = _cams(intr, pose, cams_packed)
     disp = _f32(disp)
     out = torch.empty((b * 2, hw, d), dtype=torch.float32, device=feat.device)
     rc = lib.tsplat_uv_coarse_fwd(_lib.ptr(feat), _lib.ptr(cams), _lib.ptr(disp), _lib.ptr(out), b, h, w,
@@ -134,9 +191,10 @@ def uv_coarse(feat, intr, pose, disp, h: int, w: int):
     return out
 
 
-def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
+def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int, *, cams_packed=None):
     """Fine cross correlation. value, key [B, 2, HW, C]; offsets [B*2, HW, D*P*2];
-    logits [B*2, HW, D*P] -> [B*2, HW, D] (see oracle.uv_cross).
+    logits [B*2, HW, D*P] -> [B*2, HW, D] (see oracle.uv_cross). cams_packed: pack_cameras(intr,
+    pose) where the caller already has it.
 
     Two steps: the correlation table G[(b v)] = key_v value_(1-v)^T [HW, HW] as one batched
     fp32 library GEMM (hipBLASLt, MFMA; autocast off so it stays fp32), then
@@ -161,7 +219,7 @@ def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
         key, offsets, logits, disp = map(_f32, (key, offsets, logits, disp))
     elif _DENSE == "bf16x3" and value.is_cuda and c == 128 and _UV_FUSED:
         # bf16x3 dense mode: the same split-bf16 products computed and gathered on chip, no table
-        return uv_cross_fused(value, key, intr, pose, disp, offsets, logits, h, w)
+        return uv_cross_fused(value, key, intr, pose, disp, offsets, logits, h, w, cams_packed=cams_packed)
     elif _DENSE == "bf16x3" and value.is_cuda and c % 4 == 0:
         # _UV_FUSED off (or C != 128): the table in split-bf16 precision as ONE hipBLASLt bf16 GEMM with K = 3C,
         # [key_hi | key_hi | key_lo] x [val_hi | val_lo | val_hi]^T, fp32 output (47 vs 83 us for the
@@ -177,7 +235,7 @@ def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
         with torch.autocast("cuda", enabled=False):
             table = torch.bmm(key.reshape(b * 2, hw, c),
                               torch.flip(value, dims=[1]).reshape(b * 2, hw, c).transpose(1, 2))
-    cams = pack_cameras(intr, pose)
+    cams = _cams(intr, pose, cams_packed)
     out = torch.empty((b * 2, hw, d), dtype=torch.float32, device=table.device)
     rc = lib.tsplat_uv_cross_table_fwd(_lib.ptr(table), _lib.ptr(cams), _lib.ptr(disp), _lib.ptr(offsets),
                                        _lib.ptr(logits), _lib.ptr(out), b, h, w, c, d, p, _lib.stream_ptr(table.device))
@@ -185,25 +243,38 @@ def uv_cross(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
     return out
 
 
-def uv_cross_fused(value, key, intr, pose, disp, offsets, logits, h: int, w: int):
+def uv_cross_fused(value, key, intr, pose, disp, offsets, logits, h: int, w: int, *, cams_packed=None):
     """uv_cross in split-bf16 precision without the [HW, HW] table: tsplat_uv_cross_pack_fwd splits
     value of both views into the MFMA operand image (one launch, in place of the flip and the two
     splits), tsplat_uv_cross_fused_fwd computes each 32-query block's slices of the table in LDS
-    and gathers there, skipping the slices nobody samples. C = 128."""
+    and gathers there, skipping the slices nobody samples. C = 128. value, offsets and logits may be
+    column ranges of wider row-major buffers (one GEMM over concatenated weights): the _ld entry
+    points read them in place."""
     lib = _lib.load()
     b, _, hw, c = value.shape
     d = disp.shape[1]
     p = logits.shape[-1] // d
-    value, key, offsets, logits, disp = map(_f32, (value, key, offsets, logits, disp))
-    cams = pack_cameras(intr, pose)
+    key, disp = _f32(key), _f32(disp)
+    (value, ldv), (offsets, ldo), (logits, ldl) = _rows(value), _rows(offsets), _rows(logits)
+    cams = _cams(intr, pose, cams_packed)
     packed = torch.empty(int(lib.tsplat_uv_cross_pack_bytes(b, h, w)), dtype=torch.uint8, device=value.device)
     stream = _lib.stream_ptr(value.device)
-    _lib.check(lib.tsplat_uv_cross_pack_fwd(_lib.ptr(value), _lib.ptr(packed), b, h, w, c, stream),
-               "tsplat_uv_cross_pack_fwd")
+    if ldv == c:
+        _lib.check(lib.tsplat_uv_cross_pack_fwd(_lib.ptr(value), _lib.ptr(packed), b, h, w, c, stream),
+                   "tsplat_uv_cross_pack_fwd")
+    else:
+        _lib.check(lib.tsplat_uv_cross_pack_ld_fwd(_lib.ptr(value), ldv, _lib.ptr(packed), b, h, w, c, stream),
+                   "tsplat_uv_cross_pack_ld_fwd")
     out = torch.empty((b * 2, hw, d), dtype=torch.float32, device=value.device)
-    rc = lib.tsplat_uv_cross_fused_fwd(_lib.ptr(packed), _lib.ptr(key), _lib.ptr(cams), _lib.ptr(disp),
-                                       _lib.ptr(offsets), _lib.ptr(logits), _lib.ptr(out), b, h, w, c, d, p, stream)
-    _lib.check(rc, "tsplat_uv_cross_fused_fwd")
+    if ldo == offsets.shape[-1] and ldl == logits.shape[-1]:
+        rc = lib.tsplat_uv_cross_fused_fwd(_lib.ptr(packed), _lib.ptr(key), _lib.ptr(cams), _lib.ptr(disp),
+                                           _lib.ptr(offsets), _lib.ptr(logits), _lib.ptr(out), b, h, w, c, d, p, stream)
+        _lib.check(rc, "tsplat_uv_cross_fused_fwd")
+    else:
+        rc = lib.tsplat_uv_cross_fused_ld_fwd(_lib.ptr(packed), _lib.ptr(key), _lib.ptr(cams), _lib.ptr(disp),
+                                              _lib.ptr(offsets), ldo, _lib.ptr(logits), ldl, _lib.ptr(out), b, h, w, c,
+                                              d, p, stream)
+        _lib.check(rc, "tsplat_uv_cross_fused_ld_fwd")
     return out
 
 
@@ -960,6 +1031,41 @@ def _conv2d_direct_x3(lib, a, b, c1, c2, weight, bias, n, h, w, co, k, stride, u
     return y
 
 
+def conv1x1_scaled_ok(x, weight) -> bool:
+    """True when conv1x1_scaled takes conv2d(x * scale, weight): the bf16x3 dense mode's 1x1 / stride-1
+    convolutions that conv2d_forward runs on tsplat_conv2d_bf16x3_fwd (the same launch plan, so the
+    same bits)."""
+    return (split_mode() and weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1) and x.is_contiguous()
+            and conv2d_direct_ok(x, weight, 1, 0) and conv_x3_wins(x.shape[0] * x.shape[2] * x.shape[3],
+                                                                     x.shape[1], weight.shape[0], 1))
+
+
+def conv1x1_scaled(x, scale, weight, bias=None, channel_last: bool = False):
+    """conv2d(x * scale[:, :, None, None], weight, bias) for a 1x1 weight in one launch
+    (tsplat_conv1x1_bf16x3_scaled_fwd): scale [n, c_in] multiplies the input as it is loaded;
+    channel_last returns the [n, h w, c_out] rows of the result instead of NCHW. Bit-identical to
+    the multiply, conv2d_direct and permuted copy it replaces (see conv1x1_scaled_ok)."""
+    lib = _lib.load()
+    n, ci, h, w = x.shape
+    co = weight.shape[0]
+    a, sc = _f32(x), _f32(scale)
+    if tuple(sc.shape) != (n, ci) or weight.shape[1] != ci:
+        raise ValueError(f"scale {tuple(sc.shape)} / weight {tuple(weight.shape)} do not match x {tuple(x.shape)}")
+    y = torch.empty((n, h * w, co) if channel_last else (n, co, h, w), dtype=torch.float32, device=x.device)
+    tiles = ((n * h * w + 31) // 32) * ((co + 31) // 32)
+    ksplit, z = _conv_x3_shape(tiles, (ci + 15) // 16)
+    part = cnt = None
+    if z > 1:
+        part = torch.empty(tiles * z * 1024, dtype=torch.float32, device=y.device)
+        cnt = _zsplit_counters(y.device, tiles)
+    pb = _f32(bias) if bias is not None else None
+    rc = lib.tsplat_conv1x1_bf16x3_scaled_fwd(_lib.ptr(a), ci, _lib.ptr(sc), _lib.ptr(conv_pack_weight_x3(weight)),
+                                              _lib.ptr(pb), _lib.ptr(y), n, h, w, co, int(channel_last), ksplit, z,
+                                              _lib.ptr(part), _lib.ptr(cnt), _lib.stream_ptr(y.device))
+    _lib.check(rc, "tsplat_conv1x1_bf16x3_scaled_fwd")
+    return y
+
+
 def conv2d_direct(x1, weight, bias=None, stride: int = 1, x2=None, upsample: bool = False):
     """conv2d(cat([x1, x2], 1) (nearest-upsampled 2x if upsample), weight, bias, stride,
     padding = k // 2) in one MFMA launch, NCHW fp32: exact fp32 (tsplat_conv2d_f32_zsplit_fwd), or
@@ -1351,6 +1457,13 @@ def gemm_x3_ok(x, weight) -> bool:
     return k % 4 == 0 and n % 4 == 0 and x.shape[-1] == k
 
 
+def gemm_x3_takes(x, weight) -> bool:
+    """True when linear_forward runs F.linear(x, weight) on gemm_x3 (gemm_x3_ok and at least 64 rows):
+    where several nn.Linear modules read the same rows, one gemm_x3 over their concatenated weights
+    then computes the same bits column for column."""
+    return gemm_x3_ok(x, weight) and x.numel() // x.shape[-1] >= 64
+
+
 def _pack_gemm(weight):
     lib = _lib.load()
     n = weight.shape[0]
@@ -1379,15 +1492,26 @@ def gemm_ksplit(m: int, n: int, k: int) -> int:
     return s
 
 
-def gemm_x3(x, weight, bias=None, act: str = "none", ksplit: int = 1):
+# gemm_x3(x, ..., x2=...) reads [x | x2] in place (tsplat_gemm_x3_cat_fwd); False = the concatenation
+# materialised first (A/B scripts set it)
+_GEMM_CAT = True
+
+
+def gemm_x3(x, weight, bias=None, act: str = "none", ksplit: int = 1, x2=None):
     """act(x W^T + bias) on the split-bf16 GEMM (tsplat_gemm_x3_fwd); ksplit > 1 returns the [ksplit,
     *x.shape[:-1], n] partial slabs (bias in slab 0) for residual_ln to sum; ksplit 0: gemm_ksplit's
-    choice (1 with an activation). weight [n, k] or [n, ...] (see gemm_x3_ok)."""
+    choice (1 with an activation). weight [n, k] or [n, ...] (see gemm_x3_ok). x2: the rows are
+    [x | x2] along the last axis, read in place when x's width is a multiple of 64
+    (tsplat_gemm_x3_cat_fwd, the same bits), else concatenated first."""
     lib = _lib.load()
     n = weight.shape[0]
     k = weight.numel() // n
+    k1 = x.shape[-1]
+    if x2 is not None and not (_GEMM_CAT and k1 % 64 == 0 and x2.shape[:-1] == x.shape[:-1]):
+        x, x2 = torch.cat([x, x2], dim=-1), None
     xf = _f32(x)
-    m = xf.numel() // k
+    x2f = _f32(x2) if x2 is not None else None
+    m = xf.numel() // (k1 if x2 is not None else k)
     if ksplit == 0:
         ksplit = 1 if act != "none" else gemm_ksplit(m, n, k)
     if act == "split":  # [2, *x.shape[:-1], n] bf16: hi and lo images (x W^T + bias = hi + lo)
@@ -1399,8 +1523,14 @@ def gemm_x3(x, weight, bias=None, act: str = "none", ksplit: int = 1):
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
     if GEMM_LOG is not None:
         GEMM_LOG.append((m, n, k, ksplit))
-    rc = lib.tsplat_gemm_x3_fwd(_lib.ptr(xf), _lib.ptr(_gemm_pack(weight)), _lib.ptr(_f32(bias)) if bias is not None else None,
-                                _lib.ptr(out), m, n, k, ksplit, {"none": 0, "gelu": 1, "split": 2}[act],
+    pb = _lib.ptr(_f32(bias)) if bias is not None else None
+    acti = {"none": 0, "gelu": 1, "split": 2}[act]
+    if x2f is not None:
+        rc = lib.tsplat_gemm_x3_cat_fwd(_lib.ptr(xf), k1, _lib.ptr(x2f), k - k1, _lib.ptr(_gemm_pack(weight)), pb,
+                                        _lib.ptr(out), m, n, ksplit, acti, _lib.stream_ptr(x.device))
+        _lib.check(rc, "tsplat_gemm_x3_cat_fwd", "bf16x3")
+        return out
+    rc = lib.tsplat_gemm_x3_fwd(_lib.ptr(xf), _lib.ptr(_gemm_pack(weight)), pb, _lib.ptr(out), m, n, k, ksplit, acti,
                                 _lib.stream_ptr(x.device))
     _lib.check(rc, "tsplat_gemm_x3_fwd", "bf16x3")
     return out
@@ -1412,7 +1542,7 @@ def linear_forward(mod, x):
     F.linear below 64 rows); everything else is F.linear."""
     if linear_xf32_ok(x, mod.weight):
         return linear_xf32(x, mod.weight, mod.bias)
-    if gemm_x3_ok(x, mod.weight) and x.numel() // x.shape[-1] >= 64:
+    if gemm_x3_takes(x, mod.weight):
         return gemm_x3(x, mod.weight, mod.bias)
     return F.linear(x, mod.weight, mod.bias)
 

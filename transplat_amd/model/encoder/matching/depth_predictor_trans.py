@@ -45,6 +45,14 @@ def _conv_gelu_conv(seq: nn.Sequential, x, extra=()):
     return kernels.conv_bias_act(seq[2], kernels.conv_bias_act(seq[0], x, "gelu", extra=extra))
 
 
+# camera_prep also computes the camera-parameter encoder's gate / the correlation kernels' packed
+# camera rows (two views); False = where they are used, as before (A/B scripts set these)
+_GATE_AHEAD = True
+_PACKED_AHEAD = True
+# coarse_two passes no query (it is zero); False = a torch.zeros query added to the correlation, as before
+_NO_ZERO_QUERY = True
+
+
 @torch.autocast("cuda", enabled=False)
 def camera_lists(intrinsics, extrinsics, near, far, num_samples: int, h: int, w: int):
     """The camera half of prepare_feat_proj_data_lists (reference :59-109): pixel intrinsics, relative
@@ -159,36 +167,51 @@ class DepthPredictorTrans(nn.Module):
         self.cam_param_encoder = cam_param_encoder(in_channels=DA_size, mid_channels=128, embed_dims=128)
 
     def camera_prep(self, intrinsics, extrinsics, near, far, h: int, w: int) -> dict:
-        """Everything the depth predictor derives from the cameras alone (camera_lists, and
-        match_two's img2world for two views), for forward(cams=...)."""
+        """Everything the depth predictor derives from the cameras alone (camera_lists, and for two
+        views match_two's img2world, the camera-parameter encoder's gate on it and the correlation
+        kernels' packed camera rows), for forward(cams=...). Every tensor sits in the returned dict:
+        it crosses a stream join there (streams._tensors walks dicts, tuples and lists)."""
         intr, poses, disp = camera_lists(intrinsics, extrinsics, near, far, self.num_depth_candidates, h, w)
         out = {"lists": (intr, poses, disp)}
         if intrinsics.shape[1] == 2:
             out["img2world"] = match_img2world(intr, extrinsics)
+            gate = self.cam_param_encoder.gate(out["img2world"]) if _GATE_AHEAD else None
+            if gate is not None:
+                out["gate"] = gate
+            if _PACKED_AHEAD and intr.is_cuda and intr.dtype == poses[0].dtype == torch.float32:
+                out["packed"] = kernels.pack_cameras_fused(intr, poses[0])
         return out
 
-    def coarse_two(self, intr_curr, pose_curr, disp_candi_curr, features):
+    def coarse_two(self, intr_curr, pose_curr, disp_candi_curr, features, cams_packed=None):
         """(reference :236-290, first half) the coarse correlation layer of a pair of views: reads
         only the backbone features and the cameras, so the encoder runs it before Depth-Anything's
         features exist (the reference computes the camera-parameter embedding first; the two are
         independent)."""
         b, v, c, h, w = features.shape
         cameras = (intr_curr, pose_curr, disp_candi_curr.flatten(1).float())
+        if cams_packed is not None:  # kernels.pack_cameras(intr_curr, pose_curr), from camera_prep
+            cameras += (cams_packed,)
         feat_cl = features.flatten(3).transpose(2, 3).contiguous()  # [b, v, HW, C]
-        query = torch.zeros((b * v, h * w, self.embed_dims), device=features.device, dtype=features.dtype)
+        # the query is zero: None, the coarse layer then returns the correlation as it is
+        query = None if _NO_ZERO_QUERY else torch.zeros((b * v, h * w, self.embed_dims), device=features.device,
+                                                        dtype=features.dtype)
         corr = self.coarse_transformer([features], query, w, h, cameras=cameras, channel_last=feat_cl)
         return corr, cameras, feat_cl
 
-    def fine_two(self, coarse, intr_curr, extrinsics, dino_feature, features, img2world=None):
+    def fine_two(self, coarse, intr_curr, extrinsics, dino_feature, features, img2world=None, gate=None):
         """(reference :236-290, second half) the fine layers on the coarse correlation, with the
         Depth-Anything-feature position embedding -> [(v b), D, h, w]."""
         b, v, c, h, w = features.shape
         corr, cameras, feat_cl = coarse
         if img2world is None:
             img2world = match_img2world(intr_curr, extrinsics)
-        pos_feature = self.cam_param_encoder(dino_feature, img2world)  # [(v b), C, h, w]
+        # [(v b), C, h, w], or where its last 1x1 can write them directly [(v b), h w, C] rows
+        pos_feature = self.cam_param_encoder(dino_feature, img2world, gate=gate, channel_last=b == 1)
         # (b v)-ordered channel-last query positions: the reference's bev_pos after its permutes
-        bev_pos = rearrange(pos_feature, "(v b) c h w -> (b v) (h w) c", v=v, b=b).contiguous()  # read by 2 layers
+        if pos_feature.dim() == 3:  # b = 1: (v b) order is (b v) order
+            bev_pos = pos_feature
+        else:
+            bev_pos = rearrange(pos_feature, "(v b) c h w -> (b v) (h w) c", v=v, b=b).contiguous()  # read by 2 layers
         corr = self.fine_transformer([features], corr, w, h, bev_pos=bev_pos, cameras=cameras, channel_last=feat_cl)
         return rearrange(corr, "(b v) (h w) c -> (v b) c h w", b=b, v=v, h=h, w=w)
 
@@ -245,7 +268,8 @@ class DepthPredictorTrans(nn.Module):
         coarse = None
         if v == 2:
             with stage(None, "dp_coarse"):  # diagnostic sub-stage mark
-                coarse = self.coarse_two(intr_curr, pose_curr_lists[0], disp_candi_curr, features)
+                coarse = self.coarse_two(intr_curr, pose_curr_lists[0], disp_candi_curr, features,
+                                         cams.get("packed") if cams is not None else None)
         return {"lists": (intr_curr, pose_curr_lists, disp_candi_curr), "feat01": feat01, "proj": proj,
                 "coarse": coarse}
 
@@ -265,8 +289,9 @@ class DepthPredictorTrans(nn.Module):
         with stage(benchmarker, "encoder_4b_cost_volume_matching"):
             img2world = cams.get("img2world") if cams is not None else None
             if begun["coarse"] is not None:
+                gate = cams.get("gate") if cams is not None else None
                 raw_correlation_in = torch.cat((self.fine_two(begun["coarse"], intr_curr, extrinsics, dino_feature,
-                                                              features, img2world), feat01), dim=1)
+                                                              features, img2world, gate), feat01), dim=1)
             else:
                 raw_correlation_in = self._match(v, intr_curr, pose_curr_lists, extrinsics, disp_candi_curr,
                                                  dino_feature, features, feat01, img2world)

@@ -37,6 +37,14 @@ class SELayer(nn.Module):
         return x * self.gate(x_se)
 
 
+# forward multiplies the gate into context_conv's input as that 1x1 loads it, and writes channel-last
+# rows where asked (kernels.conv1x1_scaled); False = multiply, convolution, permuted copy (A/B scripts)
+_FUSE_GATE_CONV = True
+# gate() runs the one-launch kernel; False = forward's module chain everywhere (A/B and drift scripts:
+# the gate kernel is the only piece of its round that moves values)
+_GATE_KERNEL = True
+
+
 class cam_param_encoder(nn.Module):  # noqa: N801  (reference class name kept for state_dict parity)
     def __init__(self, in_channels, mid_channels, embed_dims):
         super().__init__()
@@ -77,16 +85,42 @@ class cam_param_encoder(nn.Module):  # noqa: N801  (reference class name kept fo
             self.__dict__["_fold"] = hit
         return hit[1:]
 
-    def forward(self, feat, cam_params):
+    def _kernel_ok(self, t) -> bool:
+        """The inference path on the HIP kernels: fp32 device tensors outside autocast, eval mode."""
+        return (not self.training and t.is_cuda and t.dtype == torch.float32
+                and not torch.is_autocast_enabled("cuda"))
+
+    def gate(self, cam_params):
+        """The squeeze-excite gate [vb, mid_channels] = sigmoid(context_se's two 1x1s on context_mlp of
+        the (BatchNorm-ed) camera vector) as one launch (kernels.cam_gate). It reads the cameras only,
+        so a caller that has them early computes it once and passes it to forward(gate=...). None
+        where the kernel path does not apply (host tensors, training, autocast)."""
+        mlp, se = self.context_mlp, self.context_se
+        if not (_GATE_KERNEL and self._kernel_ok(cam_params) and self.cam_param_len == 16 and self.mid_channels == 128
+                and isinstance(mlp.act, nn.ReLU) and isinstance(se.act1, nn.ReLU) and isinstance(se.gate, nn.Sigmoid)):
+            return None
+        _, _, w1, b1 = self._folded()
+        return kernels.cam_gate(cam_params.reshape(-1, self.cam_param_len), w1, b1, mlp.fc2.weight, mlp.fc2.bias,
+                                se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias)
+
+    def forward(self, feat, cam_params, gate=None, channel_last: bool = False):
+        """[vb, C, h, w]; with channel_last, where the fused 1x1 takes the call, the same values as
+        [vb, h w, C] rows (the caller tells the two by the rank)."""
         vb = feat.shape[0]
         conv = self.reduce_conv[0]
-        if (not self.training and feat.is_cuda and feat.dtype == torch.float32 and conv.bias is not None
-                and not torch.is_autocast_enabled("cuda")
+        if (self._kernel_ok(feat) and conv.bias is not None
                 and kernels.conv3x3_wino_ok(feat, conv.weight, conv.stride, conv.padding, conv.dilation,
                                             conv.groups, vs_miopen=True)):
             # inference: both BatchNorms folded, conv + bias + ReLU as one Winograd launch
             w, b, w1, b1 = self._folded()
             feat = kernels.conv3x3_wino(feat, w, b, act="relu")
+            if gate is None:
+                gate = self.gate(cam_params)
+            if gate is not None:
+                cc = self.context_conv
+                if _FUSE_GATE_CONV and cc.padding_mode == "zeros" and kernels.conv1x1_scaled_ok(feat, cc.weight):
+                    return kernels.conv1x1_scaled(feat, gate, cc.weight, cc.bias, channel_last=channel_last)
+                return cc(feat * gate.view(vb, -1, 1, 1))
             mlp = self.context_mlp
             context_se = mlp.fc2(mlp.act(F.linear(cam_params.reshape(vb, -1), w1, b1)))[..., None, None]
             return self.context_conv(self.context_se(feat, context_se))

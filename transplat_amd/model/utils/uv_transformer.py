@@ -23,6 +23,34 @@ from torch import nn
 from ... import kernels
 
 
+# One split-bf16 GEMM where several nn.Linear modules read the same rows (the fine cross attention's
+# sampling_offsets | attention_weights, both fine layers' value_proj); False = one GEMM per module
+# (A/B scripts and the bit-identity test set it)
+_MERGE_PROJ = True
+
+
+def _split_cameras(cameras):
+    """(intr, pose, disp, keywords) of a cameras tuple: its optional fourth element is
+    kernels.pack_cameras(intr, pose) computed ahead (the depth predictor's camera prep), passed on to
+    the device kernels as cams_packed (the CPU restatements of those ops do not take it)."""
+    intr, pose, disp = cameras[:3]
+    packed = cameras[3] if len(cameras) > 3 else None
+    return intr, pose, disp, ({"cams_packed": packed} if packed is not None and packed.is_cuda else {})
+
+
+def _cat_linears(owner, slot: str, linears):
+    """(weight, bias) of several nn.Linear modules concatenated along the outputs, cached on `owner`
+    per parameter version: one GEMM then serves every module that reads the same rows."""
+    key = tuple((t.data_ptr(), t._version) for m in linears for t in (m.weight, m.bias))
+    hit = owner.__dict__.get(slot)
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            hit = (key, torch.cat([m.weight for m in linears], 0).contiguous(),
+                   torch.cat([m.bias for m in linears], 0).contiguous())
+        owner.__dict__[slot] = hit
+    return hit[1], hit[2]
+
+
 _REF2D: dict = {}  # (h, w, dtype, device) -> [1, h*w, 2] reference points
 _WH: dict = {}     # (w, h, dtype, device) -> tensor([w, h])
 
@@ -121,13 +149,25 @@ class UVCrossAttention(nn.Module):
         self.value_proj = nn.Linear(embed_dims, embed_dims)
         self.output_proj = nn.Linear(embed_dims, embed_dims)
 
-    def core(self, query, key_cl, value_cl, cameras, bev_h: int, bev_w: int):
-        """The correlation before output_proj (forward = output_proj(core) + identity)."""
-        value = self.value_proj(value_cl)  # per view; the kernel reads the other view (the flip)
-        offsets = self.sampling_offsets(query)
-        logits = self.attention_weights(query)
-        intr, pose, disp = cameras
-        return kernels.uv_cross(value, key_cl, intr, pose, disp, offsets, logits, bev_h, bev_w)
+    def core(self, query, key_cl, value_cl, cameras, bev_h: int, bev_w: int, value=None):
+        """The correlation before output_proj (forward = output_proj(core) + identity). value:
+        value_proj(value_cl) where the caller already has it (UVTransformerEncoder computes the fine
+        layers' projections of the shared features in one GEMM)."""
+        if value is None:
+            value = self.value_proj(value_cl)  # per view; the kernel reads the other view (the flip)
+        so, aw = self.sampling_offsets, self.attention_weights
+        if (_MERGE_PROJ and kernels.gemm_x3_takes(query, so.weight) and so.bias is not None
+                and aw.bias is not None):
+            # both projections of the same rows as one split-bf16 GEMM over [so.weight ; aw.weight];
+            # the kernel reads the two column ranges of its output in place (the same bits as two GEMMs)
+            w, b = _cat_linears(self, "_ow", (so, aw))
+            ow = kernels.gemm_x3(query, w, b)
+            offsets, logits = ow[..., :so.out_features], ow[..., so.out_features:]
+        else:
+            offsets = so(query)
+            logits = aw(query)
+        intr, pose, disp, kw = _split_cameras(cameras)
+        return kernels.uv_cross(value, key_cl, intr, pose, disp, offsets, logits, bev_h, bev_w, **kw)
 
     def forward(self, query, key_cl, value_cl, cameras, bev_h: int, bev_w: int):
         out = self.core(query, key_cl, value_cl, cameras, bev_h, bev_w)
@@ -149,8 +189,10 @@ class UVCoarseAttention(nn.Module):
             embed_dims, num_cams * self.num_heads * self.num_levels * self.num_depth * self.num_points)
 
     def forward(self, query, key_cl, cameras, bev_h: int, bev_w: int):
-        intr, pose, disp = cameras
-        return kernels.uv_coarse(key_cl, intr, pose, disp, bev_h, bev_w) + query
+        """query None: the zero query the depth predictor starts from (the correlation as it is)."""
+        intr, pose, disp, kw = _split_cameras(cameras)
+        corr = kernels.uv_coarse(key_cl, intr, pose, disp, bev_h, bev_w, **kw)
+        return corr if query is None else corr + query
 
 
 class FFN(nn.Module):
@@ -197,11 +239,11 @@ class UVTransformerEncoderLayer(nn.Module):
         else:
             raise NotImplementedError(mode)
 
-    def forward(self, query, key_cl, bev_pos, ref_2d, cameras, bev_h, bev_w):
+    def forward(self, query, key_cl, bev_pos, ref_2d, cameras, bev_h, bev_w, value=None):
         if self.mode == "coarse":
             return self.attentions[0](query, key_cl, cameras, bev_h, bev_w)
         if self._fused_ok(query):
-            return self._fine_fused(query, key_cl, bev_pos, ref_2d, cameras, bev_h, bev_w)
+            return self._fine_fused(query, key_cl, bev_pos, ref_2d, cameras, bev_h, bev_w, value)
         if self._ln128_ok(query):  # bf16 dense mode: the post-norms as kernels (fp32 in and out)
             ln = lambda i, t: kernels.layer_norm128(t, self.norms[i], out_dtype=torch.float32)
         else:
@@ -219,7 +261,7 @@ class UVTransformerEncoderLayer(nn.Module):
         return (query.dtype == torch.float32 and not torch.is_autocast_enabled(query.device.type)
                 and self.embed_dims == 128 and len(ffn.layers) == 3 and ffn.feedforward_channels % 128 == 0)
 
-    def _fine_fused(self, query, key_cl, bev_pos, ref_2d, cameras, bev_h, bev_w):
+    def _fine_fused(self, query, key_cl, bev_pos, ref_2d, cameras, bev_h, bev_w, value=None):
         """Fine layer with each output projection + bias + identity + LayerNorm (and the FFN's
         second Linear with its ReLU-on-load) as one kernels.fused_linear launch; same math as the
         module chain (dropout is the identity at test time)."""
@@ -232,7 +274,7 @@ class UVTransformerEncoderLayer(nn.Module):
             out = sa.core(query, query, bev_pos, ref_2d, bev_h, bev_w)
         query = K.fused_linear(out, sa.output_proj.weight, bias=sa.output_proj.bias, ln=ln(self.norms[0]),
                                residual=query, res_pre_ln=True)
-        out = ca.core(query, key_cl, key_cl, cameras, bev_h, bev_w)
+        out = ca.core(query, key_cl, key_cl, cameras, bev_h, bev_w, value=value)
         query = K.fused_linear(out, ca.output_proj.weight, bias=ca.output_proj.bias, ln=ln(self.norms[1]),
                                residual=query, res_pre_ln=True)
         fc1, fc2 = ffn.layers[0][0], ffn.layers[1]
@@ -262,11 +304,32 @@ class UVTransformerEncoder(nn.Module):
             _REF2D[key] = ref
         return ref.expand(n, -1, -1)
 
+    def _cross_values(self, query, key_cl):
+        """value_proj(key_cl) of every fine layer's cross attention as one split-bf16 GEMM over the
+        concatenated weights -> per layer a column range [..., 128] of its output (read in place by
+        the correlation kernel), or None per layer where the layers run their own projection."""
+        none = [None] * len(self.layers)
+        if not _MERGE_PROJ or len(self.layers) < 2 or any(l.mode != "fine" or not l._fused_ok(query) for l in self.layers):
+            return none
+        projs = [l.attentions[1].value_proj for l in self.layers]
+        if any(p.bias is None for p in projs) or not kernels.gemm_x3_takes(key_cl, projs[0].weight):
+            return none
+        w, b = _cat_linears(self, "_vw", projs)
+        vals = kernels.gemm_x3(key_cl, w, b)
+        c = projs[0].out_features
+        return [vals[..., i * c:(i + 1) * c] for i in range(len(projs))]
+
     def forward(self, query, key_cl, bev_h, bev_w, bev_pos=None, cameras=None):
-        # query, bev_pos: [(b v), HW, C]; key_cl: [B, 2, HW, C]
-        ref_2d = self.reference_points_2d(bev_h, bev_w, query.shape[0], query.dtype, query.device)
-        for layer in self.layers:
-            query = layer(query, key_cl, bev_pos, ref_2d, cameras, bev_h, bev_w)
+        # query, bev_pos: [(b v), HW, C]; key_cl: [B, 2, HW, C]; query None (coarse): a zero query
+        n = key_cl.shape[0] * key_cl.shape[1] if query is None else query.shape[0]
+        ref_2d = self.reference_points_2d(bev_h, bev_w, n, key_cl.dtype if query is None else query.dtype,
+                                          key_cl.device)
+        values = [None] * len(self.layers) if query is None else self._cross_values(query, key_cl)
+        for layer, value in zip(self.layers, values):
+            if value is None:
+                query = layer(query, key_cl, bev_pos, ref_2d, cameras, bev_h, bev_w)
+            else:
+                query = layer(query, key_cl, bev_pos, ref_2d, cameras, bev_h, bev_w, value=value)
         return query
 
 

@@ -37,6 +37,7 @@ _HIP = {
     "tsplat_conv3x3_wino_cat_f32_fwd": ("3x3 convs (HIP Winograd)", "exact fp32"),
     "tsplat_conv3x3_few_bf16x3_fwd": ("direct convs (HIP)", "bf16x3"),
     "tsplat_conv2d_bf16x3_fwd": ("direct convs (HIP)", "bf16x3"),
+    "tsplat_conv1x1_bf16x3_scaled_fwd": ("direct convs (HIP)", "bf16x3"),
     "tsplat_conv2d_f32_fwd": ("direct convs (HIP)", "exact fp32"),
     "tsplat_conv2d_f32_zsplit_fwd": ("direct convs (HIP)", "exact fp32"),
     "tsplat_conv2d_f32_nhwc_fwd": ("direct convs (HIP)", "exact fp32"),
@@ -45,6 +46,7 @@ _HIP = {
     "tsplat_linear_f32_split_x3_fwd": ("transformer linears (HIP)", None),
     "tsplat_linear_f32_attn_merge_fwd": ("transformer linears (HIP)", None),
     "tsplat_gemm_x3_fwd": ("GEMMs (HIP)", "bf16x3"),
+    "tsplat_gemm_x3_cat_fwd": ("GEMMs (HIP)", "bf16x3"),
     "tsplat_mha_x3_fwd": ("DINOv2 attention (HIP)", "bf16x3"),
     "tsplat_mha_x3_presplit_fwd": ("DINOv2 attention (HIP)", "bf16x3"),
     "tsplat_mha_f32_fwd": ("DINOv2 attention (HIP)", "exact fp32"),
@@ -54,6 +56,9 @@ _HIP = {
     "tsplat_uv_cross_table_fwd": ("correlation (HIP)", "fp32"),
     "tsplat_uv_cross_fwd": ("correlation (HIP)", "fp32"),
     "tsplat_uv_cross_fused_fwd": ("correlation (HIP)", "bf16x3 products, fp32 gather"),
+    "tsplat_uv_cross_fused_ld_fwd": ("correlation (HIP)", "bf16x3 products, fp32 gather"),
+    "tsplat_cam_gate_fwd": ("camera prep (HIP)", "exact fp32"),
+    "tsplat_pack_cameras_fwd": ("camera prep (HIP)", "exact fp32"),
     "tsplat_msda_fwd": ("correlation (HIP)", "fp32"),
     "tsplat_msda_raw_fwd": ("correlation (HIP)", "fp32"),
     "tsplat_ms_deform_attn_fwd": ("correlation (HIP)", "fp32"),
@@ -74,7 +79,7 @@ _HIP = {
 }
 _ORDER = ("window attention", "transformer linears (HIP)", "GEMMs (HIP)", "3x3 convs (HIP Winograd)", "direct convs (HIP)",
           "DINOv2 attention (HIP)", "U-Net attention (HIP)", "library GEMMs (hipBLASLt)", "library convs (MIOpen)",
-          "correlation (HIP)", "norms (HIP)", "Depth-Anything glue (HIP)", "gaussian adapter (HIP)", "rasterizer (HIP)")
+          "camera prep (HIP)", "correlation (HIP)", "norms (HIP)", "Depth-Anything glue (HIP)", "gaussian adapter (HIP)", "rasterizer (HIP)")
 _GEMMS = {"mm", "addmm", "bmm", "baddbmm", "addbmm", "_scaled_mm"}
 _CONVS = {"convolution", "_convolution", "cudnn_convolution", "miopen_convolution", "convolution_overrideable",
           "conv2d", "conv_transpose2d", "miopen_convolution_transpose"}
