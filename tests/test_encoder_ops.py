@@ -976,9 +976,11 @@ def test_upsample_bilinear_act_kernel(device, shape, scale, act, bias):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("vb,heads,views,t", [(2, 4, 2, 256), (2, 1, 2, 256), (3, 2, 1, 100), (4, 1, 2, 37)])
+@pytest.mark.parametrize("vb,heads,views,t", [(2, 4, 2, 256), (2, 1, 2, 256), (3, 2, 1, 100), (4, 1, 2, 37),
+                                                  (6, 2, 3, 40), (6, 1, 3, 37)])
 def test_qkv_attention_cf_kernel(device, vb, heads, views, t):
-    """U-Net legacy QKV attention (head dim 32, views folded into the tokens) vs the oracle."""
+    """U-Net legacy QKV attention (head dim 32, views folded into the tokens) vs the oracle; the
+    vb = 6 cases fold 3 views of 2 scenes (row view * 2 + scene)."""
     from transplat_amd import kernels as K
 
     qkv = seeded((vb, 3 * heads * 32, t), 81) * 2.0

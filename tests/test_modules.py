@@ -240,7 +240,7 @@ def test_uv_transformers_gpu(device, dense):
     _close(f, g["fine"], _gtol("uv.fine", dense), f"uv.fine {dense}")
 
 
-# ------------------------------------------------------------------ U-Nets (MIOpen path)
+# ------------------------------------------------------------------ U-Nets (direct HIP convolutions at these sizes)
 @pytest.mark.parametrize("tag,ch,mult,attn,hw", [("cv", 128, (1, 1, 1), (4,), 16),
                                                  ("depth", 32, (1, 1, 1, 1, 1), (16,), 32)])
 def test_unet_cpu(cpu_ops, tag, ch, mult, attn, hw):

@@ -26,6 +26,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent / "golden"))
 from canonical import seeded  # noqa: E402
 
 from oracle import encoder_ops as E  # noqa: E402
+from oracle.unet_blocks import bf16_hi, x3_ideal  # noqa: E402,F401
 from test_conv import tf32_round  # noqa: E402  (the TF32 operand rounding behind every etf bar)
 
 F = torch.nn.functional
@@ -636,20 +637,8 @@ def test_fused_linear_ln_shifted(device, dense, res_pre_ln):
 
 
 # ===================================================================== C. split-bf16 products
-def bf16_hi(t: torch.Tensor, truncate: bool = False) -> torch.Tensor:
-    """The bf16 image of fp32 t (round to nearest even, or the biased truncation), as float64."""
-    if truncate:
-        return (t.float().contiguous().view(torch.int32) & ~0xFFFF).view(torch.float32).double()
-    return t.float().bfloat16().double()
-
-
-def x3_ideal(op, x, w, truncate: bool = False):
-    """An ideal bf16x3 product in float64: hi = bf16(x), lo = bf16(x - hi), hi hi' + hi lo' + lo hi'."""
-    xh, wh = bf16_hi(x, truncate), bf16_hi(w, truncate)
-    xl, wl = (x.double() - xh).float().bfloat16().double(), (w.double() - wh).float().bfloat16().double()
-    return op(xh, wh + wl) + op(xl, wh)
-
-
+# (bf16_hi and x3_ideal, the ideal split in float64, are shared with the U-Net block tests:
+# oracle/unet_blocks.py)
 # name -> (kind, geometry): gemm (m, k, n, ksplit); conv (n, c1, c2, h, w, co, k, stride)
 C_CASES = {
     "gemm_130_200_260": ("gemm", (130, 200, 260, 2)),
