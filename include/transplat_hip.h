@@ -745,6 +745,39 @@ size_t tsplat_ssim_workspace_bytes(int32_t n, int32_t height, int32_t width);
 int tsplat_ssim_fwd(const float* gt, const float* pred, float* ssim, void* workspace, int32_t n, int32_t height,
                     int32_t width, void* stream);
 
+/* LPIPS of the evaluation (reference compute_lpips, src/evaluation/metrics.py:22-33, recorded per scene
+ * by test_step, src/model/model_wrapper.py:318-320): LPIPS(net="vgg"), version 0.1, linear layers on,
+ * forward(gt, pred, normalize=True) -- the launches around the thirteen VGG16 convolutions, which the
+ * caller runs with tsplat_conv3x3_wino_f32_fwd (bias and ReLU fused). All maps fp32 NCHW contiguous.
+ *
+ * tsplat_lpips_scale_fwd: gt, pred [n, 3, height, width] (not clipped) -> out [2n, 3, height, width], the
+ *   gt images first: ((2 x - 1) - shift_c) / scale_c with shift (-0.030, -0.088, -0.188) and scale
+ *   (0.458, 0.448, 0.450), as separate fp32 multiply, subtract, subtract and IEEE divide (torch's bits).
+ * tsplat_lpips_tap_fwd: one tap. feat [2n, channels, height, width] (pair i = images i and n + i), lin
+ *   [channels] the tap's 1x1 weights. Per pixel d = sum_c lin_c (f0_c / (|f0| + 1e-10) - f1_c / (|f1| +
+ *   1e-10))^2 (0 for an all-zero pixel); partials receives tsplat_lpips_tap_blocks(channels, height,
+ *   width) float64 sums of d per pair, [pair][block] (ordinary stores, no atomics; the count depends on
+ *   the map alone). Every sum is float64. pooled, when not null: [2n, channels, height / 2, width / 2],
+ *   the 2x2 / stride-2 max-pool in floor mode, written in the same pass (an odd last row or column
+ *   counts in d and not in the pool).
+ * tsplat_lpips_workspace_bytes(n, channels, height, width): bytes of one tap's partials (8-byte aligned;
+ *   0 for arguments tsplat_lpips_tap_fwd rejects). The taps of one call lie back to back in one workspace.
+ * tsplat_lpips_reduce_fwd: workspace = the partials of ntaps (<= 8) taps back to back, [tap][pair][block];
+ *   blocks[ntaps] (int32) and pixels[ntaps] (int64, height_k * width_k) are HOST arrays read during the
+ *   call. Per pair: tap k's partials summed in a fixed order / pixels[k] -> out_layers[n, ntaps] (may be
+ *   null), their float64 sum rounded once -> out[n]. A pair's values repeat bit for bit and depend on
+ *   neither n nor the pair's place in the batch.
+ * TSPLAT_EINVAL, before any launch: a null pointer (other than pooled / out_layers), n, channels, height
+ *   or width <= 0, ntaps outside 1..8, a grid beyond 2^31 - 1 workgroups (scale: n > 10922). */
+int tsplat_lpips_scale_fwd(const float* gt, const float* pred, float* out, int32_t n, int32_t height, int32_t width,
+                           void* stream);
+int32_t tsplat_lpips_tap_blocks(int32_t channels, int32_t height, int32_t width);
+size_t tsplat_lpips_workspace_bytes(int32_t n, int32_t channels, int32_t height, int32_t width);
+int tsplat_lpips_tap_fwd(const float* feat, const float* lin, void* partials, float* pooled, int32_t n,
+                         int32_t channels, int32_t height, int32_t width, void* stream);
+int tsplat_lpips_reduce_fwd(const void* workspace, const int32_t* blocks, const int64_t* pixels, int32_t ntaps,
+                            float* out, float* out_layers, int32_t n, void* stream);
+
 /* Diagnostics: write the 100-MHz device wall clock into ((uint64_t*)buf)[slot] when this launch
  * runs on `stream` (stage marks of a captured / replayed step, tools/graph_stages.py). */
 int tsplat_timestamp(void* buf, int32_t slot, void* stream);

@@ -80,6 +80,11 @@ SIGNATURES = {
     "tsplat_depth_tail_fwd": (ctypes.c_int, [_P] * 6 + [_I32] * 3 + [_P]),
     "tsplat_ssim_workspace_bytes": (ctypes.c_size_t, [_I32] * 3),
     "tsplat_ssim_fwd": (ctypes.c_int, [_P] * 4 + [_I32] * 3 + [_P]),
+    "tsplat_lpips_scale_fwd": (ctypes.c_int, [_P] * 3 + [_I32] * 3 + [_P]),
+    "tsplat_lpips_tap_blocks": (_I32, [_I32] * 3),
+    "tsplat_lpips_workspace_bytes": (ctypes.c_size_t, [_I32] * 4),
+    "tsplat_lpips_tap_fwd": (ctypes.c_int, [_P] * 4 + [_I32] * 4 + [_P]),
+    "tsplat_lpips_reduce_fwd": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _I32, _P]),
     "tsplat_raster_cameras": (ctypes.c_int, [_P] * 5 + [_I32] * 3 + [_P] * 7),
     "tsplat_small_inverse": (ctypes.c_int, [_P, _P, _I32, _I32, _P]),
     "tsplat_pack_cameras_fwd": (ctypes.c_int, [_P, _P, _P, _I32, _P]),

@@ -36,7 +36,8 @@ HIPCC_FLAGS = [
 # (entry, pixel) without it)
 FILE_FLAGS = {"raster.hip": ["-fno-slp-vectorize"],
               "upsample.hip": ["-ffp-contract=off"],  # torch's rounding of the interpolation weights
-              "daglue.hip": ["-ffp-contract=off"]}  # the same formula, and torch's separate sub / div / mul / add
+              "daglue.hip": ["-ffp-contract=off"],  # the same formula, and torch's separate sub / div / mul / add
+              "lpips.hip": ["-ffp-contract=off"]}  # the input scaling's separate mul / sub / sub / div
 
 
 def _hipcc() -> str:

@@ -1,8 +1,9 @@
 """Scene-sharded evaluation: rank r of N takes scenes r, r+N, ... of the evaluation
 index, runs the reference test_step sequence (encoder -> decoder -> PSNR and SSIM per target view,
 reference src/model/model_wrapper.py:185-323) and the per-scene metrics are gathered once at the
-end with ONE all_gather of a fixed-width fp32 tensor [n_local, 6] = (scene_idx, psnr, n_views,
-seconds, capture, ssim) — RCCL over xGMI on GPUs, gloo on CPU. No collective touches the data path.
+end with ONE all_gather of a fixed-width fp32 tensor [n_local, 7] = (scene_idx, psnr, n_views,
+seconds, capture, ssim, lpips) — RCCL over xGMI on GPUs, gloo on CPU. No collective touches the data
+path.
 
 With no dataset offline, scenes are synthetic (transplat_amd.synthetic) unless a loader is passed;
 the evaluation index (e.g. the reference's assets/evaluation_index_re10k_small.json) supplies the
@@ -14,11 +15,14 @@ hipGraph per input-shape signature (bench.py's timed region), in the bench's def
 bracketed by HIP events; the host synchronises ONCE per shard, after its last scene, then reads the
 metrics and event times. `--output-path DIR` writes the reference's scores files
 (model_wrapper.py:325-343): scores_psnr_all.json, scores_ssim_all.json, scene_all.json,
-scores_all_avg.json.
+scores_all_avg.json. `--lpips-weights FILE` adds the reference's third metric, LPIPS (VGG16; the two
+weight layouts: evaluation/lpips_vgg.py): queued per scene behind the SSIM, outside `seconds`, read at
+the same synchronisation, and written as scores_lpips_all.json.
 """
 from __future__ import annotations
 
 import json
+import math
 import time
 from dataclasses import dataclass
 from pathlib import Path
@@ -27,7 +31,7 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
-from .evaluation.metrics import SSIM_WIN, compute_psnr, compute_ssim
+from .evaluation.metrics import LPIPS_MIN_SIZE, SSIM_WIN, compute_lpips, compute_psnr, compute_ssim
 
 
 @dataclass
@@ -38,6 +42,7 @@ class SceneResult:
     seconds: float
     capture: bool = False  # the step captured its hipGraph (warmup + capture inside `seconds`)
     ssim: float = float("nan")  # mean over the target views; NaN where it was not computed
+    lpips: float = float("nan")  # likewise; computed only when the evaluation is given LPIPS weights
 
 
 def load_index(path: str | Path) -> list[tuple[str, dict]]:
@@ -53,9 +58,9 @@ def shard(items: list, rank: int, world: int) -> list[tuple[int, object]]:
 
 
 def gather_results(local: list[SceneResult], device: torch.device, world: int) -> list[SceneResult]:
-    """One all_gather of [n_local_max, 6] fp32 rows (padded with scene_idx = -1)."""
-    rows = torch.tensor([[r.scene_idx, r.psnr, r.n_views, r.seconds, float(r.capture), r.ssim] for r in local],
-                        dtype=torch.float32, device=device).reshape(-1, 6)
+    """One all_gather of [n_local_max, 7] fp32 rows (padded with scene_idx = -1)."""
+    rows = torch.tensor([[r.scene_idx, r.psnr, r.n_views, r.seconds, float(r.capture), r.ssim, r.lpips]
+                         for r in local], dtype=torch.float32, device=device).reshape(-1, 7)
     if world == 1:
         gathered = [rows]
     else:
@@ -63,7 +68,7 @@ def gather_results(local: list[SceneResult], device: torch.device, world: int) -
         counts = [torch.zeros_like(n) for _ in range(world)]
         dist.all_gather(counts, n)
         nmax = int(max(c.item() for c in counts))
-        pad = torch.full((nmax, 6), -1.0, device=device)
+        pad = torch.full((nmax, 7), -1.0, device=device)
         pad[: rows.shape[0]] = rows
         gathered = [torch.empty_like(pad) for _ in range(world)]
         dist.all_gather(gathered, pad)
@@ -71,7 +76,7 @@ def gather_results(local: list[SceneResult], device: torch.device, world: int) -
     for g in gathered:
         for row in g.cpu().tolist():
             if row[0] >= 0:
-                out.append(SceneResult(int(row[0]), row[1], int(row[2]), row[3], row[4] > 0.5, row[5]))
+                out.append(SceneResult(int(row[0]), row[1], int(row[2]), row[3], row[4] > 0.5, row[5], row[6]))
     return sorted(out, key=lambda r: r.scene_idx)
 
 
@@ -122,8 +127,8 @@ class _Pending:
     scene a device-side copy of the rasterizer's sticky overflow flag is kept, so an overflow found
     at the end names the first scene that raised it."""
 
-    def __init__(self, device: torch.device):
-        self.device, self.rows = device, []
+    def __init__(self, device: torch.device, lpips=None):
+        self.device, self.rows, self.lpips = device, [], lpips  # lpips: an LpipsVGG on `device`, or None
 
     @staticmethod
     def _ssim(gt: torch.Tensor, color: torch.Tensor) -> torch.Tensor:
@@ -132,6 +137,12 @@ class _Pending:
         if min(color.shape[-2:]) < SSIM_WIN:
             return torch.full((), float("nan"), dtype=torch.float64, device=color.device)
         return compute_ssim(gt, color).double().mean()
+
+    def _lpips(self, gt: torch.Tensor, color: torch.Tensor) -> torch.Tensor:
+        """Mean LPIPS over the scene's target views, like _ssim; NaN without weights or below 16 x 16."""
+        if self.lpips is None or min(color.shape[-2:]) < LPIPS_MIN_SIZE:
+            return torch.full((), float("nan"), dtype=torch.float64, device=color.device)
+        return compute_lpips(gt, color, self.lpips).double().mean()
 
     def run(self, idx: int, step, batch: dict) -> None:
         from .model.decoder.hip_splatting import status_tensor
@@ -145,16 +156,18 @@ class _Pending:
             psnr = compute_psnr(gt, color[0]).mean()  # before a replay reuses color
             e1.record()  # `seconds` = step + PSNR; the SSIM follows on the same stream, outside it
             ssim = self._ssim(gt, color[0])  # also before the next replay
+            lpips = self._lpips(gt, color[0])  # likewise, behind the SSIM
             st = status_tensor(self.device)
             self.rows.append((idx, psnr, int(color.shape[1]), (e0, e1), getattr(step, "last_captured", False),
-                              st.clone() if st is not None else None, ssim))
+                              st.clone() if st is not None else None, ssim, lpips))
         else:
             t0 = time.perf_counter()
             color = step(batch)
             gt = gt.to(color.device)
             psnr = compute_psnr(gt, color[0]).mean()
             sec = time.perf_counter() - t0
-            self.rows.append((idx, psnr, int(color.shape[1]), sec, False, None, self._ssim(gt, color[0])))
+            self.rows.append((idx, psnr, int(color.shape[1]), sec, False, None, self._ssim(gt, color[0]),
+                              self._lpips(gt, color[0])))
 
     def results(self) -> list[SceneResult]:
         if self.device.type == "cuda":
@@ -166,31 +179,33 @@ class _Pending:
                 raise RuntimeError(f"tsplat_raster_fwd: instance capacity exceeded (first at scene {bad[0]})")
             _raster_status(self.device)
         out = []
-        for idx, psnr, nv, t, cap, _, ssim in self.rows:
+        for idx, psnr, nv, t, cap, _, ssim, lpips in self.rows:
             sec = t[0].elapsed_time(t[1]) / 1e3 if isinstance(t, tuple) else t
-            out.append(SceneResult(idx, float(psnr.item()), nv, sec, bool(cap), float(ssim.item())))
+            out.append(SceneResult(idx, float(psnr.item()), nv, sec, bool(cap), float(ssim.item()),
+                                   float(lpips.item())))
         return out
 
 
 def evaluate(step: Callable[[dict], torch.Tensor], scenes: list, make_batch: Callable[[int, object], dict],
-             device: torch.device, rank: int = 0, world: int = 1) -> list[SceneResult]:
+             device: torch.device, rank: int = 0, world: int = 1, lpips=None) -> list[SceneResult]:
     """`make_batch(scene_idx, entry)` -> batch dict (b = 1); `step(batch)` -> color [1, V, 3, H, W].
     One device synchronisation per shard (after its last scene); `seconds` is each scene's step +
-    PSNR time from HIP events on the GPU (host wall time on CPU)."""
-    pend = _Pending(device)
+    PSNR time from HIP events on the GPU (host wall time on CPU). `lpips`: an LpipsVGG on `device` to
+    also record each scene's LPIPS (outside `seconds`); without it every result's lpips is NaN."""
+    pend = _Pending(device, lpips)
     for idx, entry in shard(scenes, rank, world):
         pend.run(idx, step, make_batch(idx, entry))
     return gather_results(pend.results(), device, world)
 
 
 def evaluate_stream(step: Callable[[dict], torch.Tensor], examples, device: torch.device, rank: int = 0,
-                    world: int = 1, keys: Optional[list] = None) -> list[SceneResult]:
+                    world: int = 1, keys: Optional[list] = None, lpips=None) -> list[SceneResult]:
     """Like `evaluate`, over an iterable of ready batches (the chunk reader): example i of the
     stream is scene i, and rank r keeps i = r, r + N, ... (every rank decodes the same stream
     order, so the split matches the index-driven one). `keys`, if given, receives every example's
     scene key (batch["scene"][0], the reference's model_wrapper.py:321-323) in stream order, on
-    every rank."""
-    pend = _Pending(device)
+    every rank. `lpips`: as in `evaluate`."""
+    pend = _Pending(device, lpips)
     for idx, batch in enumerate(examples):
         if keys is not None:
             keys.append(batch["scene"][0])
@@ -207,7 +222,7 @@ def summarize(results: list[SceneResult]) -> dict:
     captured a hipGraph carries the warmup and the capture, reported apart as `capture_seconds`)."""
     n = len(results)
     steady = [r for r in results if not r.capture]
-    return {
+    out = {
         "scenes": n,
         "psnr": sum(r.psnr for r in results) / max(n, 1),
         "ssim": sum(r.ssim for r in results) / max(n, 1),
@@ -217,18 +232,27 @@ def summarize(results: list[SceneResult]) -> dict:
         "capture_scenes": n - len(steady),
         "capture_seconds": sum(r.seconds for r in results if r.capture),
     }
+    if _has_lpips(results):
+        out["lpips"] = sum(r.lpips for r in results) / n
+    return out
+
+
+def _has_lpips(results: list[SceneResult]) -> bool:
+    """Every scene carries an LPIPS value: the run was given weights and no scene was too small."""
+    return bool(results) and not any(math.isnan(r.lpips) for r in results)
 
 
 def write_scores(results: list[SceneResult], keys: list[str], out_dir: str | Path) -> dict:
     """The reference's scores files (on_test_end, src/model/model_wrapper.py:325-343, :521-522) in
     `out_dir`: scores_psnr_all.json and scores_ssim_all.json (per-scene floats in scene order),
     scene_all.json (keys[r.scene_idx] in the same order) and scores_all_avg.json ({"psnr", "ssim"}:
-    sum / count as there). Returns the averages."""
+    sum / count as there). When every result has an LPIPS value, also scores_lpips_all.json and a
+    "lpips" average. Returns the averages."""
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     results = sorted(results, key=lambda r: r.scene_idx)
     avg = {}
-    for metric in ("psnr", "ssim"):
+    for metric in ("psnr", "ssim") + (("lpips",) if _has_lpips(results) else ()):
         scores = [getattr(r, metric) for r in results]
         avg[metric] = sum(scores) / len(scores) if scores else float("nan")
         (out_dir / f"scores_{metric}_all.json").write_text(json.dumps(scores))
@@ -270,6 +294,12 @@ def main(argv=None):
     ap.add_argument("--output-path", default=None,
                     help="directory for the reference's scores files (scores_psnr_all.json, scores_ssim_all.json, "
                          "scene_all.json, scores_all_avg.json), written by rank 0; nothing is written without it")
+    ap.add_argument("--lpips-weights", default=None,
+                    help="also report LPIPS (VGG16): a state dict of the whole metric (net.slice*.* and lin*.model.1.weight "
+                         "keys), or a torchvision VGG16 state dict together with --lpips-lin-weights")
+    ap.add_argument("--lpips-lin-weights", default=None,
+                    help="the metric's five linear layers (lin{0..4}.model.1.weight) when --lpips-weights is a plain "
+                         "VGG16 state dict")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -289,6 +319,11 @@ def main(argv=None):
     if args.checkpoint:
         model.load_checkpoint(args.checkpoint)
     step = (lambda batch: model.test_step(batch).color) if args.no_graph else GraphedSteps(model)
+    lpips = None
+    if args.lpips_weights:
+        from .evaluation.lpips_vgg import LpipsVGG
+
+        lpips = LpipsVGG.from_files(args.lpips_weights, args.lpips_lin_weights).to(device)
     if args.data_root:
         from itertools import islice
 
@@ -298,13 +333,13 @@ def main(argv=None):
         ds = ChunkTestDataset.from_index_file(cfg, args.index)
         stream = (ChunkTestDataset.batch(ex) for ex in islice(iter(ds), args.limit))
         keys = []  # the examples' scene strings, in stream order
-        results = evaluate_stream(step, stream, device, rank, world, keys)
+        results = evaluate_stream(step, stream, device, rank, world, keys, lpips=lpips)
         data = f"{args.experiment} chunks under {args.data_root}"
     else:
         scenes = load_index(args.index)[: args.limit]
         keys = [k for k, _ in scenes]
         results = evaluate(step, [(k, v) for k, v in scenes],
-                           lambda i, kv: index_batch(i, kv[0], kv[1], device=device), device, rank, world)
+                           lambda i, kv: index_batch(i, kv[0], kv[1], device=device), device, rank, world, lpips=lpips)
         data = "synthetic frames at the index's frame positions"
     if rank == 0:
         if args.output_path:
@@ -313,6 +348,8 @@ def main(argv=None):
         summary.update({"index": str(args.index), "world": world, "weights": args.checkpoint or "synthetic",
                         "data": data, "dense_dtype": args.dense_dtype, "graph": not args.no_graph,
                         "precision": precision_label(args.dense_dtype)})
+        if args.lpips_weights:
+            summary["lpips_weights"] = str(args.lpips_weights)
         print(json.dumps(summary), flush=True)
     if world > 1:
         dist.destroy_process_group()

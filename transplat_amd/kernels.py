@@ -801,6 +801,105 @@ def ssim(gt, pred):
     return out
 
 
+LPIPS_CHUNK = 8  # pairs per pass of kernels.lpips: the two largest maps (2 x 16 x 64 x 256^2 fp32) stay near 270 MB
+
+
+def lpips_scale(gt, pred):
+    """[n, 3, H, W] fp32 contiguous device pairs -> the network's input batch [2n, 3, H, W], gt images
+    first: ((2 x - 1) - shift) / scale in torch's fp32 operation order (tsplat_lpips_scale_fwd)."""
+    lib = _lib.load()
+    n, _, h, w = gt.shape
+    out = torch.empty((2 * n, 3, h, w), dtype=torch.float32, device=gt.device)
+    _lib.check(lib.tsplat_lpips_scale_fwd(_lib.ptr(gt), _lib.ptr(pred), _lib.ptr(out), n, h, w,
+                                          _lib.stream_ptr(gt.device)), "tsplat_lpips_scale_fwd")
+    return out
+
+
+def _lpips_tap_into(feat, lin, partials, pool: bool):
+    """One tsplat_lpips_tap_fwd launch on feat [2n, C, H, W]: the pairs' partial sums into the float64
+    tensor `partials` [n * blocks], and the 2x2 max-pooled map (None unless `pool`)."""
+    lib = _lib.load()
+    n2, c, h, w = feat.shape
+    pooled = torch.empty((n2, c, h // 2, w // 2), dtype=torch.float32, device=feat.device) if pool else None
+    _lib.check(lib.tsplat_lpips_tap_fwd(_lib.ptr(feat), _lib.ptr(lin), _lib.ptr(partials), _lib.ptr(pooled), n2 // 2, c,
+                                        h, w, _lib.stream_ptr(feat.device)), "tsplat_lpips_tap_fwd")
+    return pooled
+
+
+def _lpips_reduce(workspace, n: int, blocks, pixels, out, layers):
+    """tsplat_lpips_reduce_fwd over the taps' partials lying back to back in `workspace`."""
+    lib = _lib.load()
+    pix = ctypes.cast((ctypes.c_int64 * len(pixels))(*pixels), ctypes.c_void_p)
+    _lib.check(lib.tsplat_lpips_reduce_fwd(_lib.ptr(workspace), _int32_array(blocks), pix, len(blocks), _lib.ptr(out),
+                                           _lib.ptr(layers), n, _lib.stream_ptr(workspace.device)),
+               "tsplat_lpips_reduce_fwd")
+
+
+def lpips_tap(feat, lin, pool: bool = True):
+    """One LPIPS tap on its own: feat [2n, C, H, W] (pair i = images i and n + i), lin [C] -> (L [n]
+    fp32, the spatial mean of sum_c lin_c (f0_c / (|f0| + 1e-10) - f1_c / (|f1| + 1e-10))^2, and the
+    2x2 max-pooled [2n, C, H // 2, W // 2] map or None): tsplat_lpips_tap_fwd + tsplat_lpips_reduce_fwd."""
+    lib = _lib.load()
+    if not (feat.is_cuda and lin.is_cuda):
+        raise RuntimeError("transplat HIP ops need device tensors (no CPU path)")
+    if feat.dim() != 4 or feat.shape[0] % 2 or feat.shape[0] == 0 or tuple(lin.shape) != (feat.shape[1],):
+        raise ValueError(f"lpips_tap: features {tuple(feat.shape)} and weights {tuple(lin.shape)}")
+    f, v = _f32(feat), _f32(lin)
+    n2, c, h, w = f.shape
+    n = n2 // 2
+    blocks = int(lib.tsplat_lpips_tap_blocks(c, h, w))
+    ws = torch.empty(int(lib.tsplat_lpips_workspace_bytes(n, c, h, w)) // 8, dtype=torch.float64, device=f.device)
+    pooled = _lpips_tap_into(f, v, ws, pool)
+    out = torch.empty((n,), dtype=torch.float32, device=f.device)
+    _lpips_reduce(ws, n, [blocks], [h * w], out, None)
+    return out, pooled
+
+
+def lpips(gt, pred, net, return_layers: bool = False):
+    """Per-image LPIPS(net="vgg", version 0.1, linear layers on) of [n, 3, H, W] pairs called as the
+    reference does, forward(gt, pred, normalize=True), inputs not clipped -> [n] fp32 (and the five
+    taps' contributions [n, 5] with `return_layers`). `net`: an evaluation.lpips_vgg.LpipsVGG on the
+    inputs' device. H, W >= 16. Per chunk of at most LPIPS_CHUNK pairs: tsplat_lpips_scale_fwd, the
+    thirteen convolutions on the exact-fp32 Winograd kernel with bias and ReLU fused (whatever dense
+    precision mode is active), tsplat_lpips_tap_fwd after each block (which also writes the next
+    block's max-pooled input) and one tsplat_lpips_reduce_fwd: 20 launches, float64 from the features
+    to the value. A pair's value does not depend on its batch or chunk."""
+    from .evaluation.lpips_vgg import MIN_SIZE, VGG_BLOCKS
+
+    lib = _lib.load()
+    if not (gt.is_cuda and pred.is_cuda):
+        raise RuntimeError("transplat HIP ops need device tensors (no CPU path)")
+    if gt.shape != pred.shape:
+        raise ValueError(f"lpips: ground truth {tuple(gt.shape)} != prediction {tuple(pred.shape)}")
+    if gt.dim() != 4 or gt.shape[1] != 3:
+        raise ValueError(f"lpips: expected [n, 3, H, W] images, got {tuple(gt.shape)}")
+    n, _, h, w = gt.shape
+    if h < MIN_SIZE or w < MIN_SIZE:
+        raise ValueError(f"lpips: a {h} x {w} image leaves the fifth VGG block an empty map (H, W >= {MIN_SIZE})")
+    if net.device != gt.device:
+        raise RuntimeError(f"lpips: weights on {net.device}, images on {gt.device} (use LpipsVGG.to)")
+    out = torch.empty((n,), dtype=torch.float32, device=gt.device)
+    layers = torch.empty((n, len(VGG_BLOCKS)), dtype=torch.float32, device=gt.device) if return_layers else None
+    g, p = _f32(gt), _f32(pred)
+    shapes = [(net.lins[k].shape[0], h >> k, w >> k) for k in range(len(VGG_BLOCKS))]
+    blocks = [int(lib.tsplat_lpips_tap_blocks(*s)) for s in shapes]
+    pixels = [hk * wk for _, hk, wk in shapes]
+    for at in range(0, n, LPIPS_CHUNK):
+        m = min(LPIPS_CHUNK, n - at)
+        ws = torch.empty(m * sum(blocks), dtype=torch.float64, device=gt.device)
+        x = lpips_scale(g[at:at + m], p[at:at + m])
+        conv, offset = 0, 0
+        for k, count in enumerate(VGG_BLOCKS):
+            for _ in range(count):
+                weight, bias = net.convs[conv]
+                x = conv3x3_wino(x, weight, bias, act="relu", precision="fp32")
+                conv += 1
+            x = _lpips_tap_into(x, net.lins[k], ws[offset:offset + m * blocks[k]], pool=k + 1 < len(VGG_BLOCKS))
+            offset += m * blocks[k]
+        _lpips_reduce(ws, m, blocks, pixels, out[at:at + m], layers[at:at + m] if return_layers else None)
+    return (out, layers) if return_layers else out
+
+
 # DINOv2's attention in split-bf16 precision inside dense_precision("bf16x3") (tsplat_mha_x3_fwd) for
 # up to _MHA_X3_ROWS tokens per call: same-box C2 (2 x 325 tokens) 446.9 / 447.8 vs 445.6 / 445.5
 # views/s with the exact-fp32 kernel, but C3 (16 x 325) 900.1 / 899.8 vs 903.4 / 902.1 -- there the
