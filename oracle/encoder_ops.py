@@ -382,16 +382,6 @@ def conv_bias_act(conv, x, act: str = "none", residual=None, site: str = "", ext
     return y
 
 
-def conv2d_direct_ok(x, weight, stride: int = 1, padding=None, c2: int = 0, upsample: bool = False) -> bool:
-    """Every 2-D convolution the direct kernel takes (so CPU model runs exercise its call sites)."""
-    if weight.dim() == 3:
-        weight = weight.unsqueeze(-1)
-    k = weight.shape[-1]
-    pad = padding[0] if isinstance(padding, (tuple, list)) else (padding if padding is not None else k // 2)
-    return (x.dim() == 4 and k in (1, 3) and stride in (1, 2) and not (upsample and stride != 1) and pad == k // 2
-            and weight.shape[1] == x.shape[1] + c2 and x.shape[1] % 2 == 0 and c2 % 2 == 0)
-
-
 def conv2d_direct(x1, weight, bias=None, stride: int = 1, x2=None, upsample: bool = False):
     """nn.Conv2d(padding = k // 2) of cat([x1, x2], 1), nearest-upsampled 2x first if upsample:
     the reference ldm_unet chains ResBlock(cat([h, skip])) (unet.py:1096-1100), Upsample
@@ -540,7 +530,6 @@ def attention_merge(q, k, v, h: int, w: int, num_splits: int, with_shift: bool, 
 
 KERNEL_RESTATEMENTS = ("window_attention", "uv_coarse", "uv_cross", "msda", "msda_raw", "ms_deform_attn", "gaussian_adapter", "group_norm",
                        "sh_rotation", "fused_linear", "attention_merge", "instance_norm",
-                       "conv_bias_act", "mha", "residual_ln", "depth_softmax", "depth_tail", "conv2d_direct_ok",
-                       "conv2d_direct", "conv2d_nhwc_ok", "conv2d_nhwc",
-                       "upsample_bilinear_act", "qkv_attention_cf",
+                       "conv_bias_act", "mha", "residual_ln", "depth_softmax", "depth_tail", "conv2d_nhwc_ok",
+                       "conv2d_nhwc", "upsample_bilinear_act", "qkv_attention_cf",
                        "conv_nhwc_epilogue", "resize_bilinear_nhwc")

@@ -134,15 +134,17 @@ def test_square():
 
 @pytest.mark.parametrize("dilation", [1, (1, 1), 2, (2, 2)])
 def test_conv2d_fallback_dilation(dilation, monkeypatch):
-    """An int or a pair dilation; only dilation 1 is offered to the bf16x3 kernels, and on host
-    tensors every case is F.conv2d."""
-    offered = []
-    real = K._conv2d_x3_libfree
-    monkeypatch.setattr(K, "_conv2d_x3_libfree", lambda *a: offered.append(a) or real(*a))
+    """An int or a pair dilation; the call is described once, only dilation 1 is offered to the bf16x3
+    kernels (asked as if on the device in that mode), and on host tensors every case is F.conv2d."""
+    asked = []
+    real = K.conv_route
+    monkeypatch.setattr(K, "conv_route", lambda call, *a, **k: asked.append(call) or real(call, *a, **k))
     x, w, b = _weight((2, 4, 9, 11), 4), _weight((6, 4, 3, 3), 5), _weight((6,), 6)
     got = K.conv2d_fallback(x, w, b, 1, 2, dilation, 1)
     assert torch.equal(got, F.conv2d(x, w, b, 1, 2, dilation, 1))
-    assert len(offered) == (1 if dilation in (1, (1, 1)) else 0)
+    assert len(asked) == 1 and asked[0].dilation == (1 if dilation in (1, (1, 1)) else 2)
+    offered = [real(K.conv_call(w, (x,), 1, pad, dilation, on_gpu=True, dense="bf16x3"), K.SITE_LIBFREE) for pad in (1, 2)]
+    assert offered == (["wino_joined", None] if dilation in (1, (1, 1)) else [None, None])
 
 
 # (ksplit, zsplit) per _ZSPLIT in (-1, 0, 2), by case: literals from a run of the loops of the commit

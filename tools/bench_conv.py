@@ -1,7 +1,6 @@
 """Direct conv kernel (tsplat_conv2d_f32_fwd) vs MIOpen (algorithm search on, cat / upsample glue
 included as the module path runs it) on the U-Nets' convolution shapes, graph-timed; `route` is
-what the dispatch rules pick for the shape (wino = conv3x3_wino_ok, direct = conv2d_direct_ok,
-else MIOpen). --scale 4 multiplies the batch (2 views x b = 1 -> b = 4 x 2 = 8 maps; C2 b = 8)."""
+the route the U-Net glue takes for the shape (kernels.conv_route on SITE_UNET). --scale 4 multiplies the batch (2 views x b = 1 -> b = 4 x 2 = 8 maps; C2 b = 8)."""
 import argparse
 
 import torch
@@ -71,12 +70,10 @@ with torch.no_grad():
         t1 = timeit(ref)
         t2 = timeit(lambda: K.conv2d_direct(x1, wt, b, st, x2=x2, upsample=up))
         err = (K.conv2d_direct(x1, wt, b, st, x2=x2, upsample=up) - ref()).abs().max().item()
-        hh, ww = (2 * h, 2 * w) if up else (h, w)
-        gf = 2.0 * n * (hh // st) * (ww // st) * co * (c1 + c2) * k * k / 1e9
-        route = ("wino" if not up and K.conv3x3_wino_ok(x1, wt, st, k // 2, extra=(x2,) if x2 is not None else ())
-                 else "direct" if K.conv2d_direct_ok(x1, wt, st, c2=c2, upsample=up) else "miopen")
+        call = K.conv_call(wt, (x1,) if x2 is None else (x1, x2), st, k // 2, upsample=up)
+        gf, route = call.flop / 1e9, K.conv_route(call, K.SITE_UNET)
         tot[0] += t1 * calls
         tot[1] += t2 * calls
-        print(f"{t1:8.1f} {t2:8.1f} {gf:6.3f} {gf / t2 * 1e3:6.1f} {calls:5d}  {route:6s} "
+        print(f"{t1:8.1f} {t2:8.1f} {gf:6.3f} {gf / t2 * 1e3:6.1f} {calls:5d}  {route:11s} "
               f"{(n, c1, c2, h, w, co, k, st, up)} err={err:.1e}", flush=True)
 print(f"total per step: miopen {tot[0]:.1f} us, direct {tot[1]:.1f} us")

@@ -9,6 +9,7 @@ import ctypes
 import functools
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
@@ -368,30 +369,27 @@ _AFFINE_ID: dict = {}
 
 
 def conv_bias_act(conv, x, act: str = "none", residual=None, extra=()):
-    """conv(x) + bias -> act [-> + residual (-> relu for "relu")] with the bias, activation and
-    residual in ONE pass after the bias-free MIOpen convolution (tsplat_bias_act_fwd). Under bf16
-    autocast (config C3's dense layers) or for outputs the kernel's float4 layout cannot take, the
-    module's own forward and PyTorch activations run instead (dense-layer glue, same math).
+    """conv(cat([x, *extra])) + bias -> act [-> + residual (-> relu for "relu")]: the route of SITE_HEAD.
+    The bf16 and Winograd kernels read the concatenation in place with bias and activation in their epilogue;
+    any other route runs bias-free and then bias, activation and residual in ONE pass (tsplat_bias_act_fwd).
+    Under bf16 autocast or for outputs the kernel's float4 layout cannot take, the module and PyTorch run.
     Used on the depth predictor's full-resolution conv -> GELU -> conv heads (+0.4 % e2e); on the
     DPT ResidualConvUnits the bias-free convolutions measured 3 % slower end to end, so those keep
     the module path."""
     if not x.is_cuda:
         raise RuntimeError("transplat HIP ops need device tensors (no CPU path)")
-    if (residual is None and act in _ACTS and getattr(conv, "padding_mode", "zeros") == "zeros"
-            and conv_bf16_ok(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, extra)):
-        return conv_bf16(x, conv.weight, conv.bias, act, extra)  # bf16 autocast: bias + act fused
-    fused = (not torch.is_autocast_enabled("cuda") and x.dtype == torch.float32
-             and getattr(conv, "padding_mode", "zeros") == "zeros")
-    if (fused and residual is None and act in _WINO_ACT
-            and conv3x3_wino_ok(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, extra,
-                                vs_miopen=True)):
-        # the Winograd kernel reads the concatenation in place and applies the bias and the
-        # activation in its epilogue
-        return conv3x3_wino(x, conv.weight, conv.bias, act, extra)
+    srcs = (x, *extra)
+    call = conv_module_call(conv, srcs)
+    fused = call.autocast is None and x.dtype == torch.float32 and call.zeros
+    # the bf16 and Winograd kernels' own epilogues: bias and their activations, no residual
+    skip = [r for r, acts in (("bf16", _ACTS), ("wino", _WINO_ACT)) if residual is not None or act not in acts]
+    route = conv_route(call, SITE_HEAD, skip)
+    if route in ("bf16", "wino"):
+        return conv_run(route, call, conv.weight, srcs, conv.bias, act)
     if extra:
-        x = torch.cat([x, *extra], dim=1)
+        x = torch.cat(srcs, dim=1)
     if fused:
-        y = conv2d_fallback(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+        y = conv_run(route, call.joined(), conv.weight, (x,))
         # the kernel indexes the residual with y's NCHW layout: a broadcastable residual ([C, 1, 1],
         # a batch-1 map) takes the module path, where `y + residual` broadcasts
         fused = ((y.shape[-1] * y.shape[-2]) % 4 == 0 and y.is_contiguous()
@@ -953,8 +951,8 @@ def mha(qkv, heads: int, scale: float, bias=None, precision: str | None = None):
     return out
 
 
-# Which convolutions go to tsplat_conv2d_f32_fwd: "auto" (the latency-bound ones, see
-# conv2d_direct_ok), "off" (always MIOpen), "all" (every shape the kernel takes; tests / A/B)
+# Which convolutions go to the direct kernels (conv2d_direct): "auto" (the latency-bound ones, see
+# _wins_direct), "off" (never), "all" (every shape they take; tests / A/B)
 _CONV_MODE = os.environ.get("TSPLAT_CONV", "auto")
 _CONV_MAX_FLOP = 1.5e9  # above this MIOpen's kernels are as fast or faster (tools/bench_conv.py)
 # 1x1 launch shape: grid cap in waves and minimum ci pairs per wave. Same-box A/B (round-2 session script ab_conv1.sh, pruned in round 5):
@@ -1044,36 +1042,6 @@ def conv_pack_weight(weight):
     return _derived(weight, "conv", _pack_conv)
 
 
-def conv2d_direct_ok(x, weight, stride: int = 1, padding=None, c2: int = 0, upsample: bool = False,
-                     force: bool = False) -> bool:
-    """True when tsplat_conv2d_f32_fwd takes this convolution and (mode "auto") it is a
-    latency-bound one where the direct kernel beats MIOpen (force: whenever it takes it)."""
-    if _CONV_MODE == "off" or not x.is_cuda or torch.is_autocast_enabled("cuda"):
-        return False
-    if x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4:
-        return False
-    if weight.dim() == 3:  # Conv1d, kernel 1, on x viewed as [n, c, t, 1]
-        if weight.shape[-1] != 1:
-            return False
-        weight = weight.unsqueeze(-1)
-    co, ci, k, k2 = weight.shape
-    if k != k2 or k not in (1, 3) or stride not in (1, 2) or (upsample and stride != 1):
-        return False
-    c1 = x.shape[1]
-    if _square(padding if padding is not None else k // 2) != k // 2 or ci != c1 + c2 or c1 % 2 or c2 % 2:
-        return False
-    if _CONV_MODE == "all" or force:
-        return True
-    h, w = x.shape[2] * (2 if upsample else 1), x.shape[3] * (2 if upsample else 1)
-    npx = x.shape[0] * (h // stride) * (w // stride)
-    flop = 2.0 * npx * co * ci * k * k
-    # (since the batch loads are scheduled ahead of the MFMAs, the few-tile / long-reduction 3x3s
-    # -- 2 x 256 -> 128 at 16^2 -- also beat MIOpen: 23.5 vs 25.7 us, bench_conv.py)
-    if npx <= 512:
-        return True  # tiny maps with long reductions (the DPT's 768 -> 768 stride-2 at 18^2, 1.7 GFLOP)
-    return flop <= _CONV_MAX_FLOP
-
-
 def _pack_conv_x3(weight):
     co, ci = weight.shape[:2]
     k = weight.shape[2] if weight.dim() == 4 else 1
@@ -1101,7 +1069,7 @@ def conv_x3_wins(npx: int, ci: int, co: int, k: int) -> bool:
     3x3s lost 1-2 us each (18 units of 8 gathered channels over 16 waves)."""
     if k == 1:
         return True
-    return ci >= 64 and 2.0 * npx * co * ci * k * k >= 0.5e9
+    return ci >= 64 and _conv_flop(npx, co, ci, k) >= 0.5e9
 
 
 def _conv_x3_shape(tiles: int, units: int):
@@ -1128,15 +1096,6 @@ def _conv2d_direct_x3(lib, a, b, c1, c2, weight, bias, n, h, w, co, k, stride, u
                                       _lib.ptr(part), _lib.ptr(cnt), _lib.stream_ptr(y.device))
     _lib.check(rc, "tsplat_conv2d_bf16x3_fwd")
     return y
-
-
-def conv1x1_scaled_ok(x, weight) -> bool:
-    """True when conv1x1_scaled takes conv2d(x * scale, weight): the bf16x3 dense mode's 1x1 / stride-1
-    convolutions that conv2d_forward runs on tsplat_conv2d_bf16x3_fwd (the same launch plan, so the
-    same bits)."""
-    return (split_mode() and weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1) and x.is_contiguous()
-            and conv2d_direct_ok(x, weight, 1, 0) and conv_x3_wins(x.shape[0] * x.shape[2] * x.shape[3],
-                                                                     x.shape[1], weight.shape[0], 1))
 
 
 def conv1x1_scaled(x, scale, weight, bias=None, channel_last: bool = False):
@@ -1231,71 +1190,10 @@ def wino_pack_weight(weight):
 WINO_MAX_CI_PAD = 1024  # winoconv.hip kMaxCiPad: input channels (padded to 16) of one launch
 
 
-def conv3x3_wino_ok(x, weight, stride=1, padding=1, dilation=1, groups=1, extra=(), vs_miopen=False,
-                    force=False) -> bool:
-    """True when tsplat_conv3x3_wino_f32_fwd takes conv2d(x, weight) on the NCHW map x and (mode
-    "auto") it is one of the 3x3s where it beats MIOpen's kernels (tools/bench_wino.py): above the
-    direct kernel's FLOP range (unless `vs_miopen`: the caller's alternative is MIOpen, which the
-    Winograd kernel also beats below that range, e.g. 96 -> 96 at 64^2: 20.8 vs 27.1 us), and not
-    the few-tile / long-reduction shapes (256 input channels at 32^2: 64 workgroups of 32 serial
-    chunks) where MIOpen stays faster."""
-    if _WINO_MODE == "off" or not x.is_cuda or torch.is_autocast_enabled("cuda") or len(extra) > 5:
-        return False
-    for t in (x, *extra):
-        if (t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() or t.device != x.device
-                or t.shape[0] != x.shape[0] or t.shape[2:] != x.shape[2:]):
-            return False
-    if weight.dtype != torch.float32 or weight.dim() != 4:
-        return False
-    if tuple(weight.shape[2:]) != (3, 3) or _square(stride) != 1 or _square(padding) != 1:
-        return False
-    ci = sum(t.shape[1] for t in (x, *extra))
-    if _square(dilation) != 1 or groups != 1 or weight.shape[1] != ci:
-        return False
-    if (ci + 15) // 16 * 16 > WINO_MAX_CI_PAD:  # the launch's LDS plane table (winoconv.hip kMaxCiPad)
-        return False
-    if _WINO_MODE == "all" or force:
-        return True
-    n, _, h, w = x.shape
-    co = weight.shape[0]
-    groups_ = n * ((h + 1) // 2 * ((w + 1) // 2) + 31) // 32 * ((co + 31) // 32)  # ~ workgroups
-    vs_miopen = vs_miopen and _WINO_MODE != "big"  # "big": the FLOP floor everywhere (A/B knob)
-    # (a head with a handful of output channels on a large map -- 64 -> 2 at 256^2 -- still beats
-    # MIOpen's 53 us with one mostly idle 32-channel output block: the transform dominates there)
-    return (ci >= 16 and (co >= 16 or (vs_miopen and n * h * w >= 65536))
-            and (vs_miopen or 2.0 * n * h * w * co * ci * 9 > _CONV_MAX_FLOP)
-            and (ci <= 192 or groups_ >= 256))
-
-
-def conv2d_forward(mod, x):
-    """nn.Conv2d.forward (installed on the encoder's Conv2d modules by install_conv2d_dispatch):
-    the 3x3s that conv3x3_wino_ok admits on the Winograd kernel, the latency-bound 1x1 / 3x3
-    (stride 1 or 2) ones that conv2d_direct_ok admits on the direct kernel (bias in the epilogue
-    instead of MIOpen's separate bias launch), the rest through MIOpen."""
-    if mod.padding_mode == "zeros" and mod.groups == 1 and _square(mod.dilation) == 1:
-        if conv_bf16_ok(x, mod.weight, mod.stride, mod.padding, mod.dilation, mod.groups):
-            return conv_bf16(x, mod.weight, mod.bias)
-        if conv3x3_wino_ok(x, mod.weight, mod.stride, mod.padding, mod.dilation, mod.groups, vs_miopen=True):
-            return conv3x3_wino(x, mod.weight, mod.bias)
-        st, pad = _square(mod.stride), _square(mod.padding)
-        if (st > 0 and x.is_contiguous() and x.dtype == torch.float32
-                and conv2d_direct_ok(x, mod.weight, st, mod.padding)):
-            return conv2d_direct(x, mod.weight, mod.bias, st)
-        y = _conv2d_x3_libfree(x, mod.weight, mod.bias, mod.stride, mod.padding)
-        if y is not None:
-            return y
-        if (st > 0 and _square(mod.kernel_size) > 3 and pad >= 0 and x.is_cuda
-                and x.dtype == torch.float32 and mod.weight.dtype == torch.float32
-                and not torch.is_autocast_enabled("cuda")):
-            return conv_unfold_gemm(x, mod.weight, mod.bias, st, pad)
-    return mod._conv_forward(x, mod.weight, mod.bias)
-
-
 # Convolutions the encoder used to leave on MIOpen (round 5): the UniMatch CNN's 7x7 stride-2 stem
 # and the DPT's transposed convolutions (kernel = stride). MIOpen picks their algorithms by timing
 # (cudnn.benchmark), so their bits could differ from process to process; these forms are exact fp32
-# and fixed. In the bf16x3 mode every remaining Conv2d runs on the split-bf16 Winograd / direct kernels
-# (_conv2d_x3_libfree).
+# and fixed. (bf16x3 mode, every remaining Conv2d: SITE_LIBFREE.)
 
 
 def conv_unfold_gemm(x, weight, bias, stride: int, padding: int):
@@ -1340,35 +1238,6 @@ def conv_transpose_forward(mod, x):
             and not torch.is_autocast_enabled("cuda")):
         return conv_transpose_direct(x.contiguous(), mod.weight, mod.bias, st)
     return torch.nn.ConvTranspose2d.forward(mod, x)
-
-
-def _conv2d_x3_libfree(x, weight, bias, stride, padding):
-    """bf16x3 mode, a convolution the shape rules leave to MIOpen (C3's b = 8 levels): the split-bf16
-    Winograd for the 3x3 / stride-1 ones up to 256 input channels, the direct kernel for the rest --
-    per shape within ~1.4x of MIOpen either way, 1.26 vs 1.28 ms over C3's 18 such calls
-    (tools/c3_libconv.py, profiles/r6/c3_libconv.log), and no library convolution left. None when
-    the shape is not one of those (or in another mode)."""
-    if not (split_mode() and x.is_cuda and x.dim() == 4 and x.is_contiguous()
-            and x.dtype == torch.float32 and weight.dim() == 4):
-        return None
-    st = _square(stride)
-    if st <= 0:
-        return None
-    if weight.shape[1] <= 256 and conv3x3_wino_ok(x, weight, stride, padding, force=True):
-        return conv3x3_wino(x, weight, bias)
-    if conv2d_direct_ok(x, weight, st, padding, force=True):
-        return conv2d_direct(x, weight, bias, st)
-    return None
-
-
-def conv2d_fallback(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
-    """F.conv2d for the model code's last-resort branches: in the bf16x3 mode through
-    _conv2d_x3_libfree first, so no convolution of that mode reaches MIOpen."""
-    if groups == 1 and _square(dilation) == 1:
-        y = _conv2d_x3_libfree(x, weight, bias, stride, padding)
-        if y is not None:
-            return y
-    return F.conv2d(x, weight, bias, stride, padding, dilation, groups)
 
 
 def install_conv2d_dispatch(module) -> int:
@@ -1728,7 +1597,7 @@ def conv3x3_wino(x, weight, bias=None, act: str = "none", extra=(), precision: s
     co = weight.shape[0]
     if WINO_FLOP_LOG is not None:
         ci = sum(t.shape[1] for t in srcs)
-        WINO_FLOP_LOG.append((2.0 * 16 * ci * co * n * ((h + 1) // 2) * ((w + 1) // 2), 2.0 * n * h * w * co * ci * 9))
+        WINO_FLOP_LOG.append((2.0 * 16 * ci * co * n * ((h + 1) // 2) * ((w + 1) // 2), _conv_flop(n * h * w, co, ci, 3)))
     y = torch.empty((n, co, h, w), dtype=torch.float32, device=x.device)
     pb = _f32(bias) if bias is not None else None
     ptrs, chans = _src_arrays(srcs)
@@ -1780,33 +1649,6 @@ def _bf16_rounded_bias(bias):
     return _derived(bias, "bf16_bias", lambda b: b.to(torch.bfloat16).float().contiguous())
 
 
-def conv_bf16_ok(x, weight, stride=1, padding=None, dilation=1, groups=1, extra=(), upsample: bool = False) -> bool:
-    """True when conv2d(up(cat([x, *extra], 1)), weight) runs under bf16 autocast and fits
-    tsplat_conv2d_bf16_fwd: 3x3 / padding 1 or 1x1 / padding 0, stride 1, NCHW contiguous fp32 or
-    bf16 sources (any channel counts, dtypes may differ) with the convolved width a multiple of 8, at
-    most 4 sources; up = optional nearest 2x upsample read in place."""
-    if (not x.is_cuda or not torch.is_autocast_enabled("cuda")
-            or torch.get_autocast_dtype("cuda") != torch.bfloat16 or len(extra) > 3):
-        return False
-    for t in (x, *extra):
-        if (t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 4 or not t.is_contiguous()
-                or t.device != x.device or t.shape[0] != x.shape[0] or t.shape[2:] != x.shape[2:]
-                or t.numel() >= 2 ** 31):
-            return False
-    # [co, ci, k, k] (k = 1, 3) or a 1x1 Conv1d's [co, ci, 1] (on a [n, c, 1, t] view of its input)
-    if not ((weight.dim() == 4 and weight.shape[2] == weight.shape[3] and weight.shape[2] in (1, 3))
-            or (weight.dim() == 3 and weight.shape[2] == 1)) or groups != 1:
-        return False
-    k = weight.shape[2]
-    if _square(stride) != 1 or _square(padding if padding is not None else k // 2) != k // 2 or _square(dilation) != 1:
-        return False
-    n, _, h, w = x.shape
-    if upsample:
-        h, w = 2 * h, 2 * w
-    ci = sum(t.shape[1] for t in (x, *extra))
-    return weight.shape[1] == ci and w % 8 == 0 and n * max(weight.shape[0], ci) * h * w < 2 ** 31
-
-
 def conv_bf16(x, weight, bias=None, act: str = "none", extra=(), upsample: bool = False):
     """act(conv2d(up(cat([x, *extra], 1)), weight, bias, 1, k // 2)) as autocast would compute it in
     bf16 (bf16-rounded sources, weights and bias, fp32 accumulation), output bf16 NCHW, in one
@@ -1830,12 +1672,244 @@ def conv_bf16(x, weight, bias=None, act: str = "none", extra=(), upsample: bool 
     return y
 
 
+# ---------------------------------------------------------------- which kernel a convolution takes
+# ConvCall describes a call; per kernel family conv_can_* is what its C entries run and _wins_* where it measured
+# faster (module constants read at call time); SITE_*: each site's order. conv_route picks, conv_run launches.
+
+
+def _conv_flop(npx: int, co: int, ci: int, k: int) -> float:
+    return 2.0 * npx * co * ci * k * k
+
+
+class ConvCall(namedtuple("ConvCall", "co ci k chans fits n h w npx flop stride padding dilation groups upsample dtypes "
+                                      "wdtype contiguous small on_gpu autocast dense conv1d zeros raw")):
+    """conv(up(cat(sources, 1)), weight), normalised once (conv_call). ci: the weight's input channels, chans: the
+    sources'; fits: every source a 4-D map on one device, same batch and map, channels adding up to ci. k / stride /
+    padding / dilation: _square values; n, h, w: the convolved map, after the optional 2x upsample; npx = n (h // stride)
+    (w // stride), what the thresholds were measured against; contiguous: all sources NCHW-contiguous; small: every
+    tensor under 2^31 elements; autocast: the CUDA autocast dtype or None; conv1d: a Conv1d ([n, c, t] as the 1 x t
+    map); zeros: the padding mode; raw: (stride, padding, dilation) for the library call."""
+
+    def joined(self) -> "ConvCall":
+        """The call on the materialised input (torch.cat, F.interpolate): NCHW-contiguous if every source was."""
+        dtype = self.dtypes[0] if len(set(self.dtypes)) == 1 else torch.float32
+        return self._replace(chans=(sum(self.chans),), dtypes=(dtype,), upsample=False)
+
+
+def conv_call(weight, sources, stride=1, padding=None, dilation=1, groups=1, upsample: bool = False, *, c2: int = 0,
+              padding_mode: str = "zeros", on_gpu=None, autocast="current", dense=None) -> ConvCall:
+    """padding None: k // 2. c2: channels of a second source given by its count alone. on_gpu / autocast / dense:
+    stated instead of read from the tensors and the process, so routes can be asked for without a device."""
+    conv1d = weight.dim() == 3
+    shapes = [(t.shape[0], t.shape[1], 1, t.shape[2]) if conv1d and t.dim() == 3 else tuple(t.shape) for t in sources]
+    x, (n, _, h, w) = sources[0], (shapes[0] if len(shapes[0]) == 4 else (shapes[0][0], 0, 0, 0))
+    h, w = (2 * h, 2 * w) if upsample else (h, w)
+    co, ci = weight.shape[:2]
+    k = weight.shape[2] if conv1d or (weight.dim() == 4 and weight.shape[2] == weight.shape[3]) else -1
+    chans = tuple(s[1] for s in shapes) + ((c2,) if c2 else ())
+    fits = sum(chans) == ci and all(len(s) == 4 and s[0] == n and s[2:] == shapes[0][2:] and t.device == x.device
+                                    for s, t in zip(shapes, sources))
+    st, dil = _square(stride), _square(dilation)
+    npx = n * (h // st) * (w // st) if st > 0 else 0
+    if autocast == "current":
+        autocast = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
+    return ConvCall(co, ci, k, chans, fits, n, h, w, npx, _conv_flop(npx, co, ci, k), st,
+                    _square(padding) if padding is not None else k // 2, dil, groups, bool(upsample),
+                    tuple(t.dtype for t in sources), weight.dtype, all(t.is_contiguous() for t in sources),
+                    max(n * max(co, ci) * h * w, *(t.numel() for t in sources)) < 2 ** 31,
+                    all(t.is_cuda for t in sources) if on_gpu is None else on_gpu, autocast,
+                    _DENSE if dense is None else dense, conv1d, padding_mode == "zeros",
+                    (stride, padding if padding is not None else k // 2, dilation))
+
+
+def _plain(c: ConvCall, dtypes) -> bool:
+    """Zero-padded, groups 1, dilation 1, padding k // 2, device maps of `dtypes` (a Conv1d: kernel 1)."""
+    return (c.on_gpu and c.fits and c.zeros and all(d in dtypes for d in c.dtypes) and c.groups == 1
+            and c.dilation == 1 and c.padding == c.k // 2 and not (c.conv1d and c.k != 1))
+
+
+def conv_can_bf16(c: ConvCall) -> bool:
+    """tsplat_conv2d_bf16_fwd: under bf16 autocast, 3x3 / 1x1, stride 1, at most 4 NCHW-contiguous fp32 or
+    bf16 sources (any channel counts), the convolved width a multiple of 8, tensors under 2^31 elements."""
+    return (c.autocast == torch.bfloat16 and _plain(c, (torch.float32, torch.bfloat16)) and c.k in (1, 3)
+            and c.stride == 1 and len(c.chans) <= 4 and c.contiguous and c.w % 8 == 0 and c.small)
+
+
+def conv_can_direct(c: ConvCall) -> bool:
+    """tsplat_conv2d_f32_zsplit_fwd / tsplat_conv2d_bf16x3_fwd (conv2d_direct picks by conv_x3_wins): fp32 1x1 / 3x3,
+    stride 1 or 2, one or two sources of even channel counts (copied if not contiguous), upsample only at stride 1."""
+    return (_CONV_MODE != "off" and c.autocast is None and _plain(c, (torch.float32,)) and c.wdtype == torch.float32
+            and c.k in (1, 3) and c.stride in (1, 2) and not (c.upsample and c.stride != 1) and len(c.chans) <= 2
+            and all(ch % 2 == 0 for ch in c.chans))
+
+
+def conv_can_wino(c: ConvCall) -> bool:
+    """The Winograd entries and tsplat_conv3x3_few_bf16x3_fwd (conv3x3_wino picks by dense mode and _few_ok): fp32 3x3 /
+    stride 1, at most 6 NCHW-contiguous sources, ci padded to 16 within the LDS plane table (winoconv.hip kMaxCiPad)."""
+    return (_WINO_MODE != "off" and c.autocast is None and _plain(c, (torch.float32,)) and c.wdtype == torch.float32
+            and c.k == 3 and c.stride == 1 and not c.upsample and len(c.chans) <= 6 and c.contiguous
+            and (c.ci + 15) // 16 * 16 <= WINO_MAX_CI_PAD)
+
+
+def _can_library_gemm(c: ConvCall) -> bool:
+    """fp32 outside autocast: a 1x1 / stride 1 / padding 0 (batched GEMM, "gemm1x1"), a kernel above 3 ("unfold")."""
+    c = c.joined()
+    form = (c.stride == 1 and c.padding == 0) if c.k == 1 else (c.k > 3 and c.stride > 0 and c.padding >= 0 and c.dilation == 1)
+    return (form and c.on_gpu and c.zeros and c.autocast is None and c.dtypes[0] == c.wdtype == torch.float32
+            and c.groups == 1 and not c.conv1d)
+
+
+def _wins_direct(c: ConvCall) -> bool:
+    """The latency-bound convolutions, where the direct kernel beats MIOpen (tools/bench_conv.py)."""
+    # (the few-tile / long-reduction 3x3s -- 2 x 256 -> 128 at 16^2 -- also beat MIOpen, 23.5 vs 25.7 us, since the batch
+    # loads run ahead of the MFMAs; npx <= 512: tiny maps, long reductions, the DPT's 768 -> 768 stride-2 at 18^2, 1.7 GFLOP)
+    return _CONV_MODE == "all" or c.npx <= 512 or c.flop <= _CONV_MAX_FLOP
+
+
+def _wins_wino(c: ConvCall, vs_miopen: bool = False) -> bool:
+    """The 3x3s where the Winograd kernel beats MIOpen's kernels (tools/bench_wino.py): above the direct kernel's
+    FLOP range (unless `vs_miopen`: the site's alternative is MIOpen, which the Winograd kernel also beats below
+    that range, e.g. 96 -> 96 at 64^2: 20.8 vs 27.1 us), and not the few-tile / long-reduction shapes (256 input
+    channels at 32^2: 64 workgroups of 32 serial chunks) where MIOpen stays faster."""
+    if _WINO_MODE == "all":
+        return True
+    groups_ = c.n * ((c.h + 1) // 2 * ((c.w + 1) // 2) + 31) // 32 * ((c.co + 31) // 32)  # ~ workgroups
+    vs_miopen = vs_miopen and _WINO_MODE != "big"  # "big": the FLOP floor everywhere (A/B knob)
+    # (a head with a handful of output channels on a large map -- 64 -> 2 at 256^2 -- still beats
+    # MIOpen's 53 us with one mostly idle 32-channel output block: the transform dominates there)
+    return (c.ci >= 16 and (c.co >= 16 or (vs_miopen and c.n * c.h * c.w >= 65536))
+            and (vs_miopen or c.flop > _CONV_MAX_FLOP) and (c.ci <= 192 or groups_ >= 256))
+
+
+_wins_wino_vs_lib = lambda c: _wins_wino(c, vs_miopen=True)  # noqa: E731
+_x3 = lambda c: c.dense == "bf16x3"  # noqa: E731
+_joined = lambda rule: lambda c: rule(c.joined())  # noqa: E731
+
+
+# Per site (route, can, wins) in the order tried: what conv_run launches ("_joined": on the materialised concat /
+# upsample), the hard constraints, the thresholds. SITE_LIBFREE: bf16x3 mode, a convolution the shape rules leave to
+# MIOpen (C3's b = 8 levels): the split-bf16 Winograd for the 3x3 / stride-1 ones up to 256 input channels, the direct
+# kernel for the rest (NCHW-contiguous 2-D maps) -- per shape within ~1.4x of MIOpen either way, 1.26 vs 1.28 ms over
+# C3's 18 such calls (tools/c3_libconv.py, profiles/r6/c3_libconv.log), and no library convolution left.
+SITE_LIBFREE = (
+    ("wino_joined", _joined(conv_can_wino), lambda c: _x3(c) and c.ci <= 256),
+    ("direct_joined", _joined(lambda c: c.contiguous and not c.conv1d and conv_can_direct(c)), _x3),
+)
+SITE_UNET = (  # ldm_unet.conv
+
+    ("bf16", conv_can_bf16, None),  # bf16 autocast (C3): 3x3 / 1x1 on bf16 MFMA, concat / upsample in place
+    ("direct", conv_can_direct, _wins_direct),  # the latency-bound low-resolution levels, the same in place
+    ("wino", conv_can_wino, _wins_wino),  # above the direct kernel's FLOP range; the skip concat in place
+    ("wino_joined", _joined(conv_can_wino), _joined(_wins_wino)),
+    # a full-resolution 1x1 (the 256^2 skips), [cout, cin] x [cin, h*w] per image: ~10 us, MIOpen's NCHW 1x1 took 45
+    ("gemm1x1", lambda c: c.k == 1 and _can_library_gemm(c), None),
+    *SITE_LIBFREE, ("library", None, None),
+)
+SITE_FORWARD = (  # the installed nn.Conv2d.forward
+    ("bf16", conv_can_bf16, None),
+    # before the direct kernel: the alternative here is MIOpen, which it beats below the direct kernel's FLOP ceiling too
+    ("wino", conv_can_wino, _wins_wino_vs_lib),
+    # bias in the epilogue instead of MIOpen's separate bias launch; channels-last maps stay on MIOpen
+    ("direct", lambda c: c.contiguous and conv_can_direct(c), _wins_direct),
+    *SITE_LIBFREE,
+    # the UniMatch CNN's 7x7 stride-2 stem: exact fp32 and fixed, where MIOpen picks by timing
+    ("unfold", lambda c: c.k > 3 and _can_library_gemm(c), None), ("library", None, None),
+)
+# conv_bias_act (+0.4 % e2e): bias + activation in the bf16 / Winograd epilogue, else bias-free + tsplat_bias_act_fwd
+SITE_HEAD = (("bf16", conv_can_bf16, None), ("wino", conv_can_wino, _wins_wino_vs_lib), *SITE_LIBFREE, ("library", None, None))
+
+
+def conv_route(call: ConvCall, site, skip=()) -> str | None:
+    """The first route of `site` that can run `call` and wins; skip: routes the caller cannot use; None: no candidate."""
+    return next((r for r, can, wins in site
+                 if r not in skip and (can is None or can(call)) and (wins is None or wins(call))), None)
+
+
+def conv_run(route: str, call: ConvCall, weight, sources, bias=None, act: str = "none"):
+    """Launch `route` (conv_route's answer for `call`) on the tensors `call` was built from."""
+    base = route.removesuffix("_joined")
+    if call.conv1d and base in ("bf16", "direct"):
+        # a 1x1 over [n, c, t]: the bf16 kernel needs the convolved width to be t ([n, c, 1, t]; MIOpen ran
+        # the 1-D form as im2col + GEMM), the direct kernel takes [n, c, t, 1]
+        dim = 2 if base == "bf16" else 3
+        return conv_run(route, call._replace(conv1d=False), weight, [t.unsqueeze(dim) for t in sources], bias,
+                        act).squeeze(dim)
+    x, rest, up = sources[0], tuple(sources[1:]), call.upsample
+    if base != route or base in ("gemm1x1", "unfold", "library"):
+        x = torch.cat(list(sources), dim=1) if rest else x
+        x = F.interpolate(x, scale_factor=2, mode="nearest") if up else x
+        rest, up = (), False
+    if base == "bf16":
+        return conv_bf16(x, weight, bias, act, rest, up)
+    if base == "wino":
+        return conv3x3_wino(x, weight, bias, act, rest)
+    if act != "none" or not call.zeros:
+        raise ValueError(f"route {route!r} has no activation epilogue / padding mode")
+    if base == "direct":
+        return conv2d_direct(x, weight, bias, call.stride, rest[0] if rest else None, up)
+    if base == "gemm1x1":
+        n, ci, h, w = x.shape
+        wm = weight.view(call.co, ci).expand(n, call.co, ci)
+        xm = x.contiguous().view(n, ci, h * w)
+        y = torch.baddbmm(bias.view(1, call.co, 1), wm, xm) if bias is not None else torch.bmm(wm, xm)
+        return y.view(n, call.co, h, w)
+    if base == "unfold":
+        return conv_unfold_gemm(x, weight, bias, call.stride, call.padding)
+    return (F.conv1d if call.conv1d else F.conv2d)(x, weight, bias, *call.raw, call.groups)
+
+
+def conv3x3_wino_ok(x, weight, stride=1, padding=1, dilation=1, groups=1, extra=(), vs_miopen=False, force=False) -> bool:
+    """conv_can_wino and _wins_wino (vs_miopen: against MIOpen; force: whenever the kernels take it)."""
+    c = conv_call(weight, (x, *extra), stride, padding, dilation, groups)
+    return conv_can_wino(c) and (force or _wins_wino(c, vs_miopen))
+
+
+def conv2d_direct_ok(x, weight, stride: int = 1, padding=None, c2: int = 0, upsample: bool = False,
+                     force: bool = False) -> bool:
+    """conv_can_direct and _wins_direct (force: whenever the kernels take it); c2: a second source's channels."""
+    c = conv_call(weight, (x,), stride, padding, upsample=upsample, c2=c2)
+    return conv_can_direct(c) and (force or _wins_direct(c))
+
+
+def conv_bf16_ok(x, weight, stride=1, padding=None, dilation=1, groups=1, extra=(), upsample: bool = False) -> bool:
+    """conv_can_bf16 of conv2d(up(cat([x, *extra], 1)), weight); up = optional nearest 2x upsample."""
+    return conv_can_bf16(conv_call(weight, (x, *extra), stride, padding, dilation, groups, upsample))
+
+
+def conv1x1_scaled_ok(x, weight) -> bool:
+    """True when conv1x1_scaled takes conv2d(x * scale, weight): the bf16x3 mode's 1x1 / stride-1 convolutions that
+    conv2d_forward runs on tsplat_conv2d_bf16x3_fwd (the same launch plan, so the same bits)."""
+    c = conv_call(weight, (x,), 1, 0)
+    return (_x3(c) and weight.dim() == 4 and c.k == 1 and c.contiguous and conv_can_direct(c) and _wins_direct(c)
+            and conv_x3_wins(c.npx, c.ci, c.co, 1))
+
+
 def conv2d_nhwc_ok(x, weight) -> bool:
     """True when tsplat_conv2d_f32_nhwc_fwd takes conv(x, weight) (stride 1, padding k // 2) on the
     channels-last map x and (mode "auto") it is latency-bound (same rule as conv2d_direct_ok)."""
     if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last) or x.shape[1] == 1:
         return False
     return conv2d_direct_ok(x, weight, 1, weight.shape[-1] // 2)
+
+
+def conv_module_call(mod, sources, upsample: bool = False) -> ConvCall:
+    return conv_call(mod.weight, sources, mod.stride, mod.padding, mod.dilation, mod.groups, upsample,
+                     padding_mode=getattr(mod, "padding_mode", "zeros"))
+
+
+def conv2d_forward(mod, x):
+    """nn.Conv2d.forward as install_conv2d_dispatch installs it: SITE_FORWARD's route, the library being the module."""
+    call = conv_module_call(mod, (x,))
+    route = conv_route(call, SITE_FORWARD)
+    if route == "library":
+        return mod._conv_forward(x, mod.weight, mod.bias)
+    return conv_run(route, call, mod.weight, (x,), mod.bias)
+
+
+def conv2d_fallback(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
+    """F.conv2d for the model's last-resort branches; in the bf16x3 mode SITE_LIBFREE's kernels where they take it."""
+    call = conv_call(weight, (x,), stride, padding, dilation, groups)
+    return conv_run(conv_route(call, SITE_LIBFREE) or "library", call, weight, (x,), bias)
 
 
 def conv2d_nhwc(x, weight, bias=None, residual=None, relu_in: bool = False):

@@ -81,7 +81,7 @@ class ResidualConvUnit(nn.Module):
     def forward(self, x, skip=None):
         """out(x) + x (+ skip: the FeatureFusionBlock's other input, added in the same pass)."""
         if (_nchw3() and not self.bn and isinstance(self.activation, nn.ReLU) and x.is_cuda and x.is_contiguous()
-                and kernels.conv3x3_wino_ok(x, self.conv1.weight, vs_miopen=True)
+                and kernels.conv_route(kernels.conv_module_call(self.conv1, (x,)), kernels.SITE_FORWARD) == "wino"
                 and (skip is None or skip.is_contiguous())):
             # bf16x3 mode, NCHW: relu -> conv1 + bias, relu -> conv2 + bias + x (+ skip), two launches
             out = kernels.conv3x3_wino(x, self.conv1.weight, self.conv1.bias, relu_in=True)
@@ -196,7 +196,8 @@ class DPTHead(nn.Module):
         out_feature = final_out.detach()
         final_out = _resize(final_out, {"size": (int(patch_h * 14), int(patch_w * 14))}, True)
         oc = s.output_conv2
-        if _nchw3() and final_out.is_contiguous() and kernels.conv3x3_wino_ok(final_out, oc[0].weight, vs_miopen=True):
+        if (_nchw3() and final_out.is_contiguous()
+                and kernels.conv_route(kernels.conv_module_call(oc[0], (final_out,)), kernels.SITE_FORWARD) == "wino"):
             h = kernels.conv3x3_wino(final_out, oc[0].weight, oc[0].bias, act="relu")
             if raw_tail and isinstance(oc[3], nn.ReLU) and isinstance(oc[4], nn.Identity):
                 return oc[2](h), out_feature  # the ReLUs are the caller's

@@ -29,10 +29,9 @@ def _conv_upsample_gelu(seq: nn.Sequential, x):
     if (not isinstance(act, nn.GELU) or act.approximate != "none" or up.mode != "bilinear"
             or not up.align_corners or float(up.scale_factor) != int(up.scale_factor)):
         return seq(x)
-    if kernels.conv3x3_wino_ok(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, vs_miopen=True):
-        y = kernels.conv3x3_wino(x, conv.weight, None)  # (MIOpen 53 us at 256 -> 128 / 64^2; bf16x3 ~24 us)
-    else:
-        y = kernels.conv2d_fallback(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+    # bias-free on the head site's kernels (MIOpen 53 us at 256 -> 128 / 64^2, bf16x3 ~24 us); autocast: the library
+    call = kernels.conv_module_call(conv, (x,))
+    y = kernels.conv_run(kernels.conv_route(call, kernels.SITE_HEAD, skip=("bf16",)), call, conv.weight, (x,))
     return kernels.upsample_bilinear_act(y, int(up.scale_factor), conv.bias, "gelu")
 
 

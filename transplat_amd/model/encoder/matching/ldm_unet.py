@@ -5,9 +5,9 @@ Only the configuration the depth predictor instantiates is built: postnorm ResBl
 down/up-sampling, legacy QKV attention at the requested resolutions with views folded into the
 token axis, middle block = ResBlock, Identity, ResBlock. Module indices and parameter names
 follow the reference (`input_blocks.{i}.{j}`, `middle_block.{0,2}`, `output_blocks.{i}.{j}`,
-`out.{0,1}`) so checkpoint keys load. The latency-bound low-resolution convolutions run as a direct
-fp32 MFMA kernel reading the skip concat / nearest upsample in place (kernels.conv2d_direct), the
-rest and the GEMMs on MIOpen / hipBLASLt; every
+`out.{0,1}`) so checkpoint keys load. Every convolution takes the route kernels.SITE_UNET gives it (the
+HIP kernels read the skip concat / nearest upsample in place; the full-resolution fp32 1x1s are library
+GEMMs; under bf16 autocast the shapes the bf16 kernel does not take stay on the library); every
 GroupNorm runs as one fused gfx950 kernel pair together with the activation and residual add
 that follow it in the reference's module chain (kernels.group_norm).
 """
@@ -16,7 +16,6 @@ from __future__ import annotations
 import math
 
 import torch
-import torch.nn.functional as F
 from einops import rearrange
 from torch import nn
 
@@ -32,76 +31,19 @@ def gn_act(norm: nn.GroupNorm, x, act: str = "none", residual=None, pre_bias=Non
     return y.type(x.dtype)
 
 
-def _direct(conv: nn.Module, x, x2=None, upsample: bool = False) -> bool:
-    """Whether conv(cat([x, x2])) runs as the direct kernel (kernels.conv2d_direct_ok)."""
-    if not (isinstance(conv, nn.Conv2d) and conv.dilation == (1, 1) and conv.groups == 1
-            and conv.stride[0] == conv.stride[1]):
-        return False
-    c2 = x2.shape[1] if x2 is not None else 0
-    return kernels.conv2d_direct_ok(x, conv.weight, conv.stride[0], conv.padding, c2=c2, upsample=upsample)
+def conv(conv: nn.Module, x, x2=None, upsample: bool = False, bias: bool = True, decided=None):
+    """conv(cat([x, x2], 1) (nearest-upsampled 2x if upsample)) [+ bias] on the route of kernels.SITE_UNET
+    (decided: the caller's (call, route)); the concat / upsample are read in place where the kernel can."""
+    srcs = (x,) if x2 is None else (x, x2)
+    call, route = decided or (kernels.conv_module_call(conv, srcs, upsample), None)
+    route = route or kernels.conv_route(call, kernels.SITE_UNET)
+    return kernels.conv_run(route, call, conv.weight, srcs, conv.bias if bias else None)
 
 
-def conv(conv: nn.Module, x, x2=None, upsample: bool = False, bias: bool = True):
-    """conv(cat([x, x2], 1) (nearest-upsampled 2x if upsample)) [+ bias]. The latency-bound 2-D
-    convolutions of the low-resolution levels run as one direct fp32 MFMA kernel that reads the
-    concat / upsample in place (kernels.conv2d_direct); the rest materialise them and run MIOpen."""
-    b = conv.bias if bias else None
-    extra = (x2,) if x2 is not None else ()
-    if (isinstance(conv, nn.Conv2d) and conv.padding_mode == "zeros"
-            and kernels.conv_bf16_ok(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, extra,
-                                     upsample)):
-        # bf16 autocast (C3): 3x3 / 1x1 on bf16 MFMA, the concat / upsample read in place
-        return kernels.conv_bf16(x, conv.weight, b, extra=extra, upsample=upsample)
-    if (isinstance(conv, nn.Conv1d) and x2 is None and not upsample and conv.kernel_size == (1,)
-            and conv.stride == (1,) and conv.groups == 1 and x.dim() == 3
-            and kernels.conv_bf16_ok(x.unsqueeze(2), conv.weight)):
-        # the attention blocks' qkv / proj_out under bf16 autocast: a 1x1 over [n, c, t] viewed as a
-        # [n, c, 1, t] map (MIOpen ran the 1-D form as im2col + GEMM)
-        return kernels.conv_bf16(x.unsqueeze(2), conv.weight, b).squeeze(2)
-    if _direct(conv, x, x2, upsample):
-        return kernels.conv2d_direct(x, conv.weight, b, conv.stride[0], x2=x2, upsample=upsample)
-    if (isinstance(conv, nn.Conv1d) and x2 is None and not upsample and conv.kernel_size == (1,)
-            and conv.stride == (1,) and conv.groups == 1 and x.dim() == 3
-            and kernels.conv2d_direct_ok(x.unsqueeze(-1), conv.weight)):
-        # the attention blocks' qkv / proj_out: a 1x1 over [n, c, t] viewed as [n, c, t, 1]
-        return kernels.conv2d_direct(x.unsqueeze(-1), conv.weight, b).squeeze(-1)
-    if (isinstance(conv, nn.Conv2d) and not upsample
-            and kernels.conv3x3_wino_ok(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, extra)):
-        return kernels.conv3x3_wino(x, conv.weight, b, extra=extra)  # the skip concat read in place
-    if x2 is not None:
-        x = torch.cat([x, x2], dim=1)
-    if upsample:
-        x = F.interpolate(x, scale_factor=2, mode="nearest")
-    if isinstance(conv, nn.Conv2d) and kernels.conv3x3_wino_ok(x, conv.weight, conv.stride, conv.padding,
-                                                               conv.dilation, conv.groups):
-        return kernels.conv3x3_wino(x, conv.weight, b)
-    if (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
-            and conv.groups == 1
-            and conv.padding == (0, 0) and x.is_cuda and x.dtype == torch.float32 and conv.weight.dtype == torch.float32
-            and not torch.is_autocast_enabled("cuda")):
-        # a full-resolution 1x1 (the 256^2 skip convolutions) as one batched GEMM per image,
-        # [cout, cin] x [cin, h*w]: HBM-bound ~10 us where MIOpen's NCHW 1x1 kernel took 45 us
-        n, ci, h, w = x.shape
-        co = conv.weight.shape[0]
-        wm = conv.weight.view(co, ci).expand(n, co, ci)
-        xm = x.contiguous().view(n, ci, h * w)
-        y = torch.baddbmm(b.view(1, co, 1), wm, xm) if b is not None else torch.bmm(wm, xm)
-        return y.view(n, co, h, w)
-    if isinstance(conv, nn.Conv2d):
-        return kernels.conv2d_fallback(x, conv.weight, b, conv.stride, conv.padding, conv.dilation, conv.groups)
-    return F.conv1d(x, conv.weight, b, conv.stride, conv.padding, conv.dilation, conv.groups)
-
-
-def conv_nobias(conv_mod: nn.Module, x, x2=None):
-    """The convolution without its bias (the following fused GroupNorm adds it)."""
-    return conv(conv_mod, x, x2, bias=False)
-
-
-def conv_gn_act(conv_mod: nn.Module, norm: nn.GroupNorm, x, act: str = "none", residual=None, x2=None):
+def conv_gn_act(conv_mod: nn.Module, norm: nn.GroupNorm, x, act: str = "none", residual=None, x2=None, decided=None):
     """conv -> GroupNorm -> act (-> + residual) with the conv bias folded into the norm kernel."""
-    if conv_mod.bias is None:
-        return gn_act(norm, conv(conv_mod, x, x2), act, residual)
-    return gn_act(norm, conv_nobias(conv_mod, x, x2), act, residual, pre_bias=conv_mod.bias)
+    y = conv(conv_mod, x, x2, bias=False, decided=decided)
+    return gn_act(norm, y, act, residual, pre_bias=conv_mod.bias)
 
 
 def run_sequential(seq: nn.Sequential, x):
@@ -158,35 +100,30 @@ class ResBlock(nn.Module):
         self.skip_connection = (nn.Identity() if self.out_channels == channels
                                 else nn.Conv2d(channels, self.out_channels, 1))
 
-    def _concat_free(self, x, x2) -> bool:
-        """bf16x3 mode, a Winograd / few-channel in_layers conv (the output blocks' skip concatenation,
-        round 6): both convolutions read cat([x, x2]) in place (the 3x3 as a two-source launch, a 1x1
-        skip on the two-source direct kernel)."""
-        c, sk = self.in_layers[0], self.skip_connection
-        if not (kernels.split_mode() and isinstance(c, nn.Conv2d)
-                and kernels.conv3x3_wino_ok(x, c.weight, c.stride, c.padding, c.dilation, c.groups, (x2,))):
-            return False
-        return isinstance(sk, nn.Identity) or (
-            isinstance(sk, nn.Conv2d) and sk.kernel_size == (1, 1) and sk.stride == (1, 1) and sk.groups == 1
-            and kernels.conv2d_direct_ok(x, sk.weight, 1, sk.padding, c2=x2.shape[1], force=True))
-
     def forward(self, x, x2=None):
         # skip + SiLU(GN(conv(SiLU(GN(conv(x)))))): both GN + SiLU pairs and the residual fused;
         # x2: the output blocks' skip input, x = cat([x, x2], 1) without materialising the concat
-        # where the convolutions read it in place
-        cat_free = False
-        if x2 is not None and not _direct(self.in_layers[0], x, x2):
-            cat_free = self._concat_free(x, x2)
-            if not cat_free:
-                x, x2 = torch.cat([x, x2], dim=1), None  # materialised once for both convolutions
-        h = conv_gn_act(self.in_layers[0], self.in_layers[1], x, "silu", x2=x2)
-        if isinstance(self.skip_connection, nn.Identity):
+        # where the convolutions read it in place. Each convolution's route is decided once, here.
+        c, sk = self.in_layers[0], self.skip_connection
+        srcs = (x,) if x2 is None else (x, x2)
+        call = kernels.conv_module_call(c, srcs)
+        route = kernels.conv_route(call, kernels.SITE_UNET)
+        sk_call = None if isinstance(sk, nn.Identity) else kernels.conv_module_call(sk, srcs)
+        sk_route = sk_call and kernels.conv_route(sk_call, kernels.SITE_UNET)
+        if x2 is not None and route != "direct":
+            # bf16x3 mode, a Winograd / few-channel in_layers conv (the output blocks' skip concatenation,
+            # round 6): both convolutions read cat([x, x2]) in place (the 3x3 as a two-source launch, a 1x1
+            # skip on the two-source direct kernel whether or not it wins there)
+            if kernels.split_mode() and route == "wino" and (sk_call is None or kernels.conv_can_direct(sk_call)):
+                sk_route = "direct"
+            else:
+                # materialised once for both convolutions; the routes decided on the two sources run on it
+                x, x2, call, sk_call = torch.cat(srcs, dim=1), None, call.joined(), sk_call and sk_call.joined()
+        h = conv_gn_act(c, self.in_layers[1], x, "silu", x2=x2, decided=(call, route))
+        if sk_call is None:
             skip = x if x2 is None else (x, x2)  # the concat read in place by the norm's residual add
-        elif cat_free and not _direct(self.skip_connection, x, x2):
-            sk = self.skip_connection
-            skip = kernels.conv2d_direct(x, sk.weight, sk.bias, 1, x2=x2)
         else:
-            skip = conv(self.skip_connection, x, x2)
+            skip = conv(sk, x, x2, decided=(sk_call, sk_route))
         return conv_gn_act(self.out_layers[0], self.out_layers[1], h, "silu", residual=skip)
 
 

@@ -109,8 +109,7 @@ class cam_param_encoder(nn.Module):  # noqa: N801  (reference class name kept fo
         vb = feat.shape[0]
         conv = self.reduce_conv[0]
         if (self._kernel_ok(feat) and conv.bias is not None
-                and kernels.conv3x3_wino_ok(feat, conv.weight, conv.stride, conv.padding, conv.dilation,
-                                            conv.groups, vs_miopen=True)):
+                and kernels.conv_route(kernels.conv_module_call(conv, (feat,)), kernels.SITE_FORWARD) == "wino"):
             # inference: both BatchNorms folded, conv + bias + ReLU as one Winograd launch
             w, b, w1, b1 = self._folded()
             feat = kernels.conv3x3_wino(feat, w, b, act="relu")
