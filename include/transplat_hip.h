@@ -778,6 +778,59 @@ int tsplat_lpips_tap_fwd(const float* feat, const float* lin, void* partials, fl
 int tsplat_lpips_reduce_fwd(const void* workspace, const int32_t* blocks, const int64_t* pixels, int32_t ntaps,
                             float* out, float* out_layers, int32_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fly-through video (reference ModelWrapper.render_video_generic, src/model/model_wrapper.py:713-790):
+ * trajectory cameras, the depth colour map's quantiles, and the frames, all on the device.
+ * ---------------------------------------------------------------------------------------- */
+
+/* interpolate_extrinsics (reference src/visualization/camera_trajectory/interpolation.py:204-252, with
+ * intersect_rays, generate_rotation_coordinate_frame, extrinsics_to_pivot_parameters,
+ * interpolate_circular and pivot_parameters_to_extrinsics of the same file): initial, final
+ * [num_pairs, 4, 4] fp32 camera-to-world, t [num_steps] fp32 (values outside [0, 1] extrapolate) -> out
+ * [num_pairs, num_steps, 4, 4] fp32. One thread per (pair, step); every intermediate is float64 and only
+ * the 16 outputs are rounded (the reference rounds parameters, frame and pivot to fp32 before converting
+ * back). Pivot: the origins' midpoint when | |look_a . look_b| - 1 | < eps, else the least-squares
+ * intersection of the look rays by the 3x3 normal equations (lstsq's minimum-norm solution coincides
+ * whenever this branch is taken). Angles: the first and third intrinsic YXZ Euler angle (scipy
+ * as_euler("YXZ")) of frame^-1 R; in gimbal lock (cos of the middle angle below 1e-7) the third is 0.
+ * TSPLAT_EINVAL, before any launch: a null pointer, num_pairs or num_steps <= 0, more than 2^24 poses. */
+int tsplat_trajectory_extrinsics(const float* initial, const float* final_, const float* t, double eps,
+                                 int32_t num_pairs, int32_t num_steps, float* out, void* stream);
+
+/* Exact quantiles by radix selection (replaces the two torch.quantile sorts and the boolean-mask
+ * indexing of the reference's depth_map, src/model/model_wrapper.py:737-738). x [n] fp32; q and
+ * positive_only [num_requests] are HOST arrays read during the call; out [num_requests] float64 on the
+ * device. Request r is numpy.quantile(pop, q[r]) with linear interpolation, evaluated in double: pop = x,
+ * or x[x > 0] when positive_only[r]; m = |pop| is counted on the device; pos = q (m - 1), k = floor(pos),
+ * out = lo + (hi - lo) (pos - k) with lo, hi the exact order statistics k and min(k + 1, m - 1). An empty
+ * population gives NaN. Four 8-bit digit passes over the order-preserving key (sign bit flipped for
+ * non-negative floats, all bits for negative ones: -0.0 sorts below +0.0, denormals are ordinary values);
+ * integer atomics only, so results repeat bit for bit. NaN inputs: unspecified (they sort by their bits).
+ * workspace: tsplat_quantile_workspace_bytes(num_requests) bytes, 256-byte aligned (0 for a rejected
+ * count); its contents need no initialisation. TSPLAT_EINVAL, before any launch: a null pointer, n <= 0 or
+ * n > 2^31 - 1, num_requests outside 1..4, a q outside [0, 1]. */
+size_t tsplat_quantile_workspace_bytes(int32_t num_requests);
+int tsplat_quantile_f32(const float* x, int64_t n, const double* q, const int32_t* positive_only,
+                        int32_t num_requests, double* out, void* workspace, void* stream);
+
+/* Video frames (reference depth_map + vcat + the uint8 conversion, src/model/model_wrapper.py:736-741,
+ * :749-752, :771, src/visualization/layout.py:171-189; with depth == NULL: prep_image,
+ * src/misc/image_io.py:38-54). color [frames, 3, height, width] fp32; depth [frames, height, width] fp32 or
+ * NULL; quantiles: device pointer to two float64 (q01 of the positive depths, q99 of all; what
+ * tsplat_quantile_f32 wrote), required with depth. out [frames, h_out, width, 3] uint8, h_out = 2 height + 8
+ * with depth, height without:
+ *   rows [0, height): uint8(clip(color, 0, 1) * 255), an fp32 multiply then truncation;
+ *   rows [height, height + 8): 255 (vcat's default gap, white);
+ *   rows below: near = log(q01), far = log(q99), r = 1 - (log(depth) - near) / (far - near), all float64;
+ *     entry min(int(clip(r, 0, 1) * 256), 255) of the 256-entry turbo table -> fp32 -> * 255 -> truncation.
+ *     depth = 0 (an uncovered pixel) gives r = +inf, the last entry; NaN r (far == near, or an empty
+ *     positive population, where the reference raises) gives (0, 0, 0).
+ * Each thread writes 4 consecutive pixels of a row as three dwords; widths that are no multiple of 4 (or
+ * buffers not 16-byte aligned) take a byte-store path. A NaN colour gives 0.
+ * TSPLAT_EINVAL, before any launch: color or out null, depth without quantiles, a size <= 0. */
+int tsplat_video_frames_fwd(const float* color, const float* depth, const double* quantiles, int32_t frames,
+                            int32_t height, int32_t width, uint8_t* out, void* stream);
+
 /* Diagnostics: write the 100-MHz device wall clock into ((uint64_t*)buf)[slot] when this launch
  * runs on `stream` (stage marks of a captured / replayed step, tools/graph_stages.py). */
 int tsplat_timestamp(void* buf, int32_t slot, void* stream);

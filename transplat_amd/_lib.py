@@ -87,6 +87,11 @@ SIGNATURES = {
     "tsplat_lpips_reduce_fwd": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _I32, _P]),
     "tsplat_raster_cameras": (ctypes.c_int, [_P] * 5 + [_I32] * 3 + [_P] * 7),
     "tsplat_small_inverse": (ctypes.c_int, [_P, _P, _I32, _I32, _P]),
+    "tsplat_trajectory_extrinsics": (ctypes.c_int, [_P, _P, _P, ctypes.c_double, _I32, _I32, _P, _P]),
+    "tsplat_quantile_workspace_bytes": (ctypes.c_size_t, [_I32]),
+    "tsplat_quantile_f32": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(_I32), _I32, _P, _P, _P]),
+    "tsplat_video_frames_fwd": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P]),
     "tsplat_pack_cameras_fwd": (ctypes.c_int, [_P, _P, _P, _I32, _P]),
     "tsplat_cam_gate_fwd": (ctypes.c_int, [_P] * 10 + [_I32] * 3 + [_P]),
     "tsplat_mha_f32_fwd": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, ctypes.c_float, _P]),

@@ -37,7 +37,12 @@ HIPCC_FLAGS = [
 FILE_FLAGS = {"raster.hip": ["-fno-slp-vectorize"],
               "upsample.hip": ["-ffp-contract=off"],  # torch's rounding of the interpolation weights
               "daglue.hip": ["-ffp-contract=off"],  # the same formula, and torch's separate sub / div / mul / add
-              "lpips.hip": ["-ffp-contract=off"]}  # the input scaling's separate mul / sub / sub / div
+              "lpips.hip": ["-ffp-contract=off"],  # the input scaling's separate mul / sub / sub / div
+              # the video path's float64 formulas as written: a fused q (m - 1) - k would change the
+              # quantile's interpolation weight, a fused r * 256 the colour-map entry
+              "quantile.hip": ["-ffp-contract=off"],
+              "frames.hip": ["-ffp-contract=off"],
+              "trajectory.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -2105,3 +2105,64 @@ def gaussian_adapter(raw, depths, densities, extrinsics, intrinsics, image_shape
         float(opacity_exponent), int(gaussians_per_pixel), int(nchw), _lib.stream_ptr(dev))
     _lib.check(rc, "tsplat_gaussian_adapter_fwd")
     return means, cov, harm, opac
+
+
+def trajectory_extrinsics(initial, final, t, eps: float = 1e-4):
+    """initial, final [P, 4, 4] camera-to-world, t [T] -> [P, T, 4, 4] fp32: the reference's
+    interpolate_extrinsics in one launch, float64 inside (tsplat_trajectory_extrinsics)."""
+    lib = _lib.load()
+    a, b, ts = _f32(initial), _f32(final), _f32(t)
+    if a.dim() != 3 or a.shape[1:] != (4, 4) or b.shape != a.shape or ts.dim() != 1:
+        raise ValueError(f"trajectory_extrinsics: poses {tuple(a.shape)} / {tuple(b.shape)}, t {tuple(ts.shape)}")
+    out = torch.empty((a.shape[0], ts.shape[0], 4, 4), dtype=torch.float32, device=a.device)
+    _lib.check(lib.tsplat_trajectory_extrinsics(_lib.ptr(a), _lib.ptr(b), _lib.ptr(ts), float(eps), a.shape[0],
+                                                ts.shape[0], _lib.ptr(out), _lib.stream_ptr(a.device)),
+               "tsplat_trajectory_extrinsics")
+    return out
+
+
+QUANTILE_MAX = 16_000_000  # values a quantile looks at (the reference's [:16_000_000])
+
+
+def quantile(x, requests):
+    """Exact quantiles of the fp32 values of x by radix selection (tsplat_quantile_f32): requests is up
+    to four (q, positive_only) pairs -> float64 [R] on x's device, each numpy.quantile(pop, q) with
+    linear interpolation over pop = x or x[x > 0] (NaN for an empty population). No sort, no host
+    sync; bit-identical from run to run."""
+    lib = _lib.load()
+    xf = _f32(x).reshape(-1)
+    r = len(requests)
+    q = (ctypes.c_double * max(r, 1))(*(float(a) for a, _ in requests))
+    pos = (ctypes.c_int32 * max(r, 1))(*(int(bool(p)) for _, p in requests))
+    nbytes = int(lib.tsplat_quantile_workspace_bytes(r))
+    if nbytes == 0:
+        raise ValueError(f"quantile: {r} requests (1..4)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=xf.device)
+    out = torch.empty((r,), dtype=torch.float64, device=xf.device)
+    _lib.check(lib.tsplat_quantile_f32(_lib.ptr(xf), xf.numel(), q, pos, r, _lib.ptr(out), _lib.ptr(ws),
+                                       _lib.stream_ptr(xf.device)), "tsplat_quantile_f32")
+    return out
+
+
+def video_frames(color, depth=None, quantiles=None):
+    """color [T, 3, H, W] (+ depth [T, H, W] and the device float64 pair (q01 of the positive depths,
+    q99) of quantile()) -> uint8 [T, 2H + 8, W, 3]: tone-mapped colour, 8 white rows, turbo-mapped
+    log depth, in one launch (tsplat_video_frames_fwd). Without depth: uint8 [T, H, W, 3], the
+    reference's prep_image on the device."""
+    lib = _lib.load()
+    c = _f32(color)
+    if c.dim() != 4 or c.shape[1] != 3:
+        raise ValueError(f"video_frames: expected [T, 3, H, W] colour, got {tuple(c.shape)}")
+    t, _, h, w = c.shape
+    d = qd = None
+    if depth is not None:
+        d = _f32(depth)
+        if d.shape != (t, h, w):
+            raise ValueError(f"video_frames: depth {tuple(d.shape)} for colour {tuple(c.shape)}")
+        if quantiles is None or quantiles.dtype != torch.float64 or quantiles.numel() != 2:
+            raise ValueError("video_frames: depth needs the two float64 quantiles")
+        qd = quantiles.contiguous()
+    out = torch.empty((t, 2 * h + 8 if d is not None else h, w, 3), dtype=torch.uint8, device=c.device)
+    _lib.check(lib.tsplat_video_frames_fwd(_lib.ptr(c), _lib.ptr(d), _lib.ptr(qd), t, h, w, _lib.ptr(out),
+                                           _lib.stream_ptr(c.device)), "tsplat_video_frames_fwd")
+    return out

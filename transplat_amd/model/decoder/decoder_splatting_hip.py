@@ -4,7 +4,8 @@
 Differences by design: the Gaussians are NOT repeated per target view (the reference
 materialises V copies, 46 MB each at G = 131072); all (b v) views go to one rasterizer call, and
 the depth render of `depth_mode` comes out of that same call (the reference runs the rasterizer a
-second time over fake colours).
+second time over fake colours). More than 32 views per scene (a video trajectory) are rendered in
+groups of `views_per_call` views per scene, one rasterizer call each on the one shared workspace.
 """
 from __future__ import annotations
 
@@ -18,7 +19,8 @@ from torch import Tensor
 
 from ..types import Gaussians
 from .decoder import Decoder, DecoderOutput, DepthRenderingMode
-from .hip_splatting import RasterOutput, check_status, prepare_cameras, rasterize, rasterize_with_depth
+from .hip_splatting import (RasterCameras, RasterOutput, check_status, merge_view_groups, plan_view_groups,
+                            prepare_cameras, rasterize, rasterize_with_depth, select_view_rows)
 
 
 @dataclass
@@ -27,6 +29,9 @@ class DecoderSplattingHIPCfg:
     sh_eval_degree: Optional[int] = None  # None: min(isqrt(d_sh) - 1, 3), the upstream behaviour
     check_overflow: bool = True  # sync after each call to surface capacity overflow
     debug: bool = False  # upstream GaussianRasterizationSettings.debug: sync + check after every launch
+    # views per scene of one rasterizer call when a scene has more than 32 (1..32): at the production
+    # scene 16 keeps the worst-case instance keys at 4 GiB, half the MAX_CAPACITY cap
+    views_per_call: int = 16
 
 
 def _depth_fused() -> bool:
@@ -87,7 +92,8 @@ class DecoderSplattingHIP(Decoder[DecoderSplattingHIPCfg]):
 
     def _render(self, gaussians, extrinsics, intrinsics, near, far, image_shape, depth_mode, color):
         """One rasterizer call over the un-repeated Gaussians for all (b v) views: colour and / or
-        the depth render of `depth_mode` from the same pass."""
+        the depth render of `depth_mode` from the same pass. More than 32 views per scene: one call
+        per group of plan_view_groups, the overflow status checked once after the last."""
         b, v, _, _ = extrinsics.shape
         nr = rearrange(near, "b v -> (b v)")
         fr = rearrange(far, "b v -> (b v)")
@@ -98,13 +104,28 @@ class DecoderSplattingHIP(Decoder[DecoderSplattingHIPCfg]):
             fr,
             repeat(self.background_color, "c -> (b v) c", b=b, v=v),
         )
-        args = (gaussians.means, gaussians.covariances, gaussians.harmonics, gaussians.opacities, cams, image_shape)
-        kw = dict(views_per_scene=v, sh_degree=self.cfg.sh_eval_degree, check=self.cfg.check_overflow,
-                  debug=self.cfg.debug)
-        if depth_mode is None:
-            rgb, radii = rasterize(*args, **kw)
-            return RasterOutput(rgb, radii, None, None)
-        return rasterize_with_depth(*args, near=nr, far=fr, depth_mode=depth_mode, color=color, **kw)
+        gauss = (gaussians.means, gaussians.covariances, gaussians.harmonics, gaussians.opacities)
+        groups = plan_view_groups(b, v, self.cfg.views_per_call)
+        single = len(groups) == 1
+        outs = []
+        for views in groups:
+            pick = lambda t: select_view_rows(t, b, v, views)
+            c = cams if single else RasterCameras(*(pick(getattr(cams, f)) for f in cams.__dataclass_fields__))
+            kw = dict(views_per_scene=views.stop - views.start, sh_degree=self.cfg.sh_eval_degree,
+                      check=self.cfg.check_overflow and single, debug=self.cfg.debug)
+            if depth_mode is None:
+                rgb, radii = rasterize(*gauss, c, image_shape, **kw)
+                outs.append(RasterOutput(rgb, radii, None, None))
+            else:
+                outs.append(rasterize_with_depth(*gauss, c, image_shape, near=pick(nr), far=pick(fr),
+                                                 depth_mode=depth_mode, color=color, **kw))
+        if single:
+            return outs[0]
+        if self.cfg.check_overflow:
+            check_status(gaussians.means.device)
+        merge = lambda name: (None if getattr(outs[0], name) is None
+                              else merge_view_groups([getattr(o, name) for o in outs], b))
+        return RasterOutput(merge("color"), merge("radii"), merge("depth"), merge("alpha"))
 
     def render_depth(
         self,

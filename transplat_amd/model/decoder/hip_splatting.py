@@ -291,6 +291,41 @@ def rasterize_with_depth(
                       capacity, check, debug, extra)
 
 
+MAX_VIEWS_PER_CALL = 32  # the rasterizer's per-scene view mask is 32 bits wide
+
+
+def plan_view_groups(b: int, v: int, views_per_call: int) -> list[slice]:
+    """The view slices of the rasterizer calls that render v views of each of b scenes: one call for
+    v <= 32 (the rasterizer's limit per scene), else groups of views_per_call (1..32) views in order,
+    the last one shorter. Each call renders its slice of every scene."""
+    if b < 1 or v < 1:
+        raise ValueError(f"plan_view_groups: {b} scenes x {v} views")
+    if v <= MAX_VIEWS_PER_CALL:
+        return [slice(0, v)]
+    if not 1 <= views_per_call <= MAX_VIEWS_PER_CALL:
+        raise ValueError(f"views_per_call {views_per_call}: expected 1..{MAX_VIEWS_PER_CALL}")
+    return [slice(s, min(s + views_per_call, v)) for s in range(0, v, views_per_call)]
+
+
+def select_view_rows(rows: Tensor, b: int, v: int, views: slice) -> Tensor:
+    """The rows of a group from (b v)-ordered per-view rows [b * v, ...]: views `views` of every scene,
+    (b g)-ordered. A view of the input for b = 1, one gather copy otherwise; no host sync."""
+    if views == slice(0, v):
+        return rows
+    return rows.reshape(b, v, *rows.shape[1:])[:, views].reshape(-1, *rows.shape[1:])
+
+
+def merge_view_groups(parts: list[Tensor], b: int) -> Tensor:
+    """Inverse of select_view_rows over a whole plan: per-group outputs [(b g), ...] in plan order ->
+    [(b v), ...]."""
+    if len(parts) == 1:
+        return parts[0]
+    if b == 1:
+        return torch.cat(parts, dim=0)
+    merged = torch.cat([p.reshape(b, -1, *p.shape[1:]) for p in parts], dim=1)
+    return merged.reshape(-1, *merged.shape[2:])
+
+
 def num_rendered(device) -> int:
     """(Gaussian, tile) instances generated by the last rasterize() on `device` (the reference
     forward's num_rendered; syncs)."""
