@@ -445,6 +445,47 @@ def test_conv3x3_wino_bf16x3_persistent_walk(device, monkeypatch, wgs, chans):
     assert err < 2e-5, err
 
 
+def _fused_every_form_case():
+    """Inputs and float64 reference of test_conv3x3_wino_bf16x3_fused_every_form (computed once)."""
+    if not _FUSED_CASE:
+        parts = [seeded((2, c, 20, 24), 150 + c + 7 * i) for i, c in enumerate((24, 16))]
+        wt = seeded((72, 40, 3, 3), 161) * (1.0 / (9 * 40) ** 0.5)
+        b = seeded((72,), 162)
+        r1, r2 = seeded((2, 72, 20, 24), 163), seeded((2, 72, 20, 24), 164)
+        ref = torch.nn.functional.conv2d(torch.relu(torch.cat(parts, 1)).double(), wt.double(), b.double(), padding=1)
+        ref = torch.nn.functional.gelu(ref) + r1.double() + r2.double()
+        _FUSED_CASE.update(parts=parts, wt=wt, b=b, r1=r1, r2=r2, ref=ref)
+    return _FUSED_CASE
+
+
+_FUSED_CASE = {}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("stage", ["auto", "0"])
+@pytest.mark.parametrize("form", ["auto", "1", "2", "3", "4", "5", "6"])
+def test_conv3x3_wino_bf16x3_fused_every_form(device, monkeypatch, form, stage):
+    """Every workgroup form, staged and not, with every epilogue feature at once: two sources of 24 + 16
+    channels (three chunks, the last half empty), ReLU on load, bias, GELU and both residuals, on
+    2 x 20 x 24 (width a multiple of 4: the staged path applies) with 72 outputs, so forced form 4 takes
+    the 64-wide launch plus the 32 x 32 tail launch from output block 2 with the residuals. Against the
+    float64 conv of the ReLU'd concatenation, within 2e-5 of max |y| (the bound of
+    test_conv3x3_wino_bf16x3_persistent_walk: the same ci and epilogue)."""
+    from transplat_amd import kernels as K
+
+    if form != "auto":
+        monkeypatch.setenv("TSPLAT_WINO3_FORM", form)
+    if stage != "auto":
+        monkeypatch.setenv("TSPLAT_WINO3_STAGE", stage)
+    c = _fused_every_form_case()
+    p0, p1 = (t.to(device) for t in c["parts"])
+    out = K.conv3x3_wino(p0, c["wt"].to(device), c["b"].to(device), "gelu", extra=(p1,), precision="bf16x3",
+                         residual=c["r1"].to(device), residual2=c["r2"].to(device), relu_in=True)
+    err = ((out.cpu().double() - c["ref"]).abs().max() / c["ref"].abs().max()).item()
+    print(f"wino bf16x3 fused form {form} stage {stage}: rel err {err:.2e}")
+    assert err < 2e-5, err
+
+
 @pytest.mark.gpu
 def test_conv3x3_wino_bf16x3_concat_and_production_size(device):
     """bf16x3 Winograd on the to_gaussians head's three sources at 256^2 (2 x 163 -> 168, the

@@ -283,3 +283,27 @@ def test_win_attn_layout_round_trip(tmp_path):
                     str(here / "winattn_layout_check.cc"), "-o", str(exe)], check=True)
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout
+
+
+def test_wino_layout_walk(tmp_path, winattn_lib):
+    """wino_layout.h as host C++ (tests/wino_layout_check.cc): fill_tiles agrees with the launchers' former
+    search on 1..40 x 1..140 and the production maps and its regions fit, the packed-U index of each
+    precision is injective and in range, the source filler rejects what the launchers rejected; the
+    library's buffer sizes are the header's."""
+    import shutil
+    import subprocess
+    from pathlib import Path
+    here = Path(__file__).resolve().parent
+    cxx = next((c for c in map(shutil.which, ("c++", "g++", "clang++")) if c), None)
+    if cxx is None:  # the HIP compiler the build needs anyway brings a host clang++
+        from transplat_amd import build
+        cxx = str(Path(build._hipcc()).resolve().parent.parent / "lib" / "llvm" / "bin" / "clang++")
+    exe = tmp_path / "wino_layout_check"
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", f"-I{here.parent / 'transplat_amd' / 'csrc'}",
+                    str(here / "wino_layout_check.cc"), "-o", str(exe)], check=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout
+    for co, ci in ((2, 64), (32, 38), (84, 168), (168, 163), (256, 128)):
+        cobs, ci_pad = (co + 63) // 64 * 2, (ci + 15) // 16 * 16
+        assert winattn_lib.tsplat_wino_weight_floats(co, ci) == 16 * cobs * 32 * ci_pad
+        assert winattn_lib.tsplat_wino_weight_bf16x3_bytes(co, ci) == 16 * cobs * 32 * ci_pad * 4

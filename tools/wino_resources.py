@@ -1,0 +1,36 @@
+"""Resource table of the Winograd / few-channel 3x3 kernels: compiles winoconv.hip, winoconv3.hip and
+convfew.hip for the device only with the build's flags plus -Rpass-analysis=kernel-resource-usage and
+prints one row per kernel (VGPRs, AGPRs, spills, scratch, occupancy, LDS). No GPU needed.
+
+usage: python tools/wino_resources.py [csrc dir] > profiles/wino_shared/resources_after.txt"""
+import re
+import subprocess
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from transplat_amd import build  # noqa: E402
+
+FIELDS = ["VGPRs", "AGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]",
+          "LDS Size [bytes/block]"]
+csrc = Path(sys.argv[1]) if len(sys.argv) > 1 else build.CSRC
+print("| Kernel | VGPRs | AGPRs | VGPR spill | SGPR spill | Scratch | Occupancy | LDS (bytes) |")
+print("|---|---|---|---|---|---|---|---|")
+for name in ("winoconv3.hip", "winoconv.hip", "convfew.hip"):
+    cmd = [build._hipcc(), *build.HIPCC_FLAGS, f"-I{build.CSRC}", *build.FILE_FLAGS.get(name, []), "--cuda-device-only",
+           "-Rpass-analysis=kernel-resource-usage", "-c", str(csrc / name), "-o", "/dev/null"]
+    err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+    rows, cur = [], None
+    for line in err.splitlines():
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            cur = {"name": m.group(1)}
+            rows.append(cur)
+        m = re.search(r"remark:\s+([A-Za-z \[\]/]+): (\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = m.group(2)
+    names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True,
+                           text=True).stdout.split("\n")
+    for r, full in zip(rows, names):
+        short = re.sub(r"^void |tsplat::|\(.*\)$", "", full)
+        print(f"| `{short}` | " + " | ".join(r.get(f, "?") for f in FIELDS) + " |")

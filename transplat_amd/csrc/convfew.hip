@@ -24,27 +24,25 @@
 #include "common.h"
 #include "mfma.h"
 #include "prof.h"
+#include "wino_layout.h"
 
 namespace tsplat {
 namespace convfew {
 
-constexpr int kMaxSrc = 6;
+using wino_layout::kMaxSrc;
 constexpr int kCols = 64;            // output columns per workgroup
 constexpr int kRC = kCols + 8;       // region columns: x0 - 4 .. x0 + 67 (16-B aligned float4 rows)
 constexpr int kCP = 32;              // input channels per pass
 constexpr int kPS = kCP + 8;         // bf16 per region pixel (padded: conflict-free b128 reads)
 constexpr int kMaxCi = 128;
 
-struct Args {
-    const float* src[kMaxSrc];
-    int cs[kMaxSrc];
-    int nsrc;
+struct Args : wino_layout::Sources {
     const uint4* wp;     // packed weight [cot][9][ng][hl][64 lanes] uint4 (8 bf16)
     const float* bias;   // [co] or null
     const float* res;    // [n][co][h][w] or null
     const float* res2;   // [n][co][h][w] or null
     float* y;            // [n][co][h][w]
-    int n, ci, h, w, co, ng, cot;  // ng = ceil(ci / 16) chunks, cot = ceil(co / 32)
+    int n, h, w, co, ng, cot;  // ng = ceil(ci / 16) chunks, cot = ceil(co / 32)
     int act;             // 0 none, 1 ReLU, 2 GELU (erf)
     int relu_in;
     int rb, cb;          // row / column blocks per image
@@ -242,8 +240,6 @@ __global__ void __launch_bounds__(256, 2) conv_kernel(Args a) {
 using namespace tsplat;
 
 // Which (rows per block, output blocks per workgroup) form a launch of this shape takes, 0 = the
-// shape is not one for this kernel. Rows: 8 where that still gives >= 256 workgroups, else 4, else 2.
-// Which (rows per block, output blocks per workgroup) form a launch of this shape takes, 0 = the
 // shape is not one for this kernel: 4-row blocks where that still gives >= 256 workgroups (two per
 // CU), else 2-row ones; 64 output channels only in 2-row blocks (the LDS image of 4 rows is 69 KB).
 extern "C" int32_t tsplat_conv3x3_few_form(int32_t n, int32_t ci, int32_t h, int32_t w, int32_t co) {
@@ -258,29 +254,21 @@ extern "C" int tsplat_conv3x3_few_bf16x3_fwd(const float* const* srcs, const int
                                              const float* residual2, float* y, int32_t n, int32_t h, int32_t w,
                                              int32_t co, int32_t act, int32_t relu_in, void* stream_) {
     using namespace tsplat::convfew;
-    if (!srcs || !chans || nsrc <= 0 || nsrc > kMaxSrc || !packed || !y || act < 0 || act > 2) return TSPLAT_EINVAL;
-    // the kernel moves y and the residuals as float4, like the sources below
+    Args a;
+    // the kernel moves the sources, y and the residuals as float4
+    if (!wino_layout::fill_sources(a, srcs, chans, nsrc, true) || !packed || !y || act < 0 || act > 2)
+        return TSPLAT_EINVAL;
     for (const float* p : {(const float*)y, residual, residual2})
         if (reinterpret_cast<uintptr_t>(p) & 15) return TSPLAT_EINVAL;
-    Args a;
-    int ci = 0;
-    for (int q = 0; q < kMaxSrc; ++q) {
-        a.src[q] = q < nsrc ? srcs[q] : nullptr;
-        a.cs[q] = q < nsrc ? chans[q] : 0;
-        if (q < nsrc && (!srcs[q] || chans[q] <= 0 || (reinterpret_cast<uintptr_t>(srcs[q]) & 15)))
-            return TSPLAT_EINVAL;
-        ci += a.cs[q];
-    }
+    const int ci = a.ci;
     const int form = tsplat_conv3x3_few_form(n, ci, h, w, co);
     if (!form) return TSPLAT_EINVAL;
-    a.nsrc = nsrc;
     a.wp = (const uint4*)packed;
     a.bias = bias;
     a.res = residual;
     a.res2 = residual2;
     a.y = y;
     a.n = n;
-    a.ci = ci;
     a.h = h;
     a.w = w;
     a.co = co;

@@ -26,9 +26,14 @@
 #include "common.h"
 #include "mfma.h"
 #include "prof.h"
+#include "wino_layout.h"
+#include "wino_steps.h"
 
 namespace tsplat {
 namespace wino {
+
+using namespace wino_layout;  // constants, Sources, Tiles, the packed-U index
+using wino_steps::xcd_tile_order;
 
 constexpr int kThreads = 256;
 constexpr int kCoB = 32;     // output channels per workgroup
@@ -36,18 +41,11 @@ constexpr int kTiles = 32;   // output tiles per workgroup
 constexpr int kCiB = 8;      // channels per chunk of conv_kernel (16 for conv64_kernel)
 constexpr int kGroup = 16;   // packed-filter channel group: [xi][co block][group][lane][8 slots]
 
-constexpr int kMaxSrc = 6;     // input sources concatenated along channels (read in place)
-constexpr int kMaxCiPad = 1024;  // input channels (padded to 16) of one launch
-
-struct Args {
-    const float* src[kMaxSrc];  // source s: [n][cs[s]][h][w]; channel c of the conv input is
-    int cs[kMaxSrc];            // channel c - (cs[0] + .. + cs[s-1]) of the source it falls in
-    int nsrc;
-    const float* u;      // packed U: [16][cobs][ci_pad / 16][64 lanes][8 slots]
+struct Args : Sources, Tiles {
+    const float* u;      // packed U (wino_layout.h u_index): [16][cobs][ci_pad / 16][64 lanes][8 slots]
     const float* bias;   // [co] or null
     float* y;            // [n][co][h][w]
-    int n, ci, h, w, co, ci_pad, cobs;  // cobs = 32-channel blocks in the packing (even)
-    int th, tw, tbx, tby, bx, by;  // tiles per image, tile-block shape, tile blocks per image row / column
+    int n, h, w, co, ci_pad, cobs;  // cobs = 32-channel blocks in the packing (even)
     int act;             // 0 none, 1 ReLU, 2 GELU (erf)
     int cob_base;        // first 32-channel output block of this launch (a split launch's offset)
 };
@@ -64,32 +62,10 @@ __global__ void __launch_bounds__(256) weight_kernel(const float* __restrict__ g
     const int idx = blockIdx.x * 256 + threadIdx.x;  // over cobs * 32 * ci_pad
     if (idx >= cobs * 32 * ci_pad) return;
     const int c = idx % ci_pad, o = idx / ci_pad;
-    float k[3][3];
-    const bool ok = o < co && c < ci;
+    float uu[16];
+    wino_steps::filter_transform(g, o, c, ci, o < co && c < ci, uu);
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) k[i][j] = ok ? g[((size_t)o * ci + c) * 9 + 3 * i + j] : 0.0f;
-    float t[4][3];  // G g
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        t[0][j] = k[0][j];
-        t[1][j] = 0.5f * (k[0][j] + k[1][j] + k[2][j]);
-        t[2][j] = 0.5f * (k[0][j] - k[1][j] + k[2][j]);
-        t[3][j] = k[2][j];
-    }
-    const int b = o / 32, ol = o % 32;
-    const int gr = c / kGroup, rem = c % kGroup;
-    const int q = rem >> 3, h = (rem >> 2) & 1, kk = rem & 3;
-    const size_t plane = (size_t)cobs * ci_pad * 32;  // floats per xi
-    const size_t off = (((size_t)b * (ci_pad / kGroup) + gr) * 64 + 32 * h + ol) * 8 + 4 * q + kk;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float uu[4] = {t[r][0], 0.5f * (t[r][0] + t[r][1] + t[r][2]), 0.5f * (t[r][0] - t[r][1] + t[r][2]),
-                             t[r][2]};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) u[(4 * r + s) * plane + off] = uu[s];
-    }
+    for (int xi = 0; xi < 16; ++xi) u[u_index(xi, o, c, cobs, ci_pad)] = uu[xi];
 }
 
 // One thread's (tile, channel) transform slot: the 4x4 input patch of output tile tt of the
@@ -220,19 +196,6 @@ __device__ __forceinline__ void store_tile(const Args& a, const float* zs, int c
 // iterations and meet at every barrier), each with its own double-buffered sV; their Z slabs are
 // summed in the epilogue. For the few-workgroup grids of the 32^2-64^2 maps (one 4-wave workgroup
 // per CU otherwise: one wave per SIMD through 16-32 serial chunks).
-// XCD-aware (tile block, output block) order: the dispatcher deals workgroup ids (x fastest)
-// round-robin over the 8 XCDs; remapped bijectively, each XCD runs a contiguous range of
-// (tile block, output block) pairs with the output blocks of one tile block adjacent, so the tile
-// block's input patches come from that XCD's L2 for all of them (x-fastest order re-reads the whole
-// input once per output block; winoconv3.hip measured 673 -> 211 MB fetched for 163 -> 168 at 256^2)
-__device__ __forceinline__ void xcd_tile_order(int& tb, int& cb) {
-    const int nwg = gridDim.x * gridDim.y, id = blockIdx.x + blockIdx.y * gridDim.x;
-    const int q = nwg / 8, r = nwg % 8, xcd = id % 8;
-    const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + id / 8;
-    tb = logical / gridDim.y;
-    cb = logical - tb * gridDim.y;
-}
-
 template <int KS>
 __global__ void __launch_bounds__(kThreads * KS) conv_kernel(Args a) {
     __shared__ __attribute__((aligned(16))) float smem[KS * 2 * 16 * kCiB * kTiles];  // sV x2 per group, then Z
@@ -398,20 +361,15 @@ __global__ void __launch_bounds__(kThreads64) conv64_kernel(Args a) {
 
 using namespace tsplat;
 
-// input channels are padded to the 16-channel group, output channels to 64 (an even number of
-// 32-channel blocks, so both workgroup shapes read the same packing)
-static int wino_ci_pad(int ci) { return (ci + wino::kGroup - 1) / wino::kGroup * wino::kGroup; }
-static int wino_cobs(int co) { return (co + 63) / 64 * 2; }
-
 extern "C" size_t tsplat_wino_weight_floats(int32_t co, int32_t ci) {
     if (co <= 0 || ci <= 0) return 0;
-    return (size_t)16 * wino_cobs(co) * wino_ci_pad(ci) * 32;
+    return wino_layout::u_floats(co, ci);
 }
 
 extern "C" int tsplat_wino_weight_f32(const float* weight, float* packed, int32_t co, int32_t ci, void* stream_) {
     if (!weight || !packed || co <= 0 || ci <= 0) return TSPLAT_EINVAL;
-    const int ci_pad = wino_ci_pad(ci);
-    const int cob = wino_cobs(co);
+    const int ci_pad = wino_layout::ci_pad(ci);
+    const int cob = wino_layout::cobs(co);
     const int total = cob * 32 * ci_pad;
     hipLaunchKernelGGL(wino::weight_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream_, weight,
                        packed, co, ci, ci_pad, cob);
@@ -422,47 +380,22 @@ extern "C" int tsplat_wino_weight_f32(const float* weight, float* packed, int32_
 static int wino_launch(const float* const* srcs, const int32_t* chans, int32_t nsrc, const float* packed,
                        const float* bias, float* y, int32_t n, int32_t h, int32_t w, int32_t co, int32_t act,
                        void* stream_) {
-    if (!srcs || !chans || nsrc <= 0 || nsrc > wino::kMaxSrc || !packed || !y || n <= 0 || h <= 0 || w <= 0 ||
-        co <= 0 || act < 0 || act > 2)
-        return TSPLAT_EINVAL;
     wino::Args a;
-    int ci = 0;
-    for (int q = 0; q < wino::kMaxSrc; ++q) {
-        a.src[q] = q < nsrc ? srcs[q] : nullptr;
-        a.cs[q] = q < nsrc ? chans[q] : 0;
-        if (q < nsrc && (!srcs[q] || chans[q] <= 0)) return TSPLAT_EINVAL;
-        ci += a.cs[q];
-    }
-    a.nsrc = nsrc;
+    if (!wino_layout::fill_sources(a, srcs, chans, nsrc) || !packed || !y || n <= 0 || h <= 0 || w <= 0 || co <= 0 ||
+        act < 0 || act > 2)
+        return TSPLAT_EINVAL;
     a.u = packed;
     a.bias = bias;
     a.y = y;
     a.n = n;
-    a.ci = ci;
     a.h = h;
     a.w = w;
     a.co = co;
-    a.ci_pad = wino_ci_pad(ci);
-    if (a.ci_pad > wino::kMaxCiPad) return TSPLAT_EINVAL;
-    a.cobs = wino_cobs(co);
-    a.th = (h + 1) / 2;
-    a.tw = (w + 1) / 2;
+    a.ci_pad = wino_layout::ci_pad(a.ci);
+    if (a.ci_pad > wino_layout::kMaxCiPad) return TSPLAT_EINVAL;
+    a.cobs = wino_layout::cobs(co);
     // tile block of 32 tiles: the widest of 32 x 1, 16 x 2, 8 x 4 with the fewest padded tiles
-    a.tbx = 32;
-    {
-        long best = -1;
-        for (int tbx = 32; tbx >= 8; tbx /= 2) {
-            const int tby = wino::kTiles / tbx;
-            const long padded = (long)((a.tw + tbx - 1) / tbx) * tbx * ((a.th + tby - 1) / tby) * tby;
-            if (best < 0 || padded < best) {
-                best = padded;
-                a.tbx = tbx;
-            }
-        }
-    }
-    a.tby = wino::kTiles / a.tbx;
-    a.bx = (a.tw + a.tbx - 1) / a.tbx;
-    a.by = (a.th + a.tby - 1) / a.tby;
+    wino_layout::fill_tiles(a, h, w, wino::kTiles, 8);
     a.act = act;
     hipStream_t stream = (hipStream_t)stream_;
     const prof::ExtEvents ev = prof::ext_events(prof::kWinoConv);  // kernel timestamps when timed

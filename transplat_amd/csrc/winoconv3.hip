@@ -26,6 +26,8 @@
 #include "common.h"
 #include "mfma.h"
 #include "prof.h"
+#include "wino_layout.h"
+#include "wino_steps.h"
 
 #ifndef TSPLAT_W3_ABL
 #define TSPLAT_W3_ABL 0  // diagnostic ablation builds only (tools/build_ablation_w3.sh)
@@ -34,9 +36,7 @@
 namespace tsplat {
 namespace wino3 {
 
-constexpr int kMaxSrc = 6;
-constexpr int kMaxCiPad = 1024;
-constexpr int kPersistCiPad = 512;  // the persistent form's plane table (keeps it at 2 workgroups / CU)
+using namespace wino_layout;  // constants, Sources, Tiles, the packed-U index
 
 // 16 zero bytes every masked load reads instead (loads stay unconditional: a select of the address
 // instead of an exec-masked branch with zero-initialised destinations per load)
@@ -57,15 +57,11 @@ __device__ unsigned long long* g_w3_stamps = nullptr;
 #define W3_STAMP(slot) do {} while (0)
 #endif
 
-struct Args {
-    const float* src[kMaxSrc];
-    int cs[kMaxSrc];
-    int nsrc;
-    const uint4* u;      // packed U: [16 xi][cobs][nchunk][2 hl][64 lanes][8 bf16]
+struct Args : Sources, Tiles {
+    const uint4* u;      // packed U (wino_layout.h u3_index), 8 bf16 per uint4
     const float* bias;   // [co] or null
     float* y;            // [n][co][h][w]
-    int n, ci, h, w, co, ci_pad, cobs, nchunk;  // cobs: 32-channel blocks in the packing
-    int th, tw, tbx, tby, bx, by;
+    int n, h, w, co, ci_pad, cobs, nchunk;  // cobs: 32-channel blocks in the packing
     int act;             // 0 none, 1 ReLU, 2 GELU (erf)
     int relu_in;         // ReLU applied to the input as it is loaded (a pre-activation unit)
     const float* res;    // [n][co][h][w] added after the activation, or null
@@ -73,43 +69,21 @@ struct Args {
     int cob_base;        // first 32-channel output block of this launch
 };
 
-// U = G g G^T (as winoconv.hip's weight_kernel), split into hi / lo bf16 and packed as the A operand
-// of v_mfma_f32_32x32x16_bf16: lane l (co = 32 b + (l & 31), h = l >> 5), element j <- ci = 16 k + 8 h + j
+// U = G g G^T split into hi / lo bf16 and packed as the A operand of v_mfma_f32_32x32x16_bf16
+// (wino_layout.h u3_index)
 __global__ void __launch_bounds__(256) weight_kernel(const float* __restrict__ g, __bf16* __restrict__ u, int co,
                                                      int ci, int ci_pad, int cobs) {
     const int idx = blockIdx.x * 256 + threadIdx.x;  // over cobs * 32 * ci_pad
     if (idx >= cobs * 32 * ci_pad) return;
     const int c = idx % ci_pad, o = idx / ci_pad;
-    float k[3][3];
-    const bool ok = o < co && c < ci;
+    float uu[16];
+    wino_steps::filter_transform(g, o, c, ci, o < co && c < ci, uu);
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) k[i][j] = ok ? g[((size_t)o * ci + c) * 9 + 3 * i + j] : 0.0f;
-    float t[4][3];  // G g
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        t[0][j] = k[0][j];
-        t[1][j] = 0.5f * (k[0][j] + k[1][j] + k[2][j]);
-        t[2][j] = 0.5f * (k[0][j] - k[1][j] + k[2][j]);
-        t[3][j] = k[2][j];
-    }
-    const int b = o / 32, ol = o % 32;
-    const int chunk = c / 16, h = (c >> 3) & 1, j = c & 7;
-    const int nchunk = ci_pad / 16;
-    const size_t lane = 32 * h + ol;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float uu[4] = {t[r][0], 0.5f * (t[r][0] + t[r][1] + t[r][2]), 0.5f * (t[r][0] - t[r][1] + t[r][2]),
-                             t[r][2]};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const size_t base = ((((size_t)(4 * r + s) * cobs + b) * nchunk + chunk) * 2) * 64;
-            const __bf16 hi = (__bf16)uu[s];
-            const __bf16 lo = (__bf16)(uu[s] - (float)hi);
-            u[((base + lane) * 8) + j] = hi;
-            u[((base + 64 + lane) * 8) + j] = lo;
-        }
+    for (int xi = 0; xi < 16; ++xi) {
+        const __bf16 hi = (__bf16)uu[xi];
+        const __bf16 lo = (__bf16)(uu[xi] - (float)hi);
+        u[u3_index(xi, o, c, 0, cobs, ci_pad / 16)] = hi;
+        u[u3_index(xi, o, c, 1, cobs, ci_pad / 16)] = lo;
     }
 }
 
@@ -223,20 +197,8 @@ __global__ void __launch_bounds__(256 * CB * KS, (NB == 1 && CB * KS <= 2) ? 2 :
     __shared__ const float* planes[kMaxCiPad];
 
     W3_STAMP(0);
-    // XCD-aware order: the dispatcher deals workgroup ids (x fastest) round-robin over the 8 XCDs.
-    // The bijective remap gives each XCD a contiguous range of (tile block, output block) pairs with
-    // the output blocks of one tile block adjacent, so a tile block's input regions are fetched into
-    // that XCD's L2 once for all its output blocks (x-fastest order re-read the whole input map from
-    // HBM / MALL once per output block: 673 MB fetched for the 85 MB input of 2 x 163 -> 168 at 256^2,
-    // profiles/r4/traffic_wino3_163x168_b1.json)
     int tbk, cbk;
-    {
-        const int nwg = gridDim.x * gridDim.y, id = blockIdx.x + blockIdx.y * gridDim.x;
-        const int q = nwg / 8, r = nwg % 8, xcd = id % 8;
-        const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + id / 8;
-        tbk = logical / gridDim.y;
-        cbk = logical - tbk * gridDim.y;
-    }
+    wino_steps::xcd_tile_order(tbk, cbk);
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int kg = wid / (4 * CB), wg = wid % (4 * CB);
     const int hh = wg >> 2, rr = wg & 3;
@@ -780,18 +742,15 @@ extern "C" int tsplat_wino3_stamps(void* buf) {
 }
 #endif
 
-static int wino3_ci_pad(int ci) { return (ci + 15) / 16 * 16; }
-static int wino3_cobs(int co) { return (co + 63) / 64 * 2; }
-
 extern "C" size_t tsplat_wino_weight_bf16x3_bytes(int32_t co, int32_t ci) {
     if (co <= 0 || ci <= 0) return 0;
-    return (size_t)16 * wino3_cobs(co) * wino3_ci_pad(ci) * 32 * 2 * 2;  // hi + lo bf16
+    return wino_layout::u3_bytes(co, ci);
 }
 
 extern "C" int tsplat_wino_weight_bf16x3(const float* weight, void* packed, int32_t co, int32_t ci, void* stream_) {
     if (!weight || !packed || co <= 0 || ci <= 0) return TSPLAT_EINVAL;
-    const int ci_pad = wino3_ci_pad(ci);
-    const int cobs = wino3_cobs(co);
+    const int ci_pad = wino_layout::ci_pad(ci);
+    const int cobs = wino_layout::cobs(co);
     const int total = cobs * 32 * ci_pad;
     hipLaunchKernelGGL(wino3::weight_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream_, weight,
                        (__bf16*)packed, co, ci, ci_pad, cobs);
@@ -853,62 +812,37 @@ extern "C" int tsplat_conv3x3_wino_bf16x3_ex_fwd(const float* const* srcs, const
                                                  const void* packed, const float* bias, const float* residual,
                                                  const float* residual2, float* y, int32_t n, int32_t h, int32_t w,
                                                  int32_t co, int32_t act, int32_t relu_in, void* stream_) {
-    if (!srcs || !chans || nsrc <= 0 || nsrc > wino3::kMaxSrc || !packed || !y || n <= 0 || h <= 0 || w <= 0 ||
-        co <= 0 || act < 0 || act > 2)
-        return TSPLAT_EINVAL;
     wino3::Args a;
-    int ci = 0;
-    for (int q = 0; q < wino3::kMaxSrc; ++q) {
-        a.src[q] = q < nsrc ? srcs[q] : nullptr;
-        a.cs[q] = q < nsrc ? chans[q] : 0;
-        if (q < nsrc && (!srcs[q] || chans[q] <= 0)) return TSPLAT_EINVAL;
-        ci += a.cs[q];
-    }
-    a.nsrc = nsrc;
+    if (!wino_layout::fill_sources(a, srcs, chans, nsrc) || !packed || !y || n <= 0 || h <= 0 || w <= 0 || co <= 0 ||
+        act < 0 || act > 2)
+        return TSPLAT_EINVAL;
     a.u = (const uint4*)packed;
     a.bias = bias;
     a.y = y;
     a.n = n;
-    a.ci = ci;
     a.h = h;
     a.w = w;
     a.co = co;
-    a.ci_pad = wino3_ci_pad(ci);
-    if (a.ci_pad > wino3::kMaxCiPad) return TSPLAT_EINVAL;
-    a.cobs = wino3_cobs(co);
+    a.ci_pad = wino_layout::ci_pad(a.ci);
+    if (a.ci_pad > wino_layout::kMaxCiPad) return TSPLAT_EINVAL;
+    a.cobs = wino_layout::cobs(co);
     a.nchunk = a.ci_pad / 16;
-    a.th = (h + 1) / 2;
-    a.tw = (w + 1) / 2;
     a.act = act;
     a.relu_in = relu_in != 0;
     a.res = residual;
     a.res2 = residual2;
     a.cob_base = 0;
-    int form = pick_form(n, a.th, a.tw, co);
-    // tile block: the widest of T x 1, T/2 x 2, T/4 x 4, T/8 x 8 with the fewest padded tiles; false
-    // where the staged region loads' R x C4 <= 72 (32-tile blocks) / 136 (64-tile blocks) fails
-    auto geometry = [&](int ttiles) {
-        long best = -1;
-        for (int tbx = ttiles; tbx >= ttiles / 8; tbx /= 2) {
-            const int tby = ttiles / tbx;
-            const long padded = (long)((a.tw + tbx - 1) / tbx) * tbx * ((a.th + tby - 1) / tby) * tby;
-            if (best < 0 || padded < best) {
-                best = padded;
-                a.tbx = tbx;
-            }
-        }
-        a.tby = ttiles / a.tbx;
-        a.bx = (a.tw + a.tbx - 1) / a.tbx;
-        a.by = (a.th + a.tby - 1) / a.tby;
-        return (2 * a.tby + 2) * (a.tbx / 2 + 2) <= (ttiles == 32 ? 72 : 136);
-    };
-    if (!geometry(form == 3 || form == 4 ? 64 : 32)) return TSPLAT_EINVAL;
+    int form = pick_form(n, (h + 1) / 2, (w + 1) / 2, co);
+    // tile block: the widest of T x 1, T/2 x 2, T/4 x 4, T/8 x 8 with the fewest padded tiles; each of
+    // them keeps the staged region within its R x C4 <= 72 (32-tile blocks) / 136 (64-tile blocks)
+    // float4 per channel (wino_layout.h region_fits, checked there at compile time)
+    const int ttiles = form == 3 || form == 4 ? 64 : 32;
+    wino_layout::fill_tiles(a, h, w, ttiles, ttiles / 8);
     const int blocks = n * a.bx * a.by;
     // staged input: float4 rows need a width that is a multiple of 4 and 16-B aligned sources
-    bool staged = w % 4 == 0;
-    for (int q = 0; q < nsrc; ++q) staged = staged && (reinterpret_cast<uintptr_t>(srcs[q]) & 15) == 0;
+    bool staged = w % 4 == 0 && wino_layout::aligned16(a);
     if (const char* e = getenv("TSPLAT_WINO3_STAGE")) staged = staged && atoi(e) != 0;
-    if (form == 5 && (!staged || a.ci_pad > wino3::kPersistCiPad)) form = 1;
+    if (form == 5 && (!staged || a.ci_pad > wino_layout::kPersistCiPad)) form = 1;
     hipStream_t stream = (hipStream_t)stream_;
     const prof::ExtEvents ev = prof::ext_events(prof::kWinoConv);
     if (form == 5) {
@@ -927,7 +861,7 @@ extern "C" int tsplat_conv3x3_wino_bf16x3_ex_fwd(const float* const* srcs, const
     // 32 x 32 blocks
     if (form == 4 && co > 64 && co % 64 != 0 && co % 64 <= 32) {
         launch<2, 2, 1>(a, blocks, staged, stream, ev.start, nullptr, co / 64);
-        if (!geometry(32)) return TSPLAT_EINVAL;
+        wino_layout::fill_tiles(a, h, w, 32, 4);
         a.cob_base = (co / 64) * 2;
         launch<1, 1, 1>(a, n * a.bx * a.by, staged, stream, nullptr, ev.stop, 1);
         TSPLAT_CHECK_LAUNCH();

@@ -1187,7 +1187,7 @@ def wino_pack_weight(weight):
     return _derived(weight, "wino", _pack_wino)
 
 
-WINO_MAX_CI_PAD = 1024  # winoconv.hip kMaxCiPad: input channels (padded to 16) of one launch
+WINO_MAX_CI_PAD = 1024  # csrc/wino_layout.h kMaxCiPad: input channels (padded to 16) of one launch
 
 
 # Convolutions the encoder used to leave on MIOpen (round 5): the UniMatch CNN's 7x7 stride-2 stem
