@@ -12,12 +12,11 @@ bar) of float64 on every case, at least 0.05 of every case's outputs are non-zer
 with one of three index mistakes built in lies more than 1e-2 (100 x the bar) from the true one.
 
 Which coarse kernel instantiation (tsplat_uv_coarse_fwd, S = ceil(D / 64)) a case reaches; every
-case runs the five variants run / run6 / bitmap / bitmap5 / direct:
+case runs the four variants run / run6 / bitmap / direct (the launcher's table in corr.hip):
   variant   env                                        D <= 64   65..128   129..192  193..256   > 256
   run       (none)                                     run<1,8>  run<2,8>  run<3,6>  run<4,6>   plain
   run6      TSPLAT_CORR_RUN_WPE=6                      run<1,6>  run<2,6>  run<3,6>  run<4,6>   plain
-  bitmap    TSPLAT_UV_COARSE_BITMAP=1                  dedup<1,6> <2,6>    <3,6>     <4,6>      plain
-  bitmap5   ... and TSPLAT_CORR_WPE=5                  dedup<1,5> <2,5>    <3,5>     <4,5>      plain
+  bitmap    TSPLAT_UV_COARSE_BITMAP=1                  dedup<1>  dedup<2>  dedup<3>  dedup<4>   plain
   direct    TSPLAT_UV_COARSE_DIRECT=1                  plain (uv_coarse_kernel) at every D
   S = 1: shapes 6x10 D=5, 9x11 D=33, 40x24 D=64, sweep D = 1, 15, 16, 17, 63, 64
   S = 2: shapes 12x40 D=100, 24x40 D=128, every 12x20 construction (D=100), sweep D = 65, 128
@@ -52,7 +51,6 @@ COARSE_VARIANTS = {
     "run": {},
     "run6": {"TSPLAT_CORR_RUN_WPE": "6"},
     "bitmap": {"TSPLAT_UV_COARSE_BITMAP": "1"},
-    "bitmap5": {"TSPLAT_UV_COARSE_BITMAP": "1", "TSPLAT_CORR_WPE": "5"},
     "direct": {"TSPLAT_UV_COARSE_DIRECT": "1"},
 }
 
@@ -357,9 +355,8 @@ def test_uv_coarse_shapes(device, monkeypatch, case):
     assert all(out.shape == ref.shape and out.dtype == torch.float32 for out in outs.values())
     assert max(errs.values()) < BAR, errs
     if depths <= 256:
-        for name in ("run6", "bitmap5"):
+        for name in ("run6", "run"):
             assert torch.equal(outs[name], outs["bitmap"]), name
-        assert torch.equal(outs["run"], outs["bitmap"])
 
 
 @pytest.mark.gpu
@@ -423,12 +420,24 @@ def _msda_locations(n, q, p, h, w):
     return flat.reshape(n, q, p, 2).contiguous()
 
 
+def _msda_entry(K, entry, value, loc, wts, h, w):
+    """msda through tsplat_msda_fwd, or the same call as one level and one head (head dim 128) of the
+    general tsplat_ms_deform_attn_fwd."""
+    if entry == "msda":
+        return K.msda(value, loc, wts, h, w)
+    return K.ms_deform_attn(value[:, :, None], torch.tensor([[h, w]]), torch.tensor([0]), loc[:, :, None, None],
+                            wts[:, :, None, None])
+
+
 @pytest.mark.gpu
+@pytest.mark.parametrize("entry", ["msda", "ms_deform_attn"])
 @pytest.mark.parametrize("points", [1, 4, 8])
 @pytest.mark.parametrize("hw", [(12, 20), (7, 5)])
-def test_msda_shapes(device, hw, points):
+def test_msda_shapes(device, hw, points, entry):
     """(f): msda on non-square maps with 1 / 4 / 8 points and 37 queries (no multiple of the 16 per
-    workgroup), against the float64 reference at the existing 1e-5. Measured on MI355X: <= 3.0e-6."""
+    workgroup), through its own entry point and through the general mmcv-shaped kernel (which otherwise
+    sees only random locations), against the float64 reference at the existing 1e-5. The locations
+    include exact pixel centres, exactly 0 and 1, and far outside. Measured on MI355X: <= 3.0e-6."""
     from transplat_amd import kernels as K
 
     h, w = hw
@@ -438,9 +447,9 @@ def test_msda_shapes(device, hw, points):
     wts = torch.softmax(seeded((n, q, points), 53), -1)
     ref = E.msda(value, loc, wts, h, w, dtype=F64)
     assert ref.dtype == F64 and (ref != 0).double().mean().item() >= MIN_SHARE
-    out = K.msda(value.to(device), loc.to(device), wts.to(device), h, w).cpu()
+    out = _msda_entry(K, entry, value.to(device), loc.to(device), wts.to(device), h, w).cpu()
     err = _maxdiff(out, ref)
-    print(f"msda {hw} P={points}: {err:.2e}")
+    print(f"msda {entry} {hw} P={points}: {err:.2e}")
     assert out.shape == ref.shape and err < 1e-5, err
 
 

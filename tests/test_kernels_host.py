@@ -285,6 +285,27 @@ def test_win_attn_layout_round_trip(tmp_path):
     assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout
 
 
+def test_corr_cell_matches_mmcv(tmp_path):
+    """corr_cell.h as host C++ (tests/corr_cell_check.cc): the bilinear cell every sampling kernel goes
+    through equals a literal transcription of mmcv's ms_deform_attn_im2col_bilinear -- taken or not, the
+    corner, the inside mask, the four weights bit for bit -- on maps 1x1 .. 9x9, 7x5, 12x20 and 64x64 at
+    integer positions, their float neighbours, half-integers, +-1e4, +-inf and NaN; a taken sample's
+    weights sum to 1 within 2 ulp."""
+    import shutil
+    import subprocess
+    from pathlib import Path
+    here = Path(__file__).resolve().parent
+    cxx = next((c for c in map(shutil.which, ("c++", "g++", "clang++")) if c), None)
+    if cxx is None:  # the HIP compiler the build needs anyway brings a host clang++
+        from transplat_amd import build
+        cxx = str(Path(build._hipcc()).resolve().parent.parent / "lib" / "llvm" / "bin" / "clang++")
+    exe = tmp_path / "corr_cell_check"
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", f"-I{here.parent / 'transplat_amd' / 'csrc'}",
+                    str(here / "corr_cell_check.cc"), "-o", str(exe)], check=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout
+
+
 def test_wino_layout_walk(tmp_path, winattn_lib):
     """wino_layout.h as host C++ (tests/wino_layout_check.cc): fill_tiles agrees with the launchers' former
     search on 1..40 x 1..140 and the production maps and its regions fit, the packed-U index of each

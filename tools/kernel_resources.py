@@ -1,8 +1,10 @@
-"""Resource table of the Winograd / few-channel 3x3 kernels: compiles winoconv.hip, winoconv3.hip and
-convfew.hip for the device only with the build's flags plus -Rpass-analysis=kernel-resource-usage and
-prints one row per kernel (VGPRs, AGPRs, spills, scratch, occupancy, LDS). No GPU needed.
+"""Resource table of the kernels of the given csrc/*.hip files: compiles each for the device only with
+the build's flags plus -Rpass-analysis=kernel-resource-usage and prints one row per kernel (VGPRs,
+AGPRs, spills, scratch, occupancy, LDS). No GPU needed.
 
-usage: python tools/wino_resources.py [csrc dir] > profiles/wino_shared/resources_after.txt"""
+usage: python tools/kernel_resources.py [--csrc DIR] corr.hip uvfused.hip > profiles/corr_shared/resources_after.txt
+       python tools/kernel_resources.py winoconv3.hip winoconv.hip convfew.hip
+--csrc DIR: read the sources from DIR (an archive of another commit) instead of the tree's csrc."""
 import re
 import subprocess
 import sys
@@ -13,13 +15,21 @@ from transplat_amd import build  # noqa: E402
 
 FIELDS = ["VGPRs", "AGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]",
           "LDS Size [bytes/block]"]
-csrc = Path(sys.argv[1]) if len(sys.argv) > 1 else build.CSRC
+args = sys.argv[1:]
+csrc = build.CSRC
+if args[:1] == ["--csrc"]:
+    csrc, args = Path(args[1]), args[2:]
+if not args:
+    sys.exit(__doc__)
 print("| Kernel | VGPRs | AGPRs | VGPR spill | SGPR spill | Scratch | Occupancy | LDS (bytes) |")
 print("|---|---|---|---|---|---|---|---|")
-for name in ("winoconv3.hip", "winoconv.hip", "convfew.hip"):
-    cmd = [build._hipcc(), *build.HIPCC_FLAGS, f"-I{build.CSRC}", *build.FILE_FLAGS.get(name, []), "--cuda-device-only",
+for name in args:
+    cmd = [build._hipcc(), *build.HIPCC_FLAGS, f"-I{csrc}", *build.FILE_FLAGS.get(name, []), "--cuda-device-only",
            "-Rpass-analysis=kernel-resource-usage", "-c", str(csrc / name), "-o", "/dev/null"]
-    err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+    done = subprocess.run(cmd, capture_output=True, text=True)
+    if done.returncode:
+        sys.exit("\n".join(line for line in done.stderr.splitlines() if "remark:" not in line))
+    err = done.stderr
     rows, cur = [], None
     for line in err.splitlines():
         m = re.search(r"remark: Function Name: (\S+)", line)

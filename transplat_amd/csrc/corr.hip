@@ -15,6 +15,10 @@
 //
 // Mapping: one workgroup per query pixel, 16 lanes per (query, depth) (8 channels per lane, so a
 // 16-lane group reads one 512-B feature row as 16 x 32 B), 16 depths in flight per workgroup.
+//
+// One definition each: where a sample lies is corr_geo.h's, what it reads there (the bilinear cell)
+// corr_cell.h's; the two dedup coarse kernels share their steps, the sample-then-dot kernels their
+// skeletons, below.
 #include "common.h"
 #include "corr_geo.h"
 #include "prof.h"
@@ -39,28 +43,26 @@ __device__ __forceinline__ void sample_im(const float* c, const Geo& g, const fl
     yim = ry * (float)g.H - 0.5f;
 }
 
-// bilinear sample (zero padding, mmcv ms_deform_attn_im2col_bilinear) of 8 channels [c0, c0+8)
-// of a channel-last [H*W, C] map; accumulates w * value into acc
+// bilinear sample (zero padding, the cell of corr_cell.h) of 8 channels [c0, c0+8) of a channel-last
+// [H*W, C] map; accumulates w * value into acc
 __device__ __forceinline__ void bilinear_acc8(const float* __restrict__ img, const Geo& g, float xim,
                                               float yim, float w, int c0, float acc[8]) {
-    if (!(yim > -1.0f && xim > -1.0f && yim < (float)g.H && xim < (float)g.W)) return;
-    const float fy = floorf(yim), fx = floorf(xim);
-    const int y0 = (int)fy, x0 = (int)fx, y1 = y0 + 1, x1 = x0 + 1;
-    const float ly = yim - fy, lx = xim - fx, hy = 1.0f - ly, hx = 1.0f - lx;
-    const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
+    Cell cl;
+    if (!cell_at(xim, yim, g.H, g.W, cl)) return;
+    float cw[4];
+    cell_weights(cl.ly, cl.lx, cw);
     float v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = 0.f;
-    auto corner = [&](int yy, int xx, float cw) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (!((cl.in >> k) & 1u)) continue;
+        const int yy = cl.y0 + (k >> 1), xx = cl.x0 + (k & 1);
         const float4* s = reinterpret_cast<const float4*>(img + ((size_t)yy * g.W + xx) * kC + c0);
         const float4 a = s[0], b = s[1];
-        v[0] += cw * a.x; v[1] += cw * a.y; v[2] += cw * a.z; v[3] += cw * a.w;
-        v[4] += cw * b.x; v[5] += cw * b.y; v[6] += cw * b.z; v[7] += cw * b.w;
-    };
-    if (y0 >= 0 && x0 >= 0) corner(y0, x0, w1);
-    if (y0 >= 0 && x1 <= g.W - 1) corner(y0, x1, w2);
-    if (y1 <= g.H - 1 && x0 >= 0) corner(y1, x0, w3);
-    if (y1 <= g.H - 1 && x1 <= g.W - 1) corner(y1, x1, w4);
+        v[0] += cw[k] * a.x; v[1] += cw[k] * a.y; v[2] += cw[k] * a.z; v[3] += cw[k] * a.w;
+        v[4] += cw[k] * b.x; v[5] += cw[k] * b.y; v[6] += cw[k] * b.z; v[7] += cw[k] * b.w;
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] += w * v[i];
 }
@@ -73,52 +75,61 @@ __device__ __forceinline__ float group_sum16(float x) {
     return x;
 }
 
-// ---- coarse: corr[n][p][d] = <sample(feat_other, loc(p, d)), feat_own[p]> / sqrt(C)
-__global__ void __launch_bounds__(kThreads)
-uv_coarse_kernel(Geo g, const float* __restrict__ feat, const float* __restrict__ cams,
-                 const float* __restrict__ disp, float* __restrict__ out) {
+// ---- the sample-then-dot skeleton of uv_coarse_kernel / uv_cross_kernel: one workgroup per query
+// pixel, 16 lanes per depth; sample(d, c0, acc) accumulates the lane's 8 channels of depth d's sampled
+// feature, out_row[d] = scale * <sampled, key_row>. The results leave through s_out, 256 depths at a
+// time, so the stores are coalesced.
+template <typename Sample>
+__device__ __forceinline__ void per_depth_dot(int depths, const float* __restrict__ key_row, float scale,
+                                              float* __restrict__ out_row, Sample&& sample) {
     __shared__ float s_out[256];
-    const int p = blockIdx.x, n = blockIdx.y;
     const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15, c0 = gl * 8;
-    const size_t HW = (size_t)g.H * g.W;
-    const float* own = feat + (size_t)n * HW * kC;
-    const float* other = feat + (size_t)(n ^ 1) * HW * kC;
-    const float* c = cam_ptr(cams, g, n);
-    const int b = n >> 1, v = n & 1;
-    const float* dsp = disp + (size_t)(v * g.B + b) * g.D;
     float key[8];
     {
-        const float4* s = reinterpret_cast<const float4*>(own + (size_t)p * kC + c0);
+        const float4* s = reinterpret_cast<const float4*>(key_row + c0);
         const float4 a = s[0], bb = s[1];
         key[0] = a.x; key[1] = a.y; key[2] = a.z; key[3] = a.w;
         key[4] = bb.x; key[5] = bb.y; key[6] = bb.z; key[7] = bb.w;
     }
-    float ray[3];
-    pixel_ray(c, (float)(p % g.W), (float)(p / g.W), ray);
-    const float inv_sqrt_c = 1.0f / sqrtf((float)kC);
-    for (int d0 = 0; d0 < g.D; d0 += kGroups) {
+    for (int d0 = 0; d0 < depths; d0 += kGroups) {
         const int d = d0 + grp;
         float acc[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-        if (d < g.D) {
-            float rx, ry;
-            sample_ref(c, g, ray, dsp[d], rx, ry);
-            bilinear_acc8(other, g, rx * (float)g.W - 0.5f, ry * (float)g.H - 0.5f, 1.0f, c0, acc);
-        }
+        if (d < depths) sample(d, c0, acc);
         float part = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) part += acc[i] * key[i];
         part = group_sum16(part);
-        if (gl == 0 && d < g.D) s_out[d & 255] = part * inv_sqrt_c;
-        if (((d0 + kGroups) & 255) == 0 || d0 + kGroups >= g.D) {
+        if (gl == 0 && d < depths) s_out[d & 255] = part * scale;
+        if (((d0 + kGroups) & 255) == 0 || d0 + kGroups >= depths) {
             __syncthreads();
             const int base = d0 & ~255;
-            const int cnt = min(256, g.D - base);
-            if ((int)threadIdx.x < cnt) out[((size_t)n * HW + p) * g.D + base + threadIdx.x] = s_out[threadIdx.x];
+            const int cnt = min(256, depths - base);
+            if ((int)threadIdx.x < cnt) out_row[base + threadIdx.x] = s_out[threadIdx.x];
             __syncthreads();
         }
     }
+}
+
+// ---- coarse: corr[n][p][d] = <sample(feat_other, loc(p, d)), feat_own[p]> / sqrt(C)
+__global__ void __launch_bounds__(kThreads)
+uv_coarse_kernel(Geo g, const float* __restrict__ feat, const float* __restrict__ cams,
+                 const float* __restrict__ disp, float* __restrict__ out) {
+    const int p = blockIdx.x, n = blockIdx.y;
+    const size_t HW = (size_t)g.H * g.W;
+    const float* other = feat + (size_t)(n ^ 1) * HW * kC;
+    const float* c = cam_ptr(cams, g, n);
+    const int b = n >> 1, v = n & 1;
+    const float* dsp = disp + (size_t)(v * g.B + b) * g.D;
+    float ray[3];
+    pixel_ray(c, (float)(p % g.W), (float)(p / g.W), ray);
+    per_depth_dot(g.D, feat + ((size_t)n * HW + p) * kC, 1.0f / sqrtf((float)kC), out + ((size_t)n * HW + p) * g.D,
+                  [&](int d, int c0, float acc[8]) {
+                      float rx, ry;
+                      sample_ref(c, g, ray, dsp[d], rx, ry);
+                      bilinear_acc8(other, g, rx * (float)g.W - 0.5f, ry * (float)g.H - 0.5f, 1.0f, c0, acc);
+                  });
 }
 
 // ---- coarse, corner-deduplicated: corr(p, d) = sum_corner w_corner <F_other[corner], key_p> / sqrt(C)
@@ -134,43 +145,132 @@ uv_coarse_kernel(Geo g, const float* __restrict__ feat, const float* __restrict_
 //   4. each lane combines its samples' 4 weighted corner dots (rank = prefix + popcount below).
 // On-chip feature traffic drops from 2 KB to ~0.5 KB per (pixel, depth) pair's share; the sum
 // order differs from the sample-then-dot form only by rounding (tests hold 1e-4 absolute).
+// Since round 6 this kernel is the run kernel's bit-for-bit reference and an A/B witness
+// (TSPLAT_UV_COARSE_BITMAP=1), not a production route.
 constexpr int kDedupWaves = 4;
 constexpr int kDedupMaxS = 4;  // D <= 256
 
-// WPE: waves per SIMD the register budget is sized for (5: 1,280 of the production launch's 2,048
-// workgroups resident; 6: 1,536). Across the phases a sample keeps its cell's index, 4 in-map bits and the
-// two bilinear fractions, not four corner indices and weights: D = 128 takes 74 VGPRs at either budget,
-// D <= 192 78, without spills; only D <= 256 at 6 spills (20 bytes per lane)
-template <int S, int WPE>
-__global__ void __launch_bounds__(kDedupWaves * 64, WPE)
-uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const float* __restrict__ cams,
+// ---- steps shared by the two dedup coarse kernels (bitmap and run): the same loads, the same
+// hand-off, the same dots and the same per-sample sum order, which is what makes their outputs equal
+// bit for bit.
+
+// The own feature (the dot operand: 8 lanes per corner, lane `sub` holds channels i*32 + sub*4 .. +3)
+// and this lane's disparities; loaded first: their latency overlaps sampling and ranking
+template <int S>
+__device__ __forceinline__ void dedup_prologue(const Geo& g, const float* __restrict__ feat,
+                                               const float* __restrict__ disp, int n, int p, int lane,
+                                               float4 (&key)[4], float (&dv)[S]) {
+    const float4* own = reinterpret_cast<const float4*>(feat + ((size_t)n * (g.H * g.W) + p) * kC) + (lane & 7);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) key[i] = own[8 * i];
+    const int b = n >> 1, v = n & 1;
+    const float* dsp = disp + (size_t)(v * g.B + b) * g.D;
+#pragma unroll
+    for (int s = 0; s < S; ++s) dv[s] = dsp[min(lane + 64 * s, g.D - 1)];
+}
+
+// The cell of depth sample `disp` and its hand-off code (y0 + 1) (W + 2) + (x0 + 1) (y0, x0 >= -1);
+// -1: the sample is not taken
+__device__ __forceinline__ int sample_cell(const float* c, const Geo& g, const float ray[3], float disp, Cell& cl) {
+    float xim, yim;
+    sample_im(c, g, ray, disp, xim, yim);
+    return cell_at(xim, yim, g.H, g.W, cl) ? (cl.y0 + 1) * (g.W + 2) + (cl.x0 + 1) : -1;
+}
+
+// The previous depth sample's cell code: lane - 1 of this slice, lane 63 of the previous one (`carry`,
+// -1 before the first slice); (py0, px0) its top-left corner, (-100, -100) if it has none
+__device__ __forceinline__ int prev_sample_cell(int cell, int lane, int W, int& carry, int& py0, int& px0) {
+    int pcell = __shfl_up(cell, 1, 64);
+    const int last = __shfl(cell, 63, 64);
+    if (lane == 0) pcell = carry;
+    carry = last;
+    py0 = pcell >= 0 ? pcell / (W + 2) - 1 : -100;
+    px0 = pcell >= 0 ? pcell % (W + 2) - 1 : -100;
+    return pcell;
+}
+
+// One dot per listed corner: 8 lanes per corner (each load instruction covers a full 128-B line of 8
+// rows), 8 corners per pass; PASSES = 2 keeps the next pass's rows in flight, PASSES = 1 one pass per
+// wave (at 8 waves per SIMD the other waves cover the latency). `other` is the other view's map at
+// this lane's float4 column; dots may overlay list: entry j is read by its 8 lanes before its dot is
+// stored there.
+template <int PASSES>
+__device__ __forceinline__ void corner_dots(const float4* __restrict__ other, const float4 (&key)[4], const int* list,
+                                            float* dots, int total, int lane) {
+    const int sub = lane & 7;
+    const int jend = (total + 7) & ~7;  // same trip count for every lane (shuffles)
+    auto load = [&](int jj, float4* x) {
+        const float4* row = other + (size_t)(jj < total ? list[jj] : 0) * (kC / 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = row[8 * i];
+    };
+    auto dot = [&](int jj, const float4* x) {
+        float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            a0 += x[i].x * key[i].x;
+            a1 += x[i].y * key[i].y;
+            a0 += x[i].z * key[i].z;
+            a1 += x[i].w * key[i].w;
+        }
+        float acc = a0 + a1;
+        acc += __shfl_xor(acc, 1, 8);
+        acc += __shfl_xor(acc, 2, 8);
+        acc += __shfl_xor(acc, 4, 8);
+        if (jj < total && sub == 0) dots[jj] = acc;
+    };
+    if constexpr (PASSES == 1) {
+        for (int j = lane >> 3; j < jend; j += 8) {
+            float4 xa[4];
+            load(j, xa);
+            dot(j, xa);
+        }
+    } else {
+        float4 xa[4], xb[4];
+        int j = lane >> 3;
+        if (j < jend) load(j, xa);
+        for (; j < jend; j += 16) {
+            if (j + 8 < jend) load(j + 8, xb);
+            dot(j, xa);
+            if (j + 16 < jend) load(j + 16, xa);
+            if (j + 8 < jend) dot(j + 8, xb);
+        }
+    }
+}
+
+// One sample = its corners' weighted dots, in corner order, / sqrt(C); rank[k] < 0: corner k is not
+// read (zero padding, or the sample is not taken)
+__device__ __forceinline__ float combine_sample(const float (&cw)[4], const int (&rank)[4], const float* dots) {
+    float val = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (rank[k] >= 0) val += cw[k] * dots[rank[k]];
+    return val * (1.0f / sqrtf((float)kC));
+}
+
+// 6 waves per SIMD is what the register budget is sized for (1,536 of the production launch's 2,048
+// workgroups resident; profiles/r5/late/corr_wpe.txt). Across the phases a sample keeps its cell's index,
+// 4 in-map bits and the two bilinear fractions, not four corner indices and weights: D = 128 takes 75
+// VGPRs, D <= 192 78, without spills; only D <= 256 spills (20 bytes per lane)
+template <int S>
+__global__ void __launch_bounds__(kDedupWaves * 64, 6)
+uv_coarse_dedup_kernel(Geo g, const float* __restrict__ feat, const float* __restrict__ cams,
                        const float* __restrict__ disp, float* __restrict__ out) {
     extern __shared__ unsigned smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = blockIdx.y;
-    const int HW = g.H * g.W;
+    const int HW = g.H * g.W, nw = (HW + 31) / 32;
     const int p = blockIdx.x * kDedupWaves + wave;
     const bool active = p < HW;
     unsigned* bm = smem + (size_t)wave * (2 * nw + 8 * g.D);
     unsigned* pre = bm + nw;
     int* list = reinterpret_cast<int*>(pre + nw);
     float* dots = reinterpret_cast<float*>(list + 4 * g.D);
-    // own feature (the dot operand: 8 lanes per corner, lane `sub` holds channels i*32 + sub*4 .. +3)
-    // and this lane's disparities are loaded first: their latency overlaps sampling and ranking
-    const int sub = lane & 7;
     const int pc = active ? p : 0;
     float4 key[4];
-    {
-        const float4* own = reinterpret_cast<const float4*>(feat + ((size_t)n * HW + pc) * kC) + sub;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) key[i] = own[8 * i];
-    }
-    const float* c = cam_ptr(cams, g, n);
-    const int b = n >> 1, v = n & 1;
-    const float* dsp = disp + (size_t)(v * g.B + b) * g.D;
     float dv[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) dv[s] = dsp[min(lane + 64 * s, g.D - 1)];
+    dedup_prologue<S>(g, feat, disp, n, pc, lane, key, dv);
+    const float* c = cam_ptr(cams, g, n);
     for (int i = lane; i < nw; i += 64) bm[i] = 0u;
     __syncthreads();
 
@@ -180,50 +280,29 @@ uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const floa
     int cbase[S];       // y0 * W + x0 of the sample's cell (its corners: + W per row, + 1 per column)
     unsigned cin = 0u;  // 4 bits per sample: which corners are inside the map
     float fr[S][2];     // (ly, lx): the corner weights are formed from them where they are used
-    const float fw = (float)g.W, fh = (float)g.H;
     float ray[3];
     pixel_ray(c, (float)(pc % g.W), (float)(pc / g.W), ray);
-    int prev_cell = -1;  // previous sample's (y0 * W + x0) + (W + 1) offset code, -1 = none
+    int prev_cell = -1;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const int d = lane + 64 * s;
-        cbase[s] = 0;
-        unsigned m = 0u;
-        fr[s][0] = fr[s][1] = 0.f;
-        int y0 = 0, x0 = 0, cell = -1;
-        if (active && d < g.D) {
-            float xim, yim;
-            sample_im(c, g, ray, dv[s], xim, yim);
-            if (yim > -1.0f && xim > -1.0f && yim < fh && xim < fw) {
-                const float fy = floorf(yim), fx = floorf(xim);
-                y0 = (int)fy;
-                x0 = (int)fx;
-                const int y1 = y0 + 1, x1 = x0 + 1;
-                fr[s][0] = yim - fy;
-                fr[s][1] = xim - fx;
-                cbase[s] = y0 * g.W + x0;
-                if (y0 >= 0 && x0 >= 0) m |= 1u;
-                if (y0 >= 0 && x1 <= g.W - 1) m |= 2u;
-                if (y1 <= g.H - 1 && x0 >= 0) m |= 4u;
-                if (y1 <= g.H - 1 && x1 <= g.W - 1) m |= 8u;
-                cell = (y0 + 1) * (g.W + 2) + (x0 + 1);  // y0, x0 >= -1
-            }
-        }
-        // the previous depth sample's cell: lane - 1 of this slice, lane 63 of the previous one
-        int pcell = __shfl_up(cell, 1, 64);
-        const int last = __shfl(cell, 63, 64);
-        if (lane == 0) pcell = prev_cell;
-        prev_cell = last;
-        const int py0 = pcell >= 0 ? pcell / (g.W + 2) - 1 : -100, px0 = pcell >= 0 ? pcell % (g.W + 2) - 1 : -100;
+        Cell cl = {0, 0, 0.f, 0.f, 0u};
+        int cell = -1;
+        if (active && d < g.D) cell = sample_cell(c, g, ray, dv[s], cl);
+        cbase[s] = cl.y0 * g.W + cl.x0;
+        fr[s][0] = cl.ly;
+        fr[s][1] = cl.lx;
+        int py0, px0;
+        prev_sample_cell(cell, lane, g.W, prev_cell, py0, px0);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            if (!((m >> k) & 1u)) continue;
+            if (!((cl.in >> k) & 1u)) continue;
             const int ci = cbase[s] + (k >> 1) * g.W + (k & 1);
-            const int yy = y0 + (k >> 1), xx = x0 + (k & 1);
+            const int yy = cl.y0 + (k >> 1), xx = cl.x0 + (k & 1);
             const bool seen = yy >= py0 && yy <= py0 + 1 && xx >= px0 && xx <= px0 + 1;
             if (!seen) atomicOr(&bm[ci >> 5], 1u << (ci & 31));
         }
-        cin |= m << (4 * s);
+        cin |= cl.in << (4 * s);
     }
     __syncthreads();
 
@@ -256,63 +335,31 @@ uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const floa
     }
     __syncthreads();
 
-    // 3. one dot per distinct corner: 8 lanes per corner (each load instruction covers a full
-    //    128-B line of 8 rows), 8 corners per pass, the next pass's rows in flight
-    if (active) {
-        const float4* other = reinterpret_cast<const float4*>(feat + (size_t)(n ^ 1) * HW * kC) + sub;
-        const int jend = (total + 7) & ~7;  // same trip count for every lane (shuffles)
-        auto load = [&](int jj, float4* x) {
-            const float4* row = other + (size_t)(jj < total ? list[jj] : 0) * (kC / 4);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x[i] = row[8 * i];
-        };
-        auto dot = [&](int jj, const float4* x) {
-            float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                a0 += x[i].x * key[i].x;
-                a1 += x[i].y * key[i].y;
-                a0 += x[i].z * key[i].z;
-                a1 += x[i].w * key[i].w;
-            }
-            float acc = a0 + a1;
-            acc += __shfl_xor(acc, 1, 8);
-            acc += __shfl_xor(acc, 2, 8);
-            acc += __shfl_xor(acc, 4, 8);
-            if (jj < total && sub == 0) dots[jj] = acc;
-        };
-        float4 xa[4], xb[4];
-        int j = lane >> 3;
-        if (j < jend) load(j, xa);
-        for (; j < jend; j += 16) {
-            if (j + 8 < jend) load(j + 8, xb);
-            dot(j, xa);
-            if (j + 16 < jend) load(j + 16, xa);
-            if (j + 8 < jend) dot(j + 8, xb);
-        }
-    }
+    // 3. one dot per distinct corner, the next pass's rows in flight
+    if (active)
+        corner_dots<2>(reinterpret_cast<const float4*>(feat + (size_t)(n ^ 1) * HW * kC) + (lane & 7), key, list, dots,
+                       total, lane);
     __syncthreads();
     if (!active) return;
 
     // 4. each sample = its corners' weighted dots (rank = word prefix + popcount below the bit)
-    const float inv_sqrt_c = 1.0f / sqrtf((float)kC);
     float* o = out + ((size_t)n * HW + p) * g.D;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const int d = lane + 64 * s;
         if (d >= g.D) continue;
-        float val = 0.f;
-        const float ly = fr[s][0], lx = fr[s][1], hy = 1.0f - ly, hx = 1.0f - lx;
-        const float cw[4] = {hy * hx, hy * lx, ly * hx, ly * lx};
+        float cw[4];
+        cell_weights(fr[s][0], fr[s][1], cw);
+        int rank[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
+            rank[k] = -1;
             if (!((cin >> (4 * s + k)) & 1u)) continue;
             const int ci = cbase[s] + (k >> 1) * g.W + (k & 1);
             const unsigned wd = bm[ci >> 5];
-            const int rank = (int)pre[ci >> 5] + __popc(wd & ((1u << (ci & 31)) - 1u));
-            val += cw[k] * dots[rank];
+            rank[k] = (int)pre[ci >> 5] + __popc(wd & ((1u << (ci & 31)) - 1u));
         }
-        o[d] = val * inv_sqrt_c;
+        o[d] = combine_sample(cw, rank, dots);
     }
 }
 
@@ -329,12 +376,12 @@ uv_coarse_dedup_kernel(Geo g, int nw, const float* __restrict__ feat, const floa
 //      runs until none is left, so a non-monotone rounding step only costs an extra dot);
 //   3. one dot per listed corner (the 8-lane row dot above, same sum order);
 //   4. each sample reads its run's 4 corner ranks (one ds_read_b128) and combines as above.
-// The result is the bitmap kernel's bit for bit (same dots, same per-sample sum order).
+// The result is the bitmap kernel's bit for bit (the shared steps above).
 constexpr int kRunWaves = 4;
 
 // LDS words per wave: src [D cells][4] ranks, then [4 D] corner pixels that the dot phase overwrites
 // with the corners' dots (entry j is read by its 8 lanes before its dot is stored there)
-__host__ __device__ inline int run_lds_words(int depths) { return 8 * depths; }
+__host__ __device__ constexpr int run_lds_words(int depths) { return 8 * depths; }
 
 // LDS hand-off between the lanes of ONE wave (its LDS operations execute in order)
 __device__ __forceinline__ void wave_lds_sync() {
@@ -343,9 +390,9 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// WPE: waves per SIMD the register budget is sized for -- 8 (default for D <= 128: 60 VGPRs, one dot
+// WPE: waves per SIMD the register budget is sized for -- 8 (default for D <= 128: 56 VGPRs, one dot
 // pass in flight per wave, all 2,048 workgroups of the production launch resident at once) or 6
-// (73 VGPRs, two passes in flight; TSPLAT_CORR_RUN_WPE=6, and D > 128)
+// (69 VGPRs, two passes in flight; TSPLAT_CORR_RUN_WPE=6, and D > 128)
 template <int S, int WPE>
 __global__ void __launch_bounds__(kRunWaves * 64, WPE)
 uv_coarse_run_kernel(Geo g, const float* __restrict__ feat, const float* __restrict__ cams,
@@ -360,63 +407,36 @@ uv_coarse_run_kernel(Geo g, const float* __restrict__ feat, const float* __restr
     int* list = src + 4 * g.D;
     float* dots = reinterpret_cast<float*>(list);
 
-    // own feature (dot operand, 8 lanes per corner) and this lane's disparities first
-    const int sub = lane & 7;
     float4 key[4];
-    {
-        const float4* own = reinterpret_cast<const float4*>(feat + ((size_t)n * HW + p) * kC) + sub;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) key[i] = own[8 * i];
-    }
-    const float* c = cam_ptr(cams, g, n);
-    const int b = n >> 1, v = n & 1;
-    const float* dsp = disp + (size_t)(v * g.B + b) * g.D;
     float dv[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) dv[s] = dsp[min(lane + 64 * s, g.D - 1)];
+    dedup_prologue<S>(g, feat, disp, n, p, lane, key, dv);
+    const float* c = cam_ptr(cams, g, n);
 
     // 1. samples -> cells, run heads, new corners
     const unsigned long long lt = (1ull << lane) - 1ull, le = lt | (1ull << lane);
-    const float fw = (float)g.W, fh = (float)g.H;
     float ray[3];
     pixel_ray(c, (float)(p % g.W), (float)(p / g.W), ray);
     int cell_of[S];    // the sample's run (distinct-cell) index, -1 = outside the sampling window
-    float cw[S][4];
+    float cw[S][4];    // corner weights, 0 for a corner that is not read
     int cells = 0, total = 0, prev_cell = -1;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const int d = lane + 64 * s;
-        int y0 = 0, x0 = 0, cell = -1, inb = 0;
+        Cell cl = {0, 0, 0.f, 0.f, 0u};
+        int cell = -1;
+        if (d < g.D) cell = sample_cell(c, g, ray, dv[s], cl);
+        cell_weights(cl.ly, cl.lx, cw[s]);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) cw[s][k] = 0.f;
-        if (d < g.D) {
-            float xim, yim;
-            sample_im(c, g, ray, dv[s], xim, yim);
-            if (yim > -1.0f && xim > -1.0f && yim < fh && xim < fw) {
-                const float fy = floorf(yim), fx = floorf(xim);
-                y0 = (int)fy;
-                x0 = (int)fx;
-                const int y1 = y0 + 1, x1 = x0 + 1;
-                const float ly = yim - fy, lx = xim - fx, hy = 1.0f - ly, hx = 1.0f - lx;
-                if (y0 >= 0 && x0 >= 0) { inb |= 1; cw[s][0] = hy * hx; }
-                if (y0 >= 0 && x1 <= g.W - 1) { inb |= 2; cw[s][1] = hy * lx; }
-                if (y1 <= g.H - 1 && x0 >= 0) { inb |= 4; cw[s][2] = ly * hx; }
-                if (y1 <= g.H - 1 && x1 <= g.W - 1) { inb |= 8; cw[s][3] = ly * lx; }
-                cell = (y0 + 1) * (g.W + 2) + (x0 + 1);  // y0, x0 >= -1
-            }
-        }
-        // the previous depth sample's cell: lane - 1 of this slice, lane 63 of the previous one
-        int pcell = __shfl_up(cell, 1, 64);
-        const int last = __shfl(cell, 63, 64);
-        if (lane == 0) pcell = prev_cell;
-        prev_cell = last;
+        for (int k = 0; k < 4; ++k)
+            if (!((cl.in >> k) & 1u)) cw[s][k] = 0.f;
+        int py0, px0;
+        const int pcell = prev_sample_cell(cell, lane, g.W, prev_cell, py0, px0);
         const bool head = cell >= 0 && cell != pcell;
-        const int py0 = pcell >= 0 ? pcell / (g.W + 2) - 1 : -100, px0 = pcell >= 0 ? pcell % (g.W + 2) - 1 : -100;
         int code[4], nnew = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int dy = y0 + (k >> 1) - py0, dx = x0 + (k & 1) - px0;
-            if (!((inb >> k) & 1)) code[k] = -1;                                   // zero padding
+            const int dy = cl.y0 + (k >> 1) - py0, dx = cl.x0 + (k & 1) - px0;
+            if (!((cl.in >> k) & 1u)) code[k] = -1;                                // zero padding
             else if (dy >= 0 && dy <= 1 && dx >= 0 && dx <= 1) code[k] = -2 - (2 * dy + dx);  // previous cell's
             else code[k] = nnew++;                                               // new: local index
         }
@@ -430,7 +450,7 @@ uv_coarse_run_kernel(Geo g, const float* __restrict__ feat, const float* __restr
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 e[k] = code[k] >= 0 ? rbase + code[k] : code[k];
-                if (code[k] >= 0) list[rbase + code[k]] = (y0 + (k >> 1)) * g.W + x0 + (k & 1);
+                if (code[k] >= 0) list[rbase + code[k]] = (cl.y0 + (k >> 1)) * g.W + cl.x0 + (k & 1);
             }
             *reinterpret_cast<int4*>(src + 4 * ci) = make_int4(e[0], e[1], e[2], e[3]);
         }
@@ -468,67 +488,23 @@ uv_coarse_run_kernel(Geo g, const float* __restrict__ feat, const float* __restr
         if (!__any(pending)) break;
     }
 
-    // 3. one dot per listed corner: 8 lanes per corner, 8 corners per pass, the next pass in flight
-    {
-        const float4* other = reinterpret_cast<const float4*>(feat + (size_t)(n ^ 1) * HW * kC) + sub;
-        const int jend = (total + 7) & ~7;
-        auto load = [&](int jj, float4* x) {
-            const float4* row = other + (size_t)(jj < total ? list[jj] : 0) * (kC / 4);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x[i] = row[8 * i];
-        };
-        auto dot = [&](int jj, const float4* x) {
-            float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                a0 += x[i].x * key[i].x;
-                a1 += x[i].y * key[i].y;
-                a0 += x[i].z * key[i].z;
-                a1 += x[i].w * key[i].w;
-            }
-            float acc = a0 + a1;
-            acc += __shfl_xor(acc, 1, 8);
-            acc += __shfl_xor(acc, 2, 8);
-            acc += __shfl_xor(acc, 4, 8);
-            if (jj < total && sub == 0) dots[jj] = acc;
-        };
-        if constexpr (WPE >= 8) {
-            // one pass in flight per wave: at 8 waves per SIMD the other waves cover the latency
-            for (int j = lane >> 3; j < jend; j += 8) {
-                float4 xa[4];
-                load(j, xa);
-                dot(j, xa);
-            }
-        } else {
-            float4 xa[4], xb[4];
-            int j = lane >> 3;
-            if (j < jend) load(j, xa);
-            for (; j < jend; j += 16) {
-                if (j + 8 < jend) load(j + 8, xb);
-                dot(j, xa);
-                if (j + 16 < jend) load(j + 16, xa);
-                if (j + 8 < jend) dot(j + 8, xb);
-            }
-        }
-    }
+    // 3. one dot per listed corner; two passes in flight only below 8 waves per SIMD
+    corner_dots<(WPE >= 8 ? 1 : 2)>(reinterpret_cast<const float4*>(feat + (size_t)(n ^ 1) * HW * kC) + (lane & 7), key,
+                                     list, dots, total, lane);
     wave_lds_sync();
 
     // 4. each sample = its run's corners' weighted dots
-    const float inv_sqrt_c = 1.0f / sqrtf((float)kC);
     float* o = out + ((size_t)n * HW + p) * g.D;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const int d = lane + 64 * s;
         if (d >= g.D) continue;
-        float val = 0.f;
+        int ev[4] = {-1, -1, -1, -1};
         if (cell_of[s] >= 0) {
             const int4 e = *reinterpret_cast<const int4*>(src + 4 * cell_of[s]);
-            const int ev[4] = {e.x, e.y, e.z, e.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (ev[k] >= 0) val += cw[s][k] * dots[ev[k]];
+            ev[0] = e.x; ev[1] = e.y; ev[2] = e.z; ev[3] = e.w;
         }
-        o[d] = val * inv_sqrt_c;
+        o[d] = combine_sample(cw[s], ev, dots);
     }
 }
 
@@ -538,9 +514,7 @@ uv_cross_kernel(Geo g, int P, const float* __restrict__ value, const float* __re
                 const float* __restrict__ cams, const float* __restrict__ disp,
                 const float* __restrict__ offsets, const float* __restrict__ logits,
                 float* __restrict__ out) {
-    __shared__ float s_out[256];
     const int p = blockIdx.x, n = blockIdx.y;
-    const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15, c0 = gl * 8;
     const size_t HW = (size_t)g.H * g.W;
     const float* other = value + (size_t)(n ^ 1) * HW * kC;
     const float* c = cam_ptr(cams, g, n);
@@ -548,52 +522,23 @@ uv_cross_kernel(Geo g, int P, const float* __restrict__ value, const float* __re
     const float* dsp = disp + (size_t)(v * g.B + b) * g.D;
     const float* off = offsets + ((size_t)n * HW + p) * g.D * P * 2;
     const float* lg = logits + ((size_t)n * HW + p) * g.D * P;
-    float kv[8];
-    {
-        const float4* s = reinterpret_cast<const float4*>(key + ((size_t)n * HW + p) * kC + c0);
-        const float4 a = s[0], bb = s[1];
-        kv[0] = a.x; kv[1] = a.y; kv[2] = a.z; kv[3] = a.w;
-        kv[4] = bb.x; kv[5] = bb.y; kv[6] = bb.z; kv[7] = bb.w;
-    }
     float ray[3];
     pixel_ray(c, (float)(p % g.W), (float)(p / g.W), ray);
     const float fw = (float)g.W, fh = (float)g.H;
-    for (int d0 = 0; d0 < g.D; d0 += kGroups) {
-        const int d = d0 + grp;
-        float acc[8];
+    per_depth_dot(g.D, key + ((size_t)n * HW + p) * kC, 1.0f / (float)kC, out + ((size_t)n * HW + p) * g.D,
+                  [&](int d, int c0, float acc[8]) {
+                      float rx, ry;
+                      sample_ref(c, g, ray, dsp[d], rx, ry);
+                      float lv[kMaxPoints], wgt[kMaxPoints];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-        if (d < g.D) {
-            float rx, ry;
-            sample_ref(c, g, ray, dsp[d], rx, ry);
-            float e[kMaxPoints];
-            float mx = -INFINITY;
-            for (int pt = 0; pt < P; ++pt) mx = fmaxf(mx, lg[d * P + pt]);
-            float ssum = 0.f;
-            for (int pt = 0; pt < P; ++pt) {
-                e[pt] = __expf(lg[d * P + pt] - mx);
-                ssum += e[pt];
-            }
-            for (int pt = 0; pt < P; ++pt) {
-                const float wgt = e[pt] / ssum;  // torch softmax over the points
-                const float lx = rx + off[(d * P + pt) * 2] / fw;
-                const float ly = ry + off[(d * P + pt) * 2 + 1] / fh;
-                bilinear_acc8(other, g, lx * fw - 0.5f, ly * fh - 0.5f, wgt, c0, acc);
-            }
-        }
-        float part = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) part += acc[i] * kv[i];
-        part = group_sum16(part);
-        if (gl == 0 && d < g.D) s_out[d & 255] = part * (1.0f / (float)kC);
-        if (((d0 + kGroups) & 255) == 0 || d0 + kGroups >= g.D) {
-            __syncthreads();
-            const int base = d0 & ~255;
-            const int cnt = min(256, g.D - base);
-            if ((int)threadIdx.x < cnt) out[((size_t)n * HW + p) * g.D + base + threadIdx.x] = s_out[threadIdx.x];
-            __syncthreads();
-        }
-    }
+                      for (int pt = 0; pt < kMaxPoints; ++pt) lv[pt] = pt < P ? lg[d * P + pt] : -INFINITY;
+                      point_softmax(P, lv, wgt);
+                      for (int pt = 0; pt < P; ++pt) {
+                          const float lx = rx + off[(d * P + pt) * 2] / fw;
+                          const float ly = ry + off[(d * P + pt) * 2 + 1] / fh;
+                          bilinear_acc8(other, g, lx * fw - 0.5f, ly * fh - 0.5f, wgt[pt], c0, acc);
+                      }
+                  });
 }
 
 // ---- cross through a correlation table (the dot products factored out of the sampling):
@@ -622,55 +567,56 @@ uv_cross_table_kernel(Geo g, int P, int C, const float* __restrict__ table, cons
     pixel_ray(c, (float)(p % g.W), (float)(p / g.W), ray);
     float rx, ry;
     sample_ref(c, g, ray, disp[(size_t)(v * g.B + b) * g.D + d], rx, ry);
-    float e[kMaxPoints];
-    float mx = -INFINITY;
-    for (int pt = 0; pt < P; ++pt) mx = fmaxf(mx, lg[pt]);
-    float ssum = 0.f;
-    for (int pt = 0; pt < P; ++pt) {
-        e[pt] = __expf(lg[pt] - mx);
-        ssum += e[pt];
-    }
+    float lv[kMaxPoints], wgt[kMaxPoints];
+#pragma unroll
+    for (int pt = 0; pt < kMaxPoints; ++pt) lv[pt] = pt < P ? lg[pt] : -INFINITY;
+    point_softmax(P, lv, wgt);
     const float fw = (float)g.W, fh = (float)g.H;
     float acc = 0.f;
     for (int pt = 0; pt < P; ++pt) {
-        const float wgt = e[pt] / ssum;
         const float xim = (rx + off[2 * pt] / fw) * fw - 0.5f;
         const float yim = (ry + off[2 * pt + 1] / fh) * fh - 0.5f;
-        if (!(yim > -1.0f && xim > -1.0f && yim < fh && xim < fw)) continue;
-        const float fy = floorf(yim), fx = floorf(xim);
-        const int y0 = (int)fy, x0 = (int)fx, y1 = y0 + 1, x1 = x0 + 1;
-        const float ly = yim - fy, lx = xim - fx, hy = 1.0f - ly, hx = 1.0f - lx;
+        Cell cl;
+        if (!cell_at(xim, yim, g.H, g.W, cl)) continue;
+        float cw[4];
+        cell_weights(cl.ly, cl.lx, cw);
         float val = 0.f;
-        if (y0 >= 0 && x0 >= 0) val += hy * hx * row[y0 * g.W + x0];
-        if (y0 >= 0 && x1 <= g.W - 1) val += hy * lx * row[y0 * g.W + x1];
-        if (y1 <= g.H - 1 && x0 >= 0) val += ly * hx * row[y1 * g.W + x0];
-        if (y1 <= g.H - 1 && x1 <= g.W - 1) val += ly * lx * row[y1 * g.W + x1];
-        acc += wgt * val;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if ((cl.in >> k) & 1u) val += cw[k] * row[(cl.y0 + (k >> 1)) * g.W + cl.x0 + (k & 1)];
+        acc += wgt[pt] * val;
     }
     out[((size_t)n * HW + p) * g.D + d] = acc / (float)C;
+}
+
+// ---- the per-query skeleton of msda_kernel / msda_raw_kernel: 16 lanes per query (8 channels each),
+// sample(n, q, c0, acc) accumulates the lane's 8 channels of out[n][q]
+template <typename Sample>
+__device__ __forceinline__ void per_query_sample(int Q, float* __restrict__ out, Sample&& sample) {
+    const int n = blockIdx.y;
+    const int q = blockIdx.x * kGroups + (threadIdx.x >> 4);
+    const int gl = threadIdx.x & 15, c0 = gl * 8;
+    if (q >= Q) return;
+    float acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+    sample(n, q, c0, acc);
+    float4* o = reinterpret_cast<float4*>(out + ((size_t)n * Q + q) * kC + c0);
+    o[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    o[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
 }
 
 // ---- single-level single-head MSDA: out[n][q] = sum_pt w_pt sample(value[n], loc_pt)
 __global__ void __launch_bounds__(kThreads)
 msda_kernel(Geo g, int Q, int P, const float* __restrict__ value, const float* __restrict__ loc,
             const float* __restrict__ weights, float* __restrict__ out) {
-    const int n = blockIdx.y;
-    const int q = blockIdx.x * kGroups + (threadIdx.x >> 4);
-    const int gl = threadIdx.x & 15, c0 = gl * 8;
-    if (q >= Q) return;
-    const size_t HW = (size_t)g.H * g.W;
-    const float* img = value + (size_t)n * HW * kC;
-    const float* lc = loc + ((size_t)n * Q + q) * P * 2;
-    const float* wt = weights + ((size_t)n * Q + q) * P;
-    float acc[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-    for (int pt = 0; pt < P; ++pt)
-        bilinear_acc8(img, g, lc[2 * pt] * (float)g.W - 0.5f, lc[2 * pt + 1] * (float)g.H - 0.5f, wt[pt],
-                      c0, acc);
-    float4* o = reinterpret_cast<float4*>(out + ((size_t)n * Q + q) * kC + c0);
-    o[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    o[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
+    per_query_sample(Q, out, [&](int n, int q, int c0, float acc[8]) {
+        const float* img = value + (size_t)n * ((size_t)g.H * g.W) * kC;
+        const float* lc = loc + ((size_t)n * Q + q) * P * 2;
+        const float* wt = weights + ((size_t)n * Q + q) * P;
+        for (int pt = 0; pt < P; ++pt)
+            bilinear_acc8(img, g, lc[2 * pt] * (float)g.W - 0.5f, lc[2 * pt + 1] * (float)g.H - 0.5f, wt[pt], c0, acc);
+    });
 }
 
 // ---- the same sampling from the raw projections (the UV self-attention's glue folded in,
@@ -678,43 +624,35 @@ msda_kernel(Geo g, int Q, int P, const float* __restrict__ value, const float* _
 // offsets then the P attention logits (one linear's output, row stride `ows`); loc_pt = ref + off /
 // (W, H) with ref = ((x + 0.5) / W, (y + 0.5) / H) (the reference points, encoder.py:61-71, same fp32
 // operations), weights = softmax(logits) -- instead of the softmax, division and addition launches
-// around msda_kernel.
+// around msda_kernel. The softmax is expf, recomputed per point, not point_softmax's __expf: the
+// kernel's bits are those of the torch launches it replaced.
 __global__ void __launch_bounds__(kThreads)
 msda_raw_kernel(Geo g, int Q, int P, const float* __restrict__ value, const float* __restrict__ ow, int ows,
                 float* __restrict__ out) {
-    const int n = blockIdx.y;
-    const int q = blockIdx.x * kGroups + (threadIdx.x >> 4);
-    const int gl = threadIdx.x & 15, c0 = gl * 8;
-    if (q >= Q) return;
-    const size_t HW = (size_t)g.H * g.W;
-    const float* img = value + (size_t)n * HW * kC;
-    const float* r = ow + ((size_t)n * Q + q) * ows;
-    const float fw = (float)g.W, fh = (float)g.H;
-    const int qy = q / g.W, qx = q - qy * g.W;
-    const float rx = ((float)qx + 0.5f) / fw, ry = ((float)qy + 0.5f) / fh;
-    float m = -INFINITY;
-    for (int pt = 0; pt < P; ++pt) m = fmaxf(m, r[2 * P + pt]);
-    float sum = 0.f;
-    for (int pt = 0; pt < P; ++pt) sum += expf(r[2 * P + pt] - m);
-    float acc[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-    for (int pt = 0; pt < P; ++pt) {
-        const float wt = expf(r[2 * P + pt] - m) / sum;
-        const float lx = rx + r[2 * pt] / fw, ly = ry + r[2 * pt + 1] / fh;
-        bilinear_acc8(img, g, lx * fw - 0.5f, ly * fh - 0.5f, wt, c0, acc);
-    }
-    float4* o = reinterpret_cast<float4*>(out + ((size_t)n * Q + q) * kC + c0);
-    o[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    o[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
+    per_query_sample(Q, out, [&](int n, int q, int c0, float acc[8]) {
+        const float* img = value + (size_t)n * ((size_t)g.H * g.W) * kC;
+        const float* r = ow + ((size_t)n * Q + q) * ows;
+        const float fw = (float)g.W, fh = (float)g.H;
+        const int qy = q / g.W, qx = q - qy * g.W;
+        const float rx = ((float)qx + 0.5f) / fw, ry = ((float)qy + 0.5f) / fh;
+        float m = -INFINITY;
+        for (int pt = 0; pt < P; ++pt) m = fmaxf(m, r[2 * P + pt]);
+        float sum = 0.f;
+        for (int pt = 0; pt < P; ++pt) sum += expf(r[2 * P + pt] - m);
+        for (int pt = 0; pt < P; ++pt) {
+            const float wt = expf(r[2 * P + pt] - m) / sum;
+            const float lx = rx + r[2 * pt] / fw, ly = ry + r[2 * pt + 1] / fh;
+            bilinear_acc8(img, g, lx * fw - 0.5f, ly * fh - 0.5f, wt, c0, acc);
+        }
+    });
 }
 
 // ---- mmcv ms_deform_attn_forward, general form: value [bs][num_keys][heads][hd] (level l's
 // H_l x W_l map starts at key level_start[l]), sampling_loc [bs][nq][heads][L][P][2] (x, y in
 // [0, 1]), attn_weight [bs][nq][heads][L][P] -> out [bs][nq][heads * hd]. One thread per (query,
 // head, VEC channels): consecutive threads read consecutive channels of a value row. Sampling as
-// mmcv's im2col bilinear: h = y H - 1/2, w = x W - 1/2, taken only for -1 < h < H, -1 < w < W,
-// corners outside the map read as 0, val = w1 v1 + w2 v2 + w3 v3 + w4 v4, col += val * weight.
+// mmcv's im2col bilinear (corr_cell.h): h = y H - 1/2, w = x W - 1/2, the cell's corners outside the
+// map read as 0, val = w1 v1 + w2 v2 + w3 v3 + w4 v4, col += val * weight.
 template <int VEC>
 __global__ void __launch_bounds__(kThreads)
 ms_deform_attn_kernel(const float* __restrict__ value, const int64_t* __restrict__ shapes,
@@ -742,19 +680,19 @@ ms_deform_attn_kernel(const float* __restrict__ value, const int64_t* __restrict
             const float hi = ll[2 * (l * P + p) + 1] * (float)H - 0.5f;
             const float wi = ll[2 * (l * P + p)] * (float)W - 0.5f;
             const float wt = lw[l * P + p];
-            if (!(hi > -1.0f && wi > -1.0f && hi < (float)H && wi < (float)W)) continue;
-            const int h0 = (int)floorf(hi), w0 = (int)floorf(wi), h1 = h0 + 1, w1 = w0 + 1;
-            const float lh = hi - (float)h0, lwt = wi - (float)w0, hh = 1.0f - lh, hwt = 1.0f - lwt;
-            const float f1 = hh * hwt, f2 = hh * lwt, f3 = lh * hwt, f4 = lh * lwt;
-            const bool ok1 = h0 >= 0 && w0 >= 0, ok2 = h0 >= 0 && w1 <= W - 1;
-            const bool ok3 = h1 <= H - 1 && w0 >= 0, ok4 = h1 <= H - 1 && w1 <= W - 1;
+            Cell cl;
+            if (!cell_at(wi, hi, H, W, cl)) continue;
+            float f[4];
+            cell_weights(cl.ly, cl.lx, f);
+            // four arrays and one expression per channel, as they always stood: which of its products the
+            // compiler contracts depends on how it vectorises this, and the kernel's bits on that
             float v1[VEC], v2[VEC], v3[VEC], v4[VEC];
-            auto fetch = [&](bool ok, int y, int x, float (&v)[VEC]) {
-                if (ok) {
-                    const float* src = base + ((size_t)y * W + x) * row;
+            auto fetch = [&](int k, float (&v)[VEC]) {
+                if ((cl.in >> k) & 1u) {
+                    const float* src = base + ((size_t)(cl.y0 + (k >> 1)) * W + cl.x0 + (k & 1)) * row;
                     if constexpr (VEC == 4) {
-                        const float4 f = *reinterpret_cast<const float4*>(src);
-                        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+                        const float4 x = *reinterpret_cast<const float4*>(src);
+                        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
                     } else {
 #pragma unroll
                         for (int i = 0; i < VEC; ++i) v[i] = src[i];
@@ -764,12 +702,12 @@ ms_deform_attn_kernel(const float* __restrict__ value, const int64_t* __restrict
                     for (int i = 0; i < VEC; ++i) v[i] = 0.f;
                 }
             };
-            fetch(ok1, h0, w0, v1);
-            fetch(ok2, h0, w1, v2);
-            fetch(ok3, h1, w0, v3);
-            fetch(ok4, h1, w1, v4);
+            fetch(0, v1);
+            fetch(1, v2);
+            fetch(2, v3);
+            fetch(3, v4);
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) acc[i] += (f1 * v1[i] + f2 * v2[i] + f3 * v3[i] + f4 * v4[i]) * wt;
+            for (int i = 0; i < VEC; ++i) acc[i] += (f[0] * v1[i] + f[1] * v2[i] + f[2] * v3[i] + f[3] * v4[i]) * wt;
         }
     }
     float* o = out + (t * nh + head) * (size_t)hd + cg * VEC;
@@ -779,6 +717,34 @@ ms_deform_attn_kernel(const float* __restrict__ value, const int64_t* __restrict
 #pragma unroll
         for (int i = 0; i < VEC; ++i) o[i] = acc[i];
     }
+}
+
+// ---- which coarse kernel a launch takes. The run kernel serves D <= 256 (S = ceil(D / 64) <= 4
+// samples per lane), at the 8-wave budget unless TSPLAT_CORR_RUN_WPE=6; S >= 3 spills at 8 waves, so
+// both of its columns hold the 6-wave kernel. The bitmap and the plain kernel are A/B switches; the
+// plain kernel also serves D > 256 and maps whose bitmap does not fit the LDS.
+using CoarseKernel = void (*)(Geo, const float*, const float*, const float*, float*);
+constexpr CoarseKernel kRunKernel[kDedupMaxS][2] = {  // [S - 1][budget: 0 = 6 waves per SIMD, 1 = 8]
+    {uv_coarse_run_kernel<1, 6>, uv_coarse_run_kernel<1, 8>},
+    {uv_coarse_run_kernel<2, 6>, uv_coarse_run_kernel<2, 8>},
+    {uv_coarse_run_kernel<3, 6>, uv_coarse_run_kernel<3, 6>},
+    {uv_coarse_run_kernel<4, 6>, uv_coarse_run_kernel<4, 6>},
+};
+constexpr CoarseKernel kBitmapKernel[kDedupMaxS] = {uv_coarse_dedup_kernel<1>, uv_coarse_dedup_kernel<2>,
+                                                    uv_coarse_dedup_kernel<3>, uv_coarse_dedup_kernel<4>};
+static_assert((size_t)kRunWaves * run_lds_words(64 * kDedupMaxS) * sizeof(int) <= 64 * 1024,
+              "the run kernel's LDS fits at every depth count it serves");
+
+struct CoarseKnobs {
+    bool direct;  // TSPLAT_UV_COARSE_DIRECT=1: the sample-then-dot kernel
+    bool bitmap;  // TSPLAT_UV_COARSE_BITMAP=1: the round-2 bitmap dedup kernel
+    bool run6;    // TSPLAT_CORR_RUN_WPE=6: the run kernel at the 6-wave budget
+};
+static CoarseKnobs read_knobs() {
+    const char* d = getenv("TSPLAT_UV_COARSE_DIRECT");
+    const char* b = getenv("TSPLAT_UV_COARSE_BITMAP");
+    const char* r = getenv("TSPLAT_CORR_RUN_WPE");
+    return {d && d[0] == '1', b && b[0] == '1', r && atoi(r) == 6};
 }
 
 }  // namespace corr
@@ -829,57 +795,20 @@ extern "C" int tsplat_uv_coarse_fwd(const float* feat, const float* cams, const 
     Geo g{batch, height, width, depths};
     hipStream_t stream = (hipStream_t)stream_;
     const int hw = height * width;
-    const int nw = (hw + 31) / 32;
-    const size_t lds = (size_t)kDedupWaves * (2 * nw + 8 * depths) * sizeof(unsigned);
     const int S = (depths + 63) / 64;
+    const CoarseKnobs knobs = read_knobs();
+    const size_t bitmap_lds = (size_t)kDedupWaves * (2 * ((hw + 31) / 32) + 8 * depths) * sizeof(unsigned);
     TSPLAT_PROF_BEGIN(prof::kUvCoarse, stream);
-    const char* env = getenv("TSPLAT_UV_COARSE_DIRECT");  // A/B switch: the sample-then-dot kernel
-    const char* benv = getenv("TSPLAT_UV_COARSE_BITMAP");  // A/B switch: the round-2 bitmap dedup kernel
-    const size_t run_lds = (size_t)kRunWaves * run_lds_words(depths) * sizeof(int);
-    if (S <= kDedupMaxS && run_lds <= 64 * 1024 && !(env && env[0] == '1') && !(benv && benv[0] == '1')) {
-        const dim3 grid(ceil_div(hw, kRunWaves), 2 * batch), block(kRunWaves * 64);
-        const char* renv = getenv("TSPLAT_CORR_RUN_WPE");
-        const bool w8 = !renv || atoi(renv) != 6;
-#define TSPLAT_UVR(SS)                                                                                           \
-    do {                                                                                                         \
-        if (w8)                                                                                                  \
-            hipLaunchKernelGGL((uv_coarse_run_kernel<SS, 8>), grid, block, run_lds, stream, g, feat, cams, disp, out); \
-        else                                                                                                     \
-            hipLaunchKernelGGL((uv_coarse_run_kernel<SS, 6>), grid, block, run_lds, stream, g, feat, cams, disp, out); \
-    } while (0)
-        switch (S) {  // (S >= 3 spills at the 8-wave budget: 6)
-            case 1: TSPLAT_UVR(1); break;
-            case 2: TSPLAT_UVR(2); break;
-            case 3: hipLaunchKernelGGL((uv_coarse_run_kernel<3, 6>), grid, block, run_lds, stream, g, feat, cams, disp, out); break;
-            default: hipLaunchKernelGGL((uv_coarse_run_kernel<4, 6>), grid, block, run_lds, stream, g, feat, cams, disp, out); break;
-        }
-#undef TSPLAT_UVR
-    } else if (S <= kDedupMaxS && lds <= 64 * 1024 && !(env && env[0] == '1')) {
-        const dim3 grid(ceil_div(hw, kDedupWaves), 2 * batch), block(kDedupWaves * 64);
-        // 6 waves per SIMD (default; profiles/r5/late/corr_wpe.txt: b = 8 120.5 -> 111.4 us, b = 1 24.3 /
-        // 24.2 vs 24.2 / 24.6) or 5 (TSPLAT_CORR_WPE=5, the A/B knob)
-        const char* wenv = getenv("TSPLAT_CORR_WPE");
-        const bool w6 = !wenv || atoi(wenv) != 5;
-#define TSPLAT_UVC(SS)                                                                                           \
-    do {                                                                                                         \
-        if (w6)                                                                                                  \
-            hipLaunchKernelGGL((uv_coarse_dedup_kernel<SS, 6>), grid, block, lds, stream, g, nw, feat, cams, disp, \
-                               out);                                                                             \
-        else                                                                                                     \
-            hipLaunchKernelGGL((uv_coarse_dedup_kernel<SS, 5>), grid, block, lds, stream, g, nw, feat, cams, disp, \
-                               out);                                                                             \
-    } while (0)
-        switch (S) {
-            case 1: TSPLAT_UVC(1); break;
-            case 2: TSPLAT_UVC(2); break;
-            case 3: TSPLAT_UVC(3); break;
-            default: TSPLAT_UVC(4); break;
-        }
-#undef TSPLAT_UVC
-    } else {
+    if (S <= kDedupMaxS && !knobs.direct && !knobs.bitmap)
+        hipLaunchKernelGGL(kRunKernel[S - 1][knobs.run6 ? 0 : 1], dim3(ceil_div(hw, kRunWaves), 2 * batch),
+                           dim3(kRunWaves * 64), (size_t)kRunWaves * run_lds_words(depths) * sizeof(int), stream, g,
+                           feat, cams, disp, out);
+    else if (S <= kDedupMaxS && !knobs.direct && bitmap_lds <= 64 * 1024)
+        hipLaunchKernelGGL(kBitmapKernel[S - 1], dim3(ceil_div(hw, kDedupWaves), 2 * batch), dim3(kDedupWaves * 64),
+                           bitmap_lds, stream, g, feat, cams, disp, out);
+    else
         hipLaunchKernelGGL(uv_coarse_kernel, dim3(hw, 2 * batch), dim3(kThreads), 0, stream, g, feat, cams, disp,
                            out);
-    }
     TSPLAT_PROF_END(prof::kUvCoarse, stream);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;

@@ -1,9 +1,11 @@
 // Camera geometry shared by the correlation kernels (corr.hip, uvfused.hip): every kernel that
 // places depth samples does it through these helpers, with fma contraction off, so they all place
-// them identically.
+// them identically. What a placed sample reads is corr_cell.h's; the softmax over a (pixel, depth)
+// pair's points is here too, for the three kernels that weight their samples by it.
 #pragma once
 
 #include "common.h"
+#include "corr_cell.h"
 
 namespace tsplat {
 namespace corr {
@@ -55,6 +57,23 @@ __device__ __forceinline__ void sample_ref(const float* c, const Geo& g, const f
     const float gy = 2.0f * (v / w) / (float)(g.H - 1) - 1.0f;
     rx = gx / 2.0f + 0.5f;
     ry = gy / 2.0f + 0.5f;
+}
+
+// torch softmax over the P <= PMAX points of a (pixel, depth) pair, fast exponential: lv holds the
+// logits, -INFINITY from P on (or all PMAX of them when P == PMAX); w[pt >= P] = 0
+template <int PMAX>
+__device__ __forceinline__ void point_softmax(int P, const float (&lv)[PMAX], float (&w)[PMAX]) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int pt = 0; pt < PMAX; ++pt) mx = fmaxf(mx, lv[pt]);
+    float ssum = 0.f;
+#pragma unroll
+    for (int pt = 0; pt < PMAX; ++pt) {
+        w[pt] = pt < P ? __expf(lv[pt] - mx) : 0.f;
+        ssum += w[pt];
+    }
+#pragma unroll
+    for (int pt = 0; pt < PMAX; ++pt) w[pt] = w[pt] / ssum;
 }
 
 }  // namespace corr

@@ -125,40 +125,27 @@ __device__ __forceinline__ void sample_points(const Geo& g, int P, const float* 
     pixel_ray(c, (float)(p % g.W), (float)(p / g.W), ray);
     float rx, ry;
     sample_ref(c, g, ray, dsp, rx, ry);
-    float mx = -INFINITY;
-#pragma unroll
-    for (int pt = 0; pt < PMAX; ++pt) mx = fmaxf(mx, r.lv[pt]);
-    float e[PMAX], ssum = 0.f;
-#pragma unroll
-    for (int pt = 0; pt < PMAX; ++pt) {
-        e[pt] = pt < P ? __expf(r.lv[pt] - mx) : 0.f;
-        ssum += e[pt];
-    }
+    point_softmax(P, r.lv, s.w);
     const float fw = (float)g.W, fh = (float)g.H;
 #pragma unroll
     for (int pt = 0; pt < PMAX; ++pt) {
-        s.w[pt] = e[pt] / ssum;  // torch softmax over the points
         s.x[pt] = pt < P ? (rx + r.ov[2 * pt] / fw) * fw - 0.5f : -2.0f;
         s.y[pt] = pt < P ? (ry + r.ov[2 * pt + 1] / fh) * fh - 0.5f : -2.0f;
     }
 }
 
 // f(k, inside, pixel index, w x bilinear weight) for the 4 corners k of the sample at (xim, yim);
-// inside: the corner counts (mmcv: samples with -1 < y < H, -1 < x < W, corners outside the map
-// zero-padded). Branch-free, so the gather's 4 LDS reads of a point are in flight together; the
-// marking pass and the gather both walk the stored points through this.
+// inside: the corner counts (the cell of corr_cell.h; a sample that is not taken has the corner
+// (-1, -1) and no corner inside). Branch-free, so the gather's 4 LDS reads of a point are in flight
+// together; the marking pass and the gather both walk the stored points through this.
 template <typename F>
 __device__ __forceinline__ void point_corners(const Geo& g, float xim, float yim, float w, F&& f) {
-    const float fw = (float)g.W, fh = (float)g.H;
-    const bool in = yim > -1.0f && xim > -1.0f && yim < fh && xim < fw;
-    const float fy = floorf(yim), fx = floorf(xim);
-    const int y0 = in ? (int)fy : -1, x0 = in ? (int)fx : -1, y1 = y0 + 1, x1 = x0 + 1;
-    const float ly = yim - fy, lx = xim - fx, hy = 1.0f - ly, hx = 1.0f - lx;
-    const bool ty = in && y0 >= 0, by = in && y1 <= g.H - 1, lf = x0 >= 0, rt = x1 <= g.W - 1;
-    f(0, ty && lf, y0 * g.W + x0, w * (hy * hx));
-    f(1, ty && rt, y0 * g.W + x1, w * (hy * lx));
-    f(2, by && lf, y1 * g.W + x0, w * (ly * hx));
-    f(3, by && rt, y1 * g.W + x1, w * (ly * lx));
+    Cell cl;
+    cell_at(xim, yim, g.H, g.W, cl);
+    float cw[4];
+    cell_weights(cl.ly, cl.lx, cw);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f(k, (cl.in >> k) & 1u, (cl.y0 + (k >> 1)) * g.W + (cl.x0 + (k & 1)), w * cw[k]);
 }
 
 // PMAX = 4 or 8 points: a thread keeps the sample points of 32 / PMAX pairs in registers from the
@@ -306,7 +293,8 @@ uv_cross_fused_kernel(Geo g, int P, const uint4* __restrict__ vpack, const float
                     // a corner outside the band (or the map) reads some column of the row and drops the value
                     point_corners(g, x, y, pts[j].w[pt], [&](int, bool inside, int idx, float w) {
                         const float v = grow[idx & (kBand - 1)];
-                        acc[j] += w * (inside && (idx >> kBandShift) == band ? v : 0.f);
+                        // & not &&: no short-circuit branch for the compiler to sink the LDS read into
+                        acc[j] += w * (inside & ((idx >> kBandShift) == band) ? v : 0.f);
                     });
                 }
             }
