@@ -51,7 +51,8 @@ int tsplat_set_debug(int32_t on);
  * kernel (ids: 1 raster preprocess, 2 raster scan, 3 raster scatter, 4 raster render,
  * 5 uv coarse correlation, 6 uv cross correlation, 7 msda, 8 window attention, 9 the whole
  * rasterizer launch sequence, 10 group norm (both launches), 11 uv cross through the
- * correlation table; 0 = off).
+ * correlation table, 17 rasterizer backward render, 18 rasterizer backward preprocess, 19 the
+ * whole tsplat_raster_bwd launch sequence; 0 = off).
  * tsplat_prof_read waits for the recorded events, returns the summed duration and the number of
  * launches timed since the last enable/read, and resets the record. Used by bench.py only. */
 int tsplat_prof_enable(int32_t kernel_id);
@@ -140,6 +141,42 @@ int tsplat_raster_depth_fwd(const tsplat_raster_desc* desc,
                             int32_t depth_mode,
                             float* out_color, float* out_depth, float* out_alpha,
                             int32_t* out_radii, void* workspace, int32_t* status, void* stream);
+
+/* Backward of tsplat_raster_fwd in the Gaussians: the vector-Jacobian product of
+ *   F : (means, cov, shs, opacity) -> out_color
+ * for a given grad_color [V, 3, H, W], with the cameras, the background, the scale, sh_degree and
+ * every discrete decision of the forward held fixed (near-plane cull, det != 0, radius and tile
+ * rectangle, the (depth, id) order, power > 0, alpha < 1/255, test_T < 1e-4). Piecewise rules: a
+ * colour channel clamped at 0 passes nothing; an (entry, pixel) whose alpha is capped at 0.99 passes
+ * nothing to conic, mean and opacity (it still attenuates T); where vx/tz or vy/tz is clamped to
+ * +-1.3 tan(fov) the derivative is that of the clamped expression; the view direction's part of
+ * d means is included; grad_cov lands on the six upper-triangle entries the forward reads (the lower
+ * three get 0); SH coefficients above sh_degree get 0; s and s*s of scene_scale are in the chain.
+ * This is the exact derivative of what the forward computes (the published upstream backward
+ * ignores the 0.99 cap and the dependence of the clamped tx, ty on tz). No gradient of depth or
+ * alpha outputs, none with respect to cameras or background.
+ *
+ * out_color and radii are the outputs of the tsplat_raster_fwd call being differentiated,
+ * fwd_workspace its workspace, untouched since (its records, tile offsets and instance keys are
+ * read; the keys of tile lists longer than 4,096 are re-sorted in place, to the same order).
+ * bwd_workspace: tsplat_raster_bwd_workspace_bytes(G, V) bytes, 256-byte aligned: one 64-byte
+ * gradient record per (view, Gaussian), cleared by the call.
+ * grad_means [S, G, 3], grad_cov [S, G, 3, 3], grad_shs [S, G, 3, M], grad_opacity [S, G]: each
+ * may be NULL (not wanted), not all four; every row is written (0 for a Gaussian rendered nowhere).
+ * The per-pixel sums reach the gradient records by float atomic adds, so the last bits of the
+ * gradients can differ from run to run. TSPLAT_EINVAL, before any launch, for a NULL required
+ * pointer, all four outputs NULL, or a descriptor tsplat_raster_fwd would reject. */
+size_t tsplat_raster_bwd_workspace_bytes(int32_t num_gaussians, int32_t num_views);
+
+int tsplat_raster_bwd(const tsplat_raster_desc* desc,
+                      const float* means, const float* cov, const float* shs,
+                      const float* opacity, const float* viewmat, const float* projmat,
+                      const float* campos, const float* tanfov, const float* bg,
+                      const float* scene_scale,
+                      const float* out_color, const float* grad_color, const int32_t* radii,
+                      void* fwd_workspace, void* bwd_workspace,
+                      float* grad_means, float* grad_cov, float* grad_shs, float* grad_opacity,
+                      void* stream);
 
 
 /* Depth-candidate softmax head (reference depth_predictor_trans.py:170-180): logits [n, depths, hw]

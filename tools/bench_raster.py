@@ -8,7 +8,11 @@ the times mean something).
 depth from the one fused pass (tsplat_raster_depth_fwd), colour + depth by the two-pass route
 (TSPLAT_DEPTH_FUSED=0: a second rasterizer run over the Gaussians repeated per view), and the
 depth-only call. HIP events around --iters eager calls per sample, the routes alternating inside
-one process for --rounds samples each; prints the median, lowest and highest per-call time."""
+one process for --rounds samples each; prints the median, lowest and highest per-call time.
+
+--backward: what the backward (tsplat_raster_bwd through rasterize_differentiable) costs at the same
+shape beside the forward call of the same process, its two kernels separately, and the render-backward
+kernel's atomic bytes over its time against the chip-wide float-atomic rate."""
 import argparse
 import os
 import sys
@@ -25,7 +29,8 @@ ap.add_argument("--iters", type=int, default=30)
 ap.add_argument("--diag", default="0,2,3")
 ap.add_argument("--waves", action="store_true", help="per-wave cost distribution (diag 5)")
 ap.add_argument("--depth", default=None, metavar="MODE", help="time the depth routes (a DepthRenderingMode)")
-ap.add_argument("--rounds", type=int, default=15, help="--depth: samples per route")
+ap.add_argument("--rounds", type=int, default=15, help="--depth, --backward: samples per route")
+ap.add_argument("--backward", action="store_true", help="time tsplat_raster_bwd and its two kernels beside the forward")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 
@@ -90,6 +95,66 @@ def depth_routes(mode: str) -> None:
                   f"rasterizer call(s) each)", flush=True)
 
 
+def backward_cost() -> None:
+    """tsplat_raster_bwd beside tsplat_raster_fwd in one process: HIP events inside the library around
+    the forward launch sequence, the backward launch sequence (zero fill included) and its two kernels,
+    --rounds samples of --iters forward + backward pairs each; then the render-backward kernel's atomic
+    bytes (entries reaching a wave, the forward's diag-5 counters of the same walk, x 9 floats: an upper
+    bound, exact zeros are not added) over its time, against the chip-wide float-atomic rate."""
+    from statistics import median
+
+    from transplat_amd import synthetic as S
+    from transplat_amd.model.decoder.hip_splatting import prepare_cameras, rasterize, rasterize_differentiable
+
+    hw = (256, 256)
+    g = S.make_gaussians(1, image_shape=hw, device=dev)
+    tb = S.make_batch(1, image_shape=hw, device=dev)["target"]
+    b, v = tb["near"].shape
+    cams = prepare_cameras(tb["extrinsics"].reshape(b * v, 4, 4), tb["intrinsics"].reshape(b * v, 3, 3),
+                           tb["near"].reshape(-1), tb["far"].reshape(-1), torch.zeros(b * v, 3, device=dev))
+    leaves = [g[k].clone().requires_grad_() for k in ("means", "covariances", "harmonics", "opacities")]
+    grad_color = torch.randn((b * v, 3, *hw), generator=torch.Generator(device=dev).manual_seed(1), device=dev)
+
+    def pair():
+        color, _ = rasterize_differentiable(*leaves, cams, hw, v, check=False)
+        for t in leaves:
+            t.grad = None
+        color.backward(grad_color)
+
+    for _ in range(3):
+        pair()
+    torch.cuda.synchronize()
+    ids = ("raster", "raster_bwd", "raster_bwd_render", "raster_bwd_preprocess")
+    us = {k: [] for k in ids}
+    for _ in range(args.rounds):
+        for k in ids:
+            _lib.prof_enable(k)
+            for _ in range(args.iters):
+                pair()
+            ms, n = _lib.prof_read()
+            _lib.prof_enable(None)
+            us[k].append(ms / n * 1e3)
+    label = {"raster": "forward call", "raster_bwd": "backward call", "raster_bwd_render": "  render_bwd_kernel",
+             "raster_bwd_preprocess": "  preprocess_bwd_kernel"}
+    for k in ids:
+        print(f"{label[k]:>24}: median {median(us[k]):8.1f} us (min {min(us[k]):.1f}, max {max(us[k]):.1f}; "
+              f"{args.rounds} samples x {args.iters} calls, {b * v} views, G = {g['means'].shape[1]}, 256x256)", flush=True)
+    os.environ["TSPLAT_RASTER_DIAG"] = "5"
+    with torch.no_grad():
+        counters = rasterize(*leaves, cams, hw, v, check=False)[0]
+    torch.cuda.synchronize()
+    os.environ["TSPLAT_RASTER_DIAG"] = "0"
+    entries = float(counters.reshape(-1, 3, hw[0] // 8, 8, hw[1] // 8, 8)[:, 1, :, 0, :, 0].double().sum())
+    nbytes = entries * 9 * 4
+    t = median(us["raster_bwd_render"]) * 1e-6
+    print(f"render_bwd_kernel atomics: {entries:.4g} (wave, entry) instances x 36 B = {nbytes / 1e6:.1f} MB per launch "
+          f"(upper bound), / {t * 1e6:.1f} us = {nbytes / t / 1e12:.3f} TB/s against the chip-wide float-atomic rate "
+          f"of about 1.3 TB/s (floor {nbytes / 1.3e12 * 1e6:.1f} us)", flush=True)
+
+
+if args.backward:
+    backward_cost()
+    sys.exit(0)
 if args.depth:
     depth_routes(args.depth)
     sys.exit(0)

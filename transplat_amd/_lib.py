@@ -50,6 +50,11 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.POINTER(RasterDesc)] + [_P] * 12 + [_I32] + [_P] * 7,
     ),
+    "tsplat_raster_bwd_workspace_bytes": (ctypes.c_size_t, [_I32, _I32]),
+    "tsplat_raster_bwd": (
+        ctypes.c_int,
+        [ctypes.POINTER(RasterDesc)] + [_P] * 20,
+    ),
     "tsplat_uv_coarse_fwd": (ctypes.c_int, [_P] * 4 + [_I32] * 5 + [_P]),
     "tsplat_uv_cross_fwd": (ctypes.c_int, [_P] * 7 + [_I32] * 6 + [_P]),
     "tsplat_uv_cross_table_fwd": (ctypes.c_int, [_P] * 6 + [_I32] * 6 + [_P]),
@@ -216,7 +221,7 @@ def stream_ptr(device: torch.device | None = None) -> int:
 PROF_IDS = {"raster_preprocess": 1, "raster_scan": 2, "raster_scatter": 3, "raster_render": 4,
             "uv_coarse": 5, "uv_cross": 6, "msda": 7, "win_attn": 8, "raster": 9,
             "group_norm": 10, "uv_cross_table": 11, "linear": 12, "mha": 13, "conv": 14, "wino_conv": 15,
-            "gemm_x3": 16}
+            "gemm_x3": 16, "raster_bwd_render": 17, "raster_bwd_preprocess": 18, "raster_bwd": 19}
 
 
 def prof_enable(name: str | None) -> None:

@@ -27,7 +27,10 @@ enum KernelId : int {
     kConv = 14,       // tsplat_conv2d_f32_fwd
     kWinoConv = 15,   // tsplat_conv3x3_wino_f32_fwd
     kGemmX3 = 16,     // tsplat_gemm_x3_fwd
-    kNumKernels = 17,
+    kRasterBwdRender = 17,      // render_bwd_kernel
+    kRasterBwdPreprocess = 18,  // preprocess_bwd_kernel
+    kRasterBwdAll = 19,         // the whole tsplat_raster_bwd launch sequence (zero fill included)
+    kNumKernels = 20,
 };
 
 int active();                 // kernel id being timed (0 = off)

@@ -1,4 +1,6 @@
-// Gaussian-splat forward rasterizer for gfx950 (MI355X).
+// Gaussian-splat rasterizer for gfx950 (MI355X): the forward, and the backward of its colour render
+// in the Gaussians (tsplat_raster_bwd: render_bwd_kernel and preprocess_bwd_kernel, after the forward
+// kernels below, which it leaves as they are and whose steps it reuses).
 //
 // Algorithm = the graphdeco forward rasterizer behind `GaussianRasterizer` as called by
 // `render_cuda` (reference src/model/decoder/cuda_splatting.py:56-136): preprocess (cull at
@@ -980,6 +982,515 @@ render_kernel(Params p, const float* __restrict__ bg, float* __restrict__ out_co
     }
 }
 
+// =============================================================================================
+// Backward of render_kernel<true, false> / preprocess_kernel<true, false> (tsplat_raster_bwd): the
+// exact vector-Jacobian product of the colour render in (means, covariances, SH, opacities) with
+// every discrete decision of the forward held fixed. Two launches after a zero fill of the
+// gradient records:
+//   render_bwd_kernel      per (view, Gaussian): sums over pixels of d px, d py, d conic (a, b, c),
+//                          d opacity, d rgb -> 64-byte gradient records (float atomics)
+//   preprocess_bwd_kernel  per Gaussian: the chain conic <- 2-D covariance <- J R <- (3-D
+//                          covariance, mean), pixel mean <- projection, colour <- SH and view
+//                          direction, s and s^2; summed over the scene's views in registers
+// =============================================================================================
+constexpr int kGradRecFloats = 16;  // gradient record of a (view, Gaussian): 64 bytes = one atomic request
+// fields of a gradient record: 0 px, 1 py (pixel-space mean); 2 3 4 the PLAIN conic (a, b, c) of
+// power = -(a dx^2 + c dy^2) / 2 - b dx dy (not the log2-scaled form the forward stores: the
+// factors log2(e) ln(2) cancel here, so preprocess_bwd_kernel needs no constant); 5 opacity;
+// 6 7 8 the clamped colour max(r + 0.5, 0); 9..15 padding
+constexpr int kGradFields = 9;
+constexpr int kAccStride = 12;      // floats per entry of a wave's LDS sums (9 used)
+
+// Data-parallel-primitive reads of another lane's value inside the VALU (no LDS crossbar trip, unlike
+// __shfl_xor's ds_bpermute): a lane with no source lane reads 0. Controls: quad_perm [1, 0, 3, 2] and
+// [2, 3, 0, 1] (lane ^ 1, lane ^ 2), row_shl:n (lane + n of the same 16-lane row).
+constexpr int kDppQuadXor1 = 0xB1, kDppQuadXor2 = 0x4E, kDppRowShl4 = 0x104, kDppRowShl8 = 0x108;
+template <int kCtrl>
+__device__ __forceinline__ float dpp_f32(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), kCtrl, 0xf, 0xf, true));
+}
+
+// --- B1: per-tile re-sort + front-to-back walk with the saved forward colour -------------------
+// One workgroup per (tile, view), the forward's mapping. The tile list is re-sorted from the
+// forward's workspace through the forward's own three paths (same functions, same total order on
+// (depth bits, id)), and each wave walks it with the forward's cull, compaction and blend decisions
+// (the same expressions under this file's contraction-off rule, so T, alpha and every branch are
+// the forward's bit for bit; early exit included). Walk direction: FRONT TO BACK. With g the
+// colour gradient at the pixel, O = out . g from the saved forward output (background term
+// included) and S_i = O - sum_{j <= i} w_j (c_j . g) the part of O behind entry i,
+//   dL/d alpha_i = T_i (c_i . g) - S_i / (1 - alpha_i),
+// so neither a final T nor a contributor count is stored. S_i cancels for late entries: its
+// absolute error is a few ulps of |O| while it is scaled by T_i <= 1 into the result, i.e. the
+// error is relative to the largest terms of the pixel, not to the entry's own (small) gradient;
+// the measured error (DESIGN.md 3 #3 "Backward") is far below the bar that would call for a
+// back-to-front walk.
+// Reduction: the 64 pixels of a wave are summed on chip before anything leaves the CU. A quad of
+// 4 entries x 9 fields is reduced by a reduce-scatter (2 + 1 exchanges inside each lane quad fold the
+// 4 entries onto lanes (l & 3), two row shifts sum a 16-lane row onto its lanes 0-3, all five as DPP
+// reads inside the VALU, then two shuffles sum the four rows: 2 ds_bpermute per field per quad
+// instead of 24), lanes 0-3 park the sums in the wave's LDS slot, and after the chunk the wave adds them to the
+// gradient records: 16 lanes per record, 4 records per wave instruction (contiguous 36-byte
+// segments of 64-byte records), at most one add per (wave, entry, field), none for an exact 0.
+__global__ void __launch_bounds__(kTileThreads)
+render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __restrict__ grad_color,
+                  float* __restrict__ grec, Workspace ws) {
+    constexpr int kRgbField = kGeomFields;
+    constexpr int kIdField = kGeomFields + 3;  // the entry's Gaussian id (bits)
+    constexpr int kRecFields = kIdField + 1;   // 10
+    __shared__ uint64_t skeys[kSortCap];
+    __shared__ uint32_t s_cnt[kBuckets];
+    __shared__ uint32_t s_red[4];
+    __shared__ __attribute__((aligned(16))) float s_rec[kTileThreads / kWave][kRecFields][kWave];
+    __shared__ __attribute__((aligned(16))) float s_acc[kTileThreads / kWave][kWave][kAccStride];
+
+    const int v = blockIdx.y;
+    int tile = xcd_remap(blockIdx.x, gridDim.x) + v * p.view_rot;
+    tile %= p.T;
+    const int tx = tile % p.tiles_x, ty = tile / p.tiles_x;
+    const int t_idx = v * p.T + tile;
+    uint32_t start = ws.offsets[t_idx];
+    uint32_t end = ws.offsets[t_idx + 1];
+    if (end > (uint32_t)p.capacity) end = (uint32_t)p.capacity;
+    if (start > end) start = end;
+    const int n = (int)(end - start);
+
+    uint64_t* gkeys = ws.keys + start;
+    const bool in_lds = n <= kSortCap;
+    if (in_lds) {
+        const bool try_count = p.count_sort && n > kTileThreads;
+        const bool counted = try_count && counting_sort(gkeys, n, skeys, s_cnt, s_red);
+        if (!counted) {
+            for (int i = threadIdx.x; i < n; i += kTileThreads) skeys[i] = gkeys[i];
+            __syncthreads();
+            bitonic_sort_regs(skeys, n);
+        }
+    } else {
+        bitonic_sort(gkeys, n);  // already sorted in place by the forward: the network leaves it as it is
+    }
+    // no workgroup barrier below this point
+
+    const int wid = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    const int lx = (wid & 1) * 8 + (lane & 7), ly = (wid >> 1) * 8 + (lane >> 3);
+    const int pxi = tx * kTile + lx, pyi = ty * kTile + ly;
+    const float wx0 = (float)(tx * kTile + (wid & 1) * 8), wx1 = wx0 + 7.0f;
+    const float wy0 = (float)(ty * kTile + (wid >> 1) * 8), wy1 = wy0 + 7.0f;
+    const bool inside = pxi < p.W && pyi < p.H;
+    bool done = !inside;
+    const float pfx = (float)pxi, pfy = (float)pyi;
+    float T = 1.0f;
+    float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+    float S = 0.f;  // out . g minus the entries walked so far
+    if (inside) {
+        const size_t hw = (size_t)p.H * p.W;
+        const size_t at = (size_t)v * 3 * hw + (size_t)pyi * p.W + pxi;
+        g0 = grad_color[at];
+        g1 = grad_color[at + hw];
+        g2 = grad_color[at + 2 * hw];
+        S = out_color[at] * g0 + out_color[at + hw] * g1 + out_color[at + 2 * hw] * g2;
+    }
+    const size_t vbase = (size_t)v * p.G;
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    float (*w_rec)[kWave] = s_rec[wid];
+    float (*w_acc)[kAccStride] = s_acc[wid];
+    const bool b0 = (lane & 1) != 0, b1 = (lane & 2) != 0;
+    const int my_e = (b0 ? 2 : 0) + (b1 ? 1 : 0);  // the quad entry whose sums this lane ends up with
+
+    // one entry at this lane's pixel: the forward's blend() decisions, then the nine contributions
+    auto entry = [&](float x, float y, float ca, float cb, float cc, float o, float r, float g, float bl,
+                     float (&val)[kGradFields]) {
+        const float dx = x - pfx, dy = y - pfy;
+        const float power2 = fmaf(dy, fmaf(cc, dy, cb * dx), (ca * dx) * dx);
+        const float ex = __builtin_amdgcn_exp2f(power2);
+        const float oe = o * ex;
+        const float alpha = fminf(0.99f, oe);
+        const float test_T = fmaf(-alpha, T, T);
+        const bool contrib = !done && !(power2 > 0.0f) && !(alpha < 1.0f / 255.0f);
+        const bool stop = contrib && (test_T < 0.0001f);
+        const bool acc = contrib && !stop;
+        const float w = acc ? alpha * T : 0.0f;
+        const float cg = r * g0 + g * g1 + bl * g2;
+        S = fmaf(-w, cg, S);
+        const float dalpha = acc ? T * cg - S * __builtin_amdgcn_rcpf(1.0f - alpha) : 0.0f;
+        const bool pass = acc && !(oe > 0.99f);  // the 0.99 cap passes nothing to conic, mean, opacity
+        const float gp = pass ? dalpha * alpha : 0.0f;  // dL/d power (natural log domain)
+        constexpr float kLn2 = 0.69314718055994531f;
+        const float gl = gp * kLn2;  // the stored conic carries log2(e)
+        val[0] = gl * fmaf(2.0f * ca, dx, cb * dy);
+        val[1] = gl * fmaf(2.0f * cc, dy, cb * dx);
+        val[2] = gp * (-0.5f * dx * dx);
+        val[3] = gp * (-dx * dy);
+        val[4] = gp * (-0.5f * dy * dy);
+        val[5] = pass ? dalpha * ex : 0.0f;
+        val[6] = w * g0;
+        val[7] = w * g1;
+        val[8] = w * g2;
+        T = acc ? test_T : T;
+        done = done || stop;
+    };
+
+    const uint32_t* sids = reinterpret_cast<const uint32_t*>(skeys);
+    auto walk = [&](auto lds_tag) {
+        constexpr bool kInLds = decltype(lds_tag)::value;
+        float4 r_xy = make_float4(0.f, 0.f, 0.f, 0.f), r_co = r_xy, r_rgb = r_xy, r_cull = r_xy;
+        uint32_t r_gid = 0;
+        bool r_valid = false;
+        auto fetch = [&](int k) {
+            r_valid = k < n;
+            if (r_valid) {
+                if constexpr (kInLds)
+                    r_gid = sids[k];
+                else
+                    r_gid = (uint32_t)gkeys[k];
+                const float4* rec = ws.rec + 4 * (vbase + r_gid);
+                r_xy = rec[0];
+                r_co = rec[1];
+                r_rgb = rec[2];
+                r_cull = rec[3];
+            }
+        };
+        fetch(lane);
+        for (int c0 = 0; c0 < n; c0 += kWave) {
+            if (__all(done)) break;
+            const float4 xy = r_xy, co = r_co, rgb = r_rgb, cull = r_cull;
+            const uint32_t gid = r_gid;
+            const bool valid = r_valid;
+            fetch(c0 + kWave + lane);
+            bool hit = valid && !(xy.x + xy.z < wx0 || xy.x - xy.z > wx1 || xy.y + xy.w < wy0 ||
+                                  xy.y - xy.w > wy1);
+            if (hit) hit = ellipse_meets_block(xy.x, xy.y, co, cull, wx0, wx1, wy0, wy1);
+            const uint64_t mask = __ballot(hit);
+            const int m = __popcll(mask);
+            const int m4 = (m + 3) & ~3;
+            if (hit) {
+                const int pos = __popcll(mask & lt_mask);
+                w_rec[0][pos] = xy.x;
+                w_rec[1][pos] = xy.y;
+                w_rec[2][pos] = co.x;
+                w_rec[3][pos] = co.y;
+                w_rec[4][pos] = co.z;
+                w_rec[5][pos] = co.w;
+                w_rec[kRgbField][pos] = rgb.x;
+                w_rec[kRgbField + 1][pos] = rgb.y;
+                w_rec[kRgbField + 2][pos] = rgb.z;
+                w_rec[kIdField][pos] = __uint_as_float(gid);
+            }
+            // pad the last quad with entries that contribute nothing (opacity 0: alpha < 1/255)
+            if (lane < m4 - m) {
+#pragma unroll
+                for (int f = 0; f < kRecFields; ++f) w_rec[f][m + lane] = 0.0f;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int i = 0; i < m4; i += 4) {
+                float4 q[kIdField];
+#pragma unroll
+                for (int f = 0; f < kIdField; ++f) q[f] = *reinterpret_cast<const float4*>(&w_rec[f][i]);
+                float va[4][kGradFields];
+                entry(q[0].x, q[1].x, q[2].x, q[3].x, q[4].x, q[5].x, q[6].x, q[7].x, q[8].x, va[0]);
+                entry(q[0].y, q[1].y, q[2].y, q[3].y, q[4].y, q[5].y, q[6].y, q[7].y, q[8].y, va[1]);
+                entry(q[0].z, q[1].z, q[2].z, q[3].z, q[4].z, q[5].z, q[6].z, q[7].z, q[8].z, va[2]);
+                entry(q[0].w, q[1].w, q[2].w, q[3].w, q[4].w, q[5].w, q[6].w, q[7].w, q[8].w, va[3]);
+                // reduce-scatter: lanes with bit 0 clear keep entries {0, 1}, the others {2, 3};
+                // then bit 1 picks one of the pair; then the 16 lane quads are summed onto lanes 0-3
+                float tot[kGradFields];
+#pragma unroll
+                for (int f = 0; f < kGradFields; ++f) {
+                    const float keep0 = b0 ? va[2][f] : va[0][f], keep1 = b0 ? va[3][f] : va[1][f];
+                    const float send0 = b0 ? va[0][f] : va[2][f], send1 = b0 ? va[1][f] : va[3][f];
+                    const float u0 = keep0 + dpp_f32<kDppQuadXor1>(send0);
+                    const float u1 = keep1 + dpp_f32<kDppQuadXor1>(send1);
+                    float t = (b1 ? u1 : u0) + dpp_f32<kDppQuadXor2>(b1 ? u0 : u1);
+                    t += dpp_f32<kDppRowShl4>(t);  // lanes 0-11 of a 16-lane row: + lane l + 4
+                    t += dpp_f32<kDppRowShl8>(t);  // lanes 0-3 of a row: the row's four quads
+                    t += __shfl_xor(t, 16);
+                    t += __shfl_xor(t, 32);        // lanes 0-3: all four rows
+                    tot[f] = t;
+                }
+                if (lane < 4) {
+                    float* a = w_acc[i + my_e];
+                    *reinterpret_cast<float4*>(a) = make_float4(tot[0], tot[1], tot[2], tot[3]);
+                    *reinterpret_cast<float4*>(a + 4) = make_float4(tot[4], tot[5], tot[6], tot[7]);
+                    a[8] = tot[8];
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // the chunk's sums to the gradient records: 16 lanes per record, 4 records per instruction
+            {
+                const int f = lane & 15;
+                for (int j = 0; j < m; j += 4) {
+                    const int e = j + (lane >> 4);
+                    if (e < m && f < kGradFields) {
+                        const float val = w_acc[e][f];
+                        const uint32_t id = __float_as_uint(w_rec[kIdField][e]);
+                        if (val != 0.0f) atomicAdd(grec + (vbase + id) * kGradRecFloats + f, val);
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();  // reads of this chunk's LDS slots precede the next writes
+        }
+    };
+    if (in_lds)
+        walk(std::true_type{});
+    else
+        walk(std::false_type{});
+}
+
+// --- B2: gradient records -> gradients of the Gaussians ----------------------------------------
+// One thread per Gaussian for all views of its scene (blockIdx.y = scene), the mirror of
+// preprocess_kernel: the forward geometry of each view is recomputed with the forward's
+// expressions, the view's gradient record is chained through them, and the contributions of the
+// views are summed in registers (SH: in the thread's LDS slot) and written once. No atomics. Views
+// with radii == 0 are skipped. The SH block of a wave's 64 Gaussians is staged to LDS and its
+// gradient written back by coalesced loops, as the forward reads it. 128 threads per workgroup:
+// two [threads][75] float LDS arrays (coefficients and their gradients), 76,800 bytes.
+constexpr int kPreBwdThreads = 128;
+
+__global__ void __launch_bounds__(kPreBwdThreads)
+preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __restrict__ cov,
+                      const float* __restrict__ shs, const float* __restrict__ opacity,
+                      const float* __restrict__ viewmat, const float* __restrict__ projmat,
+                      const float* __restrict__ campos, const float* __restrict__ tanfov,
+                      const float* __restrict__ scene_scale, const int32_t* __restrict__ radii,
+                      const float* __restrict__ grec, float* __restrict__ grad_means,
+                      float* __restrict__ grad_cov, float* __restrict__ grad_shs,
+                      float* __restrict__ grad_opacity) {
+    __shared__ float s_sh[kPreBwdThreads * kMaxShFloats];
+    __shared__ float s_dsh[kPreBwdThreads * kMaxShFloats];
+    const int scene = blockIdx.y;
+    const int lane = threadIdx.x % kWave, wid = threadIdx.x / kWave;
+    const int g = blockIdx.x * kPreBwdThreads + threadIdx.x;
+    const int nf = 3 * p.M;
+    const size_t sg = (size_t)scene * p.G + g;
+    const float* my_sh = s_sh + (size_t)threadIdx.x * nf;
+    float* my_dsh = s_dsh + (size_t)threadIdx.x * nf;
+    const int gw0 = blockIdx.x * kPreBwdThreads + wid * kWave;
+    const int sh_total = max(0, min(kWave, p.G - gw0)) * nf;
+    const size_t sh_off = (size_t)nf * ((size_t)scene * p.G + gw0);
+    {
+        const float* sh_src = shs + sh_off;
+        float* sh_dst = s_sh + (size_t)wid * kWave * nf;
+        float* dsh_dst = s_dsh + (size_t)wid * kWave * nf;
+        for (int i = lane; i < sh_total; i += kWave) {
+            sh_dst[i] = sh_src[i];
+            dsh_dst[i] = 0.0f;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    if (g < p.G) {
+        const float m0 = means[3 * sg], m1 = means[3 * sg + 1], m2 = means[3 * sg + 2];
+        const float* C = cov + 9 * sg;
+        const float k00 = C[0], k01 = C[1], k02 = C[2], k11 = C[4], k12 = C[5], k22 = C[8];
+        float gm0 = 0.f, gm1 = 0.f, gm2 = 0.f, go = 0.f;
+        float gk00 = 0.f, gk01 = 0.f, gk02 = 0.f, gk11 = 0.f, gk12 = 0.f, gk22 = 0.f;
+        const int nb = (p.deg + 1) * (p.deg + 1);  // SH coefficients evaluated per channel
+        for (int vv = 0; vv < p.vps; ++vv) {
+            const int v = scene * p.vps + vv;
+            const size_t vg = (size_t)v * p.G + g;
+            if (radii[vg] == 0) continue;
+            const float4* gr = reinterpret_cast<const float4*>(grec + kGradRecFloats * vg);
+            const float4 ga = gr[0], gb = gr[1];
+            const float g_r2 = gr[2].x;
+            const float g_px = ga.x, g_py = ga.y, g_qa = ga.z, g_qb = ga.w, g_qc = gb.x, g_o = gb.y;
+            const float g_rgb[3] = {gb.z, gb.w, g_r2};
+            go += g_o;
+
+            const float* vm = viewmat + 16 * v;
+            const float* pm = projmat + 16 * v;
+            const float s = scene_scale[2 * v], s2 = scene_scale[2 * v + 1];
+            // forward geometry, the expressions of preprocess_kernel
+            const float mx = m0 * s, my = m1 * s, mz = m2 * s;
+            const float vx = vm[0] * mx + vm[4] * my + vm[8] * mz + vm[12];
+            const float vy = vm[1] * mx + vm[5] * my + vm[9] * mz + vm[13];
+            const float vz = vm[2] * mx + vm[6] * my + vm[10] * mz + vm[14];
+            const float hx = pm[0] * mx + pm[4] * my + pm[8] * mz + pm[12];
+            const float hy = pm[1] * mx + pm[5] * my + pm[9] * mz + pm[13];
+            const float hw = pm[3] * mx + pm[7] * my + pm[11] * mz + pm[15];
+            const float pw = 1.0f / (hw + 0.0000001f);
+            const float c00 = k00 * s2, c01 = k01 * s2, c02 = k02 * s2;
+            const float c11 = k11 * s2, c12 = k12 * s2, c22 = k22 * s2;
+            const float tfx = tanfov[2 * v], tfy = tanfov[2 * v + 1];
+            const float fx = (float)p.W / (2.0f * tfx), fy = (float)p.H / (2.0f * tfy);
+            const float limx = 1.3f * tfx, limy = 1.3f * tfy;
+            const float tz = vz;
+            const float rxu = vx / tz, ryu = vy / tz;
+            const float rx = fminf(limx, fmaxf(-limx, rxu)), ry = fminf(limy, fmaxf(-limy, ryu));
+            const bool in_x = rxu >= -limx && rxu <= limx, in_y = ryu >= -limy && ryu <= limy;
+            const float tx = rx * tz, ty = ry * tz;
+            const float j00 = fx / tz, j02 = -(fx * tx) / (tz * tz);
+            const float j11 = fy / tz, j12 = -(fy * ty) / (tz * tz);
+            const float n00 = j00 * vm[0] + j02 * vm[2];
+            const float n01 = j00 * vm[4] + j02 * vm[6];
+            const float n02 = j00 * vm[8] + j02 * vm[10];
+            const float n10 = j11 * vm[1] + j12 * vm[2];
+            const float n11 = j11 * vm[5] + j12 * vm[6];
+            const float n12 = j11 * vm[9] + j12 * vm[10];
+            const float u00 = n00 * c00 + n01 * c01 + n02 * c02;
+            const float u01 = n00 * c01 + n01 * c11 + n02 * c12;
+            const float u02 = n00 * c02 + n01 * c12 + n02 * c22;
+            const float u10 = n10 * c00 + n11 * c01 + n12 * c02;
+            const float u11 = n10 * c01 + n11 * c11 + n12 * c12;
+            const float u12 = n10 * c02 + n11 * c12 + n12 * c22;
+            const float a = u00 * n00 + u01 * n01 + u02 * n02 + 0.3f;
+            const float b = u00 * n10 + u01 * n11 + u02 * n12;
+            const float c = u10 * n10 + u11 * n11 + u12 * n12 + 0.3f;
+            const float det = a * c - b * b;
+            const float det_inv = 1.0f / det;
+            const float qa = c * det_inv, qb = -b * det_inv, qc = a * det_inv;
+
+            // conic Q = Sigma2^-1: dL/dSigma2 = -Q G Q with G = [[g_qa, g_qb / 2], [g_qb / 2, g_qc]]
+            const float hb = 0.5f * g_qb;
+            const float t00 = qa * g_qa + qb * hb, t01 = qa * hb + qb * g_qc;
+            const float t10 = qb * g_qa + qc * hb, t11 = qb * hb + qc * g_qc;
+            const float dA = -(t00 * qa + t01 * qb);
+            const float dB = -2.0f * (t00 * qb + t01 * qc);  // b sits in both off-diagonal entries
+            const float dC = -(t10 * qb + t11 * qc);
+            // a = n0' C n0 + 0.3, b = n0' C n1, c = n1' C n1 + 0.3 (C = s^2 K, the upper triangle of K read)
+            gk00 += s2 * (dA * n00 * n00 + dB * n00 * n10 + dC * n10 * n10);
+            gk01 += s2 * (2.0f * dA * n00 * n01 + dB * (n00 * n11 + n01 * n10) + 2.0f * dC * n10 * n11);
+            gk02 += s2 * (2.0f * dA * n00 * n02 + dB * (n00 * n12 + n02 * n10) + 2.0f * dC * n10 * n12);
+            gk11 += s2 * (dA * n01 * n01 + dB * n01 * n11 + dC * n11 * n11);
+            gk12 += s2 * (2.0f * dA * n01 * n02 + dB * (n01 * n12 + n02 * n11) + 2.0f * dC * n11 * n12);
+            gk22 += s2 * (dA * n02 * n02 + dB * n02 * n12 + dC * n12 * n12);
+            const float dn00 = 2.0f * dA * u00 + dB * u10, dn01 = 2.0f * dA * u01 + dB * u11,
+                        dn02 = 2.0f * dA * u02 + dB * u12;
+            const float dn10 = 2.0f * dC * u10 + dB * u00, dn11 = 2.0f * dC * u11 + dB * u01,
+                        dn12 = 2.0f * dC * u12 + dB * u02;
+            const float dj00 = dn00 * vm[0] + dn01 * vm[4] + dn02 * vm[8];
+            const float dj02 = dn00 * vm[2] + dn01 * vm[6] + dn02 * vm[10];
+            const float dj11 = dn10 * vm[1] + dn11 * vm[5] + dn12 * vm[9];
+            const float dj12 = dn10 * vm[2] + dn11 * vm[6] + dn12 * vm[10];
+            // j00 = fx / tz, j02 = -fx r / tz with r = clamp(vx / tz): inside the clamp r follows vx and
+            // tz, at the clamp it is a constant
+            const float itz = 1.0f / tz, itz2 = itz * itz;
+            const float dvx = in_x ? -dj02 * fx * itz2 : 0.0f;
+            const float dvy = in_y ? -dj12 * fy * itz2 : 0.0f;
+            const float dvz = -(dj00 * fx + dj11 * fy) * itz2 +
+                              dj02 * (fx * rx * itz2 + (in_x ? fx * vx * itz2 * itz : 0.0f)) +
+                              dj12 * (fy * ry * itz2 + (in_y ? fy * vy * itz2 * itz : 0.0f));
+            float dmx = vm[0] * dvx + vm[1] * dvy + vm[2] * dvz;
+            float dmy = vm[4] * dvx + vm[5] * dvy + vm[6] * dvz;
+            float dmz = vm[8] * dvx + vm[9] * dvy + vm[10] * dvz;
+            // pixel mean: px = ((hx pw + 1) W - 1) / 2, pw = 1 / (hw + 1e-7)
+            const float dndx = g_px * 0.5f * (float)p.W, dndy = g_py * 0.5f * (float)p.H;
+            const float dhx = dndx * pw, dhy = dndy * pw;
+            const float dhw = -(dndx * hx + dndy * hy) * pw * pw;
+            dmx += pm[0] * dhx + pm[1] * dhy + pm[3] * dhw;
+            dmy += pm[4] * dhx + pm[5] * dhy + pm[7] * dhw;
+            dmz += pm[8] * dhx + pm[9] * dhy + pm[11] * dhw;
+
+            // colour: rgb_c = max(sum_k B_k(n) sh[c][k] + 0.5, 0), n = d / |d|, d = mean s - campos
+            const float* cp = campos + 3 * v;
+            const float ddx = mx - cp[0], ddy = my - cp[1], ddz = mz - cp[2];
+            float rgb[3];
+            sh_to_rgb(my_sh, p.M, p.deg, ddx, ddy, ddz, rgb);
+            float tc[3];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) tc[ch] = rgb[ch] > 0.0f ? g_rgb[ch] : 0.0f;  // the clamp at 0
+            const float len = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+            const float x = ddx / len, y = ddy / len, z = ddz / len;
+            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            float dnx = 0.f, dny = 0.f, dnz = 0.f;
+            // one basis function: value B and its gradient (bx, by, bz) in the unit direction
+            auto term = [&](int k, float B, float bx, float by, float bz) {
+                const float ak = tc[0] * my_sh[k] + tc[1] * my_sh[p.M + k] + tc[2] * my_sh[2 * p.M + k];
+                dnx += bx * ak;
+                dny += by * ak;
+                dnz += bz * ak;
+                my_dsh[k] += tc[0] * B;
+                my_dsh[p.M + k] += tc[1] * B;
+                my_dsh[2 * p.M + k] += tc[2] * B;
+            };
+            term(0, kSH_C0, 0.f, 0.f, 0.f);
+            if (nb > 1) {
+                term(1, -kSH_C1 * y, 0.f, -kSH_C1, 0.f);
+                term(2, kSH_C1 * z, 0.f, 0.f, kSH_C1);
+                term(3, -kSH_C1 * x, -kSH_C1, 0.f, 0.f);
+            }
+            if (nb > 4) {
+                term(4, kSH_C2[0] * xy, kSH_C2[0] * y, kSH_C2[0] * x, 0.f);
+                term(5, kSH_C2[1] * yz, 0.f, kSH_C2[1] * z, kSH_C2[1] * y);
+                term(6, kSH_C2[2] * (2.0f * zz - xx - yy), kSH_C2[2] * -2.0f * x, kSH_C2[2] * -2.0f * y,
+                     kSH_C2[2] * 4.0f * z);
+                term(7, kSH_C2[3] * xz, kSH_C2[3] * z, 0.f, kSH_C2[3] * x);
+                term(8, kSH_C2[4] * (xx - yy), kSH_C2[4] * 2.0f * x, kSH_C2[4] * -2.0f * y, 0.f);
+            }
+            if (nb > 9) {
+                term(9, kSH_C3[0] * y * (3.0f * xx - yy), kSH_C3[0] * 6.0f * xy, kSH_C3[0] * (3.0f * xx - 3.0f * yy), 0.f);
+                term(10, kSH_C3[1] * xy * z, kSH_C3[1] * yz, kSH_C3[1] * xz, kSH_C3[1] * xy);
+                term(11, kSH_C3[2] * y * (4.0f * zz - xx - yy), kSH_C3[2] * -2.0f * xy,
+                     kSH_C3[2] * (4.0f * zz - xx - 3.0f * yy), kSH_C3[2] * 8.0f * yz);
+                term(12, kSH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy), kSH_C3[3] * -6.0f * xz,
+                     kSH_C3[3] * -6.0f * yz, kSH_C3[3] * (6.0f * zz - 3.0f * xx - 3.0f * yy));
+                term(13, kSH_C3[4] * x * (4.0f * zz - xx - yy), kSH_C3[4] * (4.0f * zz - 3.0f * xx - yy),
+                     kSH_C3[4] * -2.0f * xy, kSH_C3[4] * 8.0f * xz);
+                term(14, kSH_C3[5] * z * (xx - yy), kSH_C3[5] * 2.0f * xz, kSH_C3[5] * -2.0f * yz,
+                     kSH_C3[5] * (xx - yy));
+                term(15, kSH_C3[6] * x * (xx - 3.0f * yy), kSH_C3[6] * (3.0f * xx - 3.0f * yy), kSH_C3[6] * -6.0f * xy,
+                     0.f);
+            }
+            if (nb > 16) {
+                const float s7 = 7.0f * zz - 1.0f, t7 = 7.0f * zz - 3.0f;
+                term(16, kSH_C4[0] * xy * (xx - yy), kSH_C4[0] * y * (3.0f * xx - yy), kSH_C4[0] * x * (xx - 3.0f * yy),
+                     0.f);
+                term(17, kSH_C4[1] * yz * (3.0f * xx - yy), kSH_C4[1] * 6.0f * xy * z,
+                     kSH_C4[1] * z * (3.0f * xx - 3.0f * yy), kSH_C4[1] * y * (3.0f * xx - yy));
+                term(18, kSH_C4[2] * xy * s7, kSH_C4[2] * y * s7, kSH_C4[2] * x * s7, kSH_C4[2] * 14.0f * xy * z);
+                term(19, kSH_C4[3] * yz * t7, 0.f, kSH_C4[3] * z * t7, kSH_C4[3] * y * (21.0f * zz - 3.0f));
+                term(20, kSH_C4[4] * (zz * (35.0f * zz - 30.0f) + 3.0f), 0.f, 0.f,
+                     kSH_C4[4] * z * (140.0f * zz - 60.0f));
+                term(21, kSH_C4[5] * xz * t7, kSH_C4[5] * z * t7, 0.f, kSH_C4[5] * x * (21.0f * zz - 3.0f));
+                term(22, kSH_C4[6] * (xx - yy) * s7, kSH_C4[6] * 2.0f * x * s7, kSH_C4[6] * -2.0f * y * s7,
+                     kSH_C4[6] * 14.0f * z * (xx - yy));
+                term(23, kSH_C4[7] * xz * (xx - 3.0f * yy), kSH_C4[7] * z * (3.0f * xx - 3.0f * yy),
+                     kSH_C4[7] * -6.0f * xy * z, kSH_C4[7] * x * (xx - 3.0f * yy));
+                term(24, kSH_C4[8] * (xx * (xx - 3.0f * yy) - yy * (3.0f * xx - yy)),
+                     kSH_C4[8] * x * (4.0f * xx - 12.0f * yy), kSH_C4[8] * y * (4.0f * yy - 12.0f * xx), 0.f);
+            }
+            // through n = d / |d|: dL/dd = (dn - n (n . dn)) / |d|
+            const float ndot = x * dnx + y * dny + z * dnz;
+            dmx += (dnx - x * ndot) / len;
+            dmy += (dny - y * ndot) / len;
+            dmz += (dnz - z * ndot) / len;
+            // scale-invariant rendering: mean s (cov s^2 is in gk above)
+            gm0 += s * dmx;
+            gm1 += s * dmy;
+            gm2 += s * dmz;
+        }
+        if (grad_means) {
+            grad_means[3 * sg] = gm0;
+            grad_means[3 * sg + 1] = gm1;
+            grad_means[3 * sg + 2] = gm2;
+        }
+        if (grad_cov) {
+            float* o = grad_cov + 9 * sg;
+            o[0] = gk00;
+            o[1] = gk01;
+            o[2] = gk02;
+            o[3] = 0.0f;
+            o[4] = gk11;
+            o[5] = gk12;
+            o[6] = 0.0f;
+            o[7] = 0.0f;
+            o[8] = gk22;
+        }
+        if (grad_opacity) grad_opacity[sg] = go;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (grad_shs) {
+        float* dst = grad_shs + sh_off;
+        const float* src = s_dsh + (size_t)wid * kWave * nf;
+        for (int i = lane; i < sh_total; i += kWave) dst[i] = src[i];
+    }
+}
+
 }  // namespace raster
 }  // namespace tsplat
 
@@ -1041,6 +1552,44 @@ static int raster_launch(Params p, const float* means, const float* cov, const f
     return TSPLAT_OK;
 }
 
+// Descriptor checks and launch parameters of every rasterizer entry point, forward and backward
+// (sh_vec4 is the forward's own, set by raster_run). False: the descriptor is rejected.
+static bool raster_params(const tsplat_raster_desc* d, int depth_mode, Params* out) {
+    if (d->num_gaussians <= 0 || d->num_views <= 0 || d->views_per_scene <= 0 ||
+        d->num_views % d->views_per_scene != 0 || d->height <= 0 || d->width <= 0 ||
+        d->sh_coeffs <= 0 || d->sh_degree < 0 || d->sh_degree > 4 ||
+        (d->sh_degree + 1) * (d->sh_degree + 1) > d->sh_coeffs || d->capacity <= 0)
+        return false;
+    Params p;
+    p.G = d->num_gaussians;
+    p.V = d->num_views;
+    p.vps = d->views_per_scene;
+    p.H = d->height;
+    p.W = d->width;
+    p.M = d->sh_coeffs;
+    p.deg = d->sh_degree;
+    p.tiles_x = ceil_div(p.W, kTile);
+    p.tiles_y = ceil_div(p.H, kTile);
+    p.T = p.tiles_x * p.tiles_y;
+    p.capacity = d->capacity;
+    p.depth_mode = depth_mode;
+    p.sh_vec4 = 0;
+    {
+        const char* e = getenv("TSPLAT_RASTER_DIAG");
+        p.diag = e ? atoi(e) : 0;
+        const char* s = getenv("TSPLAT_RASTER_SORT");
+        p.count_sort = !(s && !strcmp(s, "bitonic"));
+        // rotation per view: about T / 3 tiles, rounded to whole rows
+        p.view_rot = (p.tiles_y + 1) / 3 * p.tiles_x;
+    }
+    if (3 * p.M > kMaxShFloats || p.vps > 32) return false;
+    // scatter keeps 3 T uint32 of per-tile counters in LDS: up to gfx950's 160 KB per workgroup
+    // (13,653 16x16 tiles, about 1860 x 1860 px)
+    if ((size_t)p.T * 3 * sizeof(uint32_t) > kMaxLdsBytes) return false;
+    *out = p;
+    return true;
+}
+
 // Argument checks and launch parameters shared by tsplat_raster_fwd (depth_mode = -1, no extra
 // outputs) and tsplat_raster_depth_fwd. Every check comes before the first launch: a rejected call
 // queues nothing.
@@ -1055,38 +1604,11 @@ static int raster_run(const tsplat_raster_desc* d, const float* means, const flo
         !bg || !scene_scale || !out_radii || !workspace || !status)
         return TSPLAT_EINVAL;
     if (!out_color && !out_depth && !out_alpha) return TSPLAT_EINVAL;
-    if (d->num_gaussians <= 0 || d->num_views <= 0 || d->views_per_scene <= 0 ||
-        d->num_views % d->views_per_scene != 0 || d->height <= 0 || d->width <= 0 ||
-        d->sh_coeffs <= 0 || d->sh_degree < 0 || d->sh_degree > 4 ||
-        (d->sh_degree + 1) * (d->sh_degree + 1) > d->sh_coeffs || d->capacity <= 0)
-        return TSPLAT_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     Params p;
-    p.G = d->num_gaussians;
-    p.V = d->num_views;
-    p.vps = d->views_per_scene;
-    p.H = d->height;
-    p.W = d->width;
-    p.M = d->sh_coeffs;
-    p.deg = d->sh_degree;
-    p.tiles_x = ceil_div(p.W, kTile);
-    p.tiles_y = ceil_div(p.H, kTile);
-    p.T = p.tiles_x * p.tiles_y;
-    p.capacity = d->capacity;
-    p.depth_mode = depth_mode;
-    {
-        const char* e = getenv("TSPLAT_RASTER_DIAG");
-        p.diag = e ? atoi(e) : 0;
-        const char* s = getenv("TSPLAT_RASTER_SORT");
-        p.count_sort = !(s && !strcmp(s, "bitonic"));
-        // rotation per view: about T / 3 tiles, rounded to whole rows
-        p.view_rot = (p.tiles_y + 1) / 3 * p.tiles_x;
-    }
-    if (3 * p.M > kMaxShFloats || p.vps > 32) return TSPLAT_EINVAL;
-    // scatter keeps 3 T uint32 of per-tile counters in LDS: up to gfx950's 160 KB per workgroup
-    // (13,653 16x16 tiles, about 1860 x 1860 px); above 64 KB the kernel's dynamic-LDS limit is raised
+    if (!raster_params(d, depth_mode, &p)) return TSPLAT_EINVAL;
+    // scatter keeps 3 T uint32 of per-tile counters in LDS: above 64 KB the kernel's dynamic-LDS limit is raised
     const size_t scatter_lds = (size_t)p.T * 3 * sizeof(uint32_t);
-    if (scatter_lds > kMaxLdsBytes) return TSPLAT_EINVAL;
     if (scatter_lds > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds) != hipSuccess)
@@ -1130,6 +1652,54 @@ extern "C" int tsplat_raster_depth_fwd(const tsplat_raster_desc* d, const float*
     return raster_run(d, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale,
                       near, far, out_depth ? depth_mode : -1, true, out_color, out_depth, out_alpha,
                       out_radii, workspace, status, stream_);
+}
+
+extern "C" size_t tsplat_raster_bwd_workspace_bytes(int32_t G, int32_t V) {
+    if (G <= 0 || V <= 0) return 0;
+    return align_up((size_t)G * V * kGradRecFloats * sizeof(float), 256);
+}
+
+// Backward of tsplat_raster_fwd: zero fill of the gradient records, render_bwd_kernel,
+// preprocess_bwd_kernel. Every check comes before the first launch.
+extern "C" int tsplat_raster_bwd(const tsplat_raster_desc* d, const float* means, const float* cov,
+                                 const float* shs, const float* opacity, const float* viewmat,
+                                 const float* projmat, const float* campos, const float* tanfov,
+                                 const float* bg, const float* scene_scale, const float* out_color,
+                                 const float* grad_color, const int32_t* radii, void* fwd_workspace,
+                                 void* bwd_workspace, float* grad_means, float* grad_cov,
+                                 float* grad_shs, float* grad_opacity, void* stream_) {
+    if (!d || !means || !cov || !shs || !opacity || !viewmat || !projmat || !campos || !tanfov ||
+        !bg || !scene_scale || !out_color || !grad_color || !radii || !fwd_workspace || !bwd_workspace)
+        return TSPLAT_EINVAL;
+    if (!grad_means && !grad_cov && !grad_shs && !grad_opacity) return TSPLAT_EINVAL;
+    Params p;
+    if (!raster_params(d, -1, &p)) return TSPLAT_EINVAL;
+    p.diag = 0;  // the forward's timing diagnostics have no backward
+    hipStream_t stream = (hipStream_t)stream_;
+    Workspace ws = carve(fwd_workspace, p.G, p.V, p.T, p.capacity, nullptr);
+    float* grec = (float*)bwd_workspace;
+    TSPLAT_PROF_BEGIN(prof::kRasterBwdAll, stream);
+    {
+        const size_t n4 = (size_t)p.G * p.V * kGradRecFloats / 4;
+        const int blocks = (int)std::min<size_t>(ceil_div(n4, (size_t)256), 4096);
+        hipLaunchKernelGGL(zero_kernel, dim3(blocks), dim3(256), 0, stream, (uint4*)grec, n4);
+        TSPLAT_CHECK_LAUNCH();
+    }
+    TSPLAT_PROF_BEGIN(prof::kRasterBwdRender, stream);
+    hipLaunchKernelGGL(render_bwd_kernel, dim3(p.T, p.V), dim3(kTileThreads), 0, stream, p, out_color,
+                       grad_color, grec, ws);
+    TSPLAT_PROF_END(prof::kRasterBwdRender, stream);
+    TSPLAT_CHECK_LAUNCH();
+    const int scenes = p.V / p.vps;
+    TSPLAT_PROF_BEGIN(prof::kRasterBwdPreprocess, stream);
+    hipLaunchKernelGGL(preprocess_bwd_kernel, dim3(ceil_div(p.G, kPreBwdThreads), scenes),
+                       dim3(kPreBwdThreads), 0, stream, p, means, cov, shs, opacity, viewmat, projmat,
+                       campos, tanfov, scene_scale, radii, (const float*)grec, grad_means, grad_cov,
+                       grad_shs, grad_opacity);
+    TSPLAT_PROF_END(prof::kRasterBwdPreprocess, stream);
+    TSPLAT_PROF_END(prof::kRasterBwdAll, stream);
+    TSPLAT_CHECK_LAUNCH();
+    return TSPLAT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -20,7 +20,8 @@ from torch import Tensor
 from ..types import Gaussians
 from .decoder import Decoder, DecoderOutput, DepthRenderingMode
 from .hip_splatting import (RasterCameras, RasterOutput, check_status, merge_view_groups, plan_view_groups,
-                            prepare_cameras, rasterize, rasterize_with_depth, select_view_rows)
+                            prepare_cameras, rasterize, rasterize_differentiable, rasterize_with_depth,
+                            select_view_rows)
 
 
 @dataclass
@@ -32,6 +33,10 @@ class DecoderSplattingHIPCfg:
     # views per scene of one rasterizer call when a scene has more than 32 (1..32): at the production
     # scene 16 keeps the worst-case instance keys at 4 GiB, half the MAX_CAPACITY cap
     views_per_call: int = 16
+    # True: while grad is enabled and a Gaussian tensor requires grad, the colour comes from
+    # rasterize_differentiable (tsplat_raster_bwd as its backward) and carries a grad_fn. No depth
+    # gradients: depth_mode then raises NotImplementedError. False: the forward-only calls.
+    differentiable: bool = False
 
 
 def _depth_fused() -> bool:
@@ -79,6 +84,13 @@ class DecoderSplattingHIP(Decoder[DecoderSplattingHIPCfg]):
         depth_mode: DepthRenderingMode | None = None,
     ) -> DecoderOutput:
         b, v, _, _ = extrinsics.shape
+        if self._wants_grad(gaussians):
+            if depth_mode is not None:
+                raise NotImplementedError(
+                    "DecoderSplattingHIP(differentiable=True): gradients of the depth render are not built; "
+                    "call with depth_mode=None, or under torch.no_grad() for a depth without gradients")
+            rgb = self._render_differentiable(gaussians, extrinsics, intrinsics, near, far, image_shape)
+            return DecoderOutput(rearrange(rgb, "(b v) c h w -> b v c h w", b=b, v=v), None)
         fused = depth_mode is not None and _depth_fused()
         out = self._render(gaussians, extrinsics, intrinsics, near, far, image_shape,
                            depth_mode if fused else None, color=True)
@@ -89,6 +101,39 @@ class DecoderSplattingHIP(Decoder[DecoderSplattingHIPCfg]):
         elif depth_mode is not None:
             depth = self.render_depth(gaussians, extrinsics, intrinsics, near, far, image_shape, depth_mode)
         return DecoderOutput(color, depth)
+
+    def _wants_grad(self, gaussians: Gaussians) -> bool:
+        """cfg.differentiable, grad enabled, and a Gaussian tensor that requires grad."""
+        return (self.cfg.differentiable and torch.is_grad_enabled() and any(
+            t.requires_grad for t in (gaussians.means, gaussians.covariances, gaussians.harmonics,
+                                      gaussians.opacities)))
+
+    def _render_differentiable(self, gaussians, extrinsics, intrinsics, near, far, image_shape) -> Tensor:
+        """The colour of _render() through rasterize_differentiable -> [(b v), 3, H, W] with a grad_fn.
+        More than 32 views per scene go group by group, each call on a workspace of its own; autograd
+        sums the groups' gradients."""
+        b, v, _, _ = extrinsics.shape
+        cams = prepare_cameras(
+            rearrange(extrinsics, "b v i j -> (b v) i j"),
+            rearrange(intrinsics, "b v i j -> (b v) i j"),
+            rearrange(near, "b v -> (b v)"),
+            rearrange(far, "b v -> (b v)"),
+            repeat(self.background_color, "c -> (b v) c", b=b, v=v),
+        )
+        groups = plan_view_groups(b, v, self.cfg.views_per_call)
+        single = len(groups) == 1
+        parts = []
+        for views in groups:
+            c = cams if single else RasterCameras(*(select_view_rows(getattr(cams, f), b, v, views)
+                                                    for f in cams.__dataclass_fields__))
+            rgb, _ = rasterize_differentiable(
+                gaussians.means, gaussians.covariances, gaussians.harmonics, gaussians.opacities, c, image_shape,
+                views_per_scene=views.stop - views.start, sh_degree=self.cfg.sh_eval_degree,
+                check=self.cfg.check_overflow and single, debug=self.cfg.debug)
+            parts.append(rgb)
+        if not single and self.cfg.check_overflow:
+            check_status(gaussians.means.device)
+        return merge_view_groups(parts, b)
 
     def _render(self, gaussians, extrinsics, intrinsics, near, far, image_shape, depth_mode, color):
         """One rasterizer call over the un-repeated Gaussians for all (b v) views: colour and / or

@@ -158,10 +158,13 @@ class RasterOutput:
 
 
 def _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
-               capacity, check, debug, extra=None) -> RasterOutput:
+               capacity, check, debug, extra=None, keep=None) -> RasterOutput:
     """The call behind rasterize() (extra None: tsplat_raster_fwd) and rasterize_with_depth()
     (extra = (near, far, mode id, color, depth, alpha): tsplat_raster_depth_fwd), with the same
-    capacity, overflow and debug rules."""
+    capacity, overflow and debug rules. keep: a list that receives what a backward needs (the
+    descriptor, the fp32 contiguous inputs and camera arrays the call read, its workspace); the call
+    then runs on a workspace tensor of its own instead of the device's shared one, which the next
+    call overwrites."""
     lib = _lib.load()
     s, g, _ = means.shape
     m = harmonics.shape[-1]
@@ -179,7 +182,11 @@ def _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, v
     if capacity is None:
         capacity = default_capacity(g, v, h, w)
     nbytes = int(lib.tsplat_raster_workspace_bytes(g, v, h, w, capacity))
-    ws, status = _STATE.get(dev, nbytes)
+    if keep is not None:
+        _lib.ptr(means)  # raises for host tensors before anything is allocated
+        ws, status = torch.empty(nbytes, dtype=torch.uint8, device=dev), _STATE.get(dev, 0)[1]
+    else:
+        ws, status = _STATE.get(dev, nbytes)
     want_color, want_depth, want_alpha = (True, False, False) if extra is None else extra[3:]
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     color = new(v, 3, h, w) if want_color else None
@@ -218,6 +225,8 @@ def _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, v
     _STATE.last[(dev.type, dev.index)] = (ws, int(lib.tsplat_raster_num_rendered_offset(g, v, h, w)))
     if check:
         check_status(dev)
+    if keep is not None:
+        keep[:] = [desc, (means, covariances, harmonics, opacities), cams, ws]
     return RasterOutput(color, radii, depth, alpha)
 
 
@@ -289,6 +298,72 @@ def rasterize_with_depth(
     extra = (near, far, DEPTH_MODES[depth_mode] if want_depth else 0, bool(color), want_depth, bool(alpha))
     return _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
                       capacity, check, debug, extra)
+
+
+class _RasterizeFn(torch.autograd.Function):
+    """rasterize() with a backward: tsplat_raster_fwd on a private workspace, tsplat_raster_bwd on
+    what that call left in it."""
+
+    @staticmethod
+    def forward(ctx, means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
+                capacity, check, debug):
+        keep = []
+        out = _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
+                         capacity, check, debug, keep=keep)
+        desc, gauss, cams, ws = keep
+        ctx.desc, ctx.workspace = desc, ws
+        ctx.dtypes = tuple(t.dtype for t in (means, covariances, harmonics, opacities))
+        ctx.save_for_backward(*gauss, *cams, out.color, out.radii)
+        ctx.mark_non_differentiable(out.radii)
+        return out.color, out.radii
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_color, _grad_radii):
+        lib = _lib.load()
+        t = ctx.saved_tensors
+        gauss, cams, color, radii = t[:4], t[4:10], t[10], t[11]
+        dev = color.device
+        desc = ctx.desc
+        grad_color = grad_color.float().contiguous()
+        grads = [torch.empty_like(x) if need else None for x, need in zip(gauss, ctx.needs_input_grad[:4])]
+        if all(g is None for g in grads):
+            return (None,) * 11
+        bws = torch.empty(int(lib.tsplat_raster_bwd_workspace_bytes(desc.num_gaussians, desc.num_views)),
+                          dtype=torch.uint8, device=dev)
+        rc = lib.tsplat_raster_bwd(desc, *(_lib.ptr(x) for x in gauss), *(_lib.ptr(x) for x in cams),
+                                   _lib.ptr(color), _lib.ptr(grad_color), _lib.ptr(radii), _lib.ptr(ctx.workspace),
+                                   _lib.ptr(bws), *(_lib.ptr(g) for g in grads), _lib.stream_ptr(dev))
+        _lib.check(rc, "tsplat_raster_bwd")
+        grads = [None if g is None else g.to(dt) for g, dt in zip(grads, ctx.dtypes)]
+        return (*grads, None, None, None, None, None, None, None)
+
+
+def rasterize_differentiable(
+    means: Tensor,
+    covariances: Tensor,
+    harmonics: Tensor,
+    opacities: Tensor,
+    cameras: RasterCameras,
+    image_shape: tuple[int, int],
+    views_per_scene: int,
+    sh_degree: int | None = None,
+    capacity: int | None = None,
+    check: bool = True,
+    debug: bool = False,
+) -> tuple[Tensor, Tensor]:
+    """rasterize() whose colour is differentiable in the four Gaussian tensors (the reference's
+    rasterizer has a backward; render_cuda hands it means3D, cov3D_precomp, shs and opacities).
+
+    Same arguments and the same (color, radii), bit for bit. The forward runs on a workspace tensor
+    of its own, kept with the inputs, the camera arrays, color and radii for the backward
+    (tsplat_raster_bwd): the exact vector-Jacobian product with every discrete decision of the
+    forward held fixed, for the inputs that require grad. radii is not differentiable; there is no
+    double backward; cameras and background get no gradient. The per-pixel sums are float atomic
+    adds, so the last bits of a gradient can differ between two runs.
+    """
+    return _RasterizeFn.apply(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene,
+                              sh_degree, capacity, check, debug)
 
 
 MAX_VIEWS_PER_CALL = 32  # the rasterizer's per-scene view mask is 32 bits wide
