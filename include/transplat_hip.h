@@ -52,7 +52,7 @@ int tsplat_set_debug(int32_t on);
  * 5 uv coarse correlation, 6 uv cross correlation, 7 msda, 8 window attention, 9 the whole
  * rasterizer launch sequence, 10 group norm (both launches), 11 uv cross through the
  * correlation table, 17 rasterizer backward render, 18 rasterizer backward preprocess, 19 the
- * whole tsplat_raster_bwd launch sequence; 0 = off).
+ * whole tsplat_raster_bwd / tsplat_raster_depth_bwd launch sequence; 0 = off).
  * tsplat_prof_read waits for the recorded events, returns the summed duration and the number of
  * launches timed since the last enable/read, and resets the record. Used by bench.py only. */
 int tsplat_prof_enable(int32_t kernel_id);
@@ -153,8 +153,8 @@ int tsplat_raster_depth_fwd(const tsplat_raster_desc* desc,
  * d means is included; grad_cov lands on the six upper-triangle entries the forward reads (the lower
  * three get 0); SH coefficients above sh_degree get 0; s and s*s of scene_scale are in the chain.
  * This is the exact derivative of what the forward computes (the published upstream backward
- * ignores the 0.99 cap and the dependence of the clamped tx, ty on tz). No gradient of depth or
- * alpha outputs, none with respect to cameras or background.
+ * ignores the 0.99 cap and the dependence of the clamped tx, ty on tz). Gradients of the depth and
+ * alpha outputs: tsplat_raster_depth_bwd below. None with respect to cameras or background.
  *
  * out_color and radii are the outputs of the tsplat_raster_fwd call being differentiated,
  * fwd_workspace its workspace, untouched since (its records, tile offsets and instance keys are
@@ -177,6 +177,42 @@ int tsplat_raster_bwd(const tsplat_raster_desc* desc,
                       void* fwd_workspace, void* bwd_workspace,
                       float* grad_means, float* grad_cov, float* grad_shs, float* grad_opacity,
                       void* stream);
+
+/* Backward of tsplat_raster_depth_fwd in the Gaussians: the vector-Jacobian product of
+ *   F : (means, cov, shs, opacity) -> (out_color, out_depth, out_alpha)
+ * for (grad_color [V, 3, H, W], grad_depth [V, H, W], grad_alpha [V, H, W]), under the rules of
+ * tsplat_raster_bwd (same fixed decisions, same piecewise rules), in ONE pass: per pixel depth and
+ * alpha are two more blended channels over a zero background, the entry "colour" being
+ * (r, g, b, d, 1) and the pixel gradient (g0, g1, g2, gd, ga). The walk's O = out_color . g +
+ * out_depth gd + out_alpha ga comes from the saved outputs; the one new per-(view, Gaussian) sum,
+ * sum_pixels w gd, is field 9 of the 64-byte gradient record (same bwd_workspace size). It is chained
+ * through d = max(C0 f(z) + 0.5, 0), z = vz / s: nothing passes where C0 f + 0.5 <= 0; f' = 1
+ * (mode 0), -1 / z^2 (1), (z + eps)^-2 / (1 / (near + eps) - 1 / (far + eps) + eps) (2), 1 / z where
+ * far < z < near strictly and 0 elsewhere (3: with near < far every d is log(far), and the depth
+ * gradient flows through the weights alone). That reaches grad_means; grad_cov, grad_opacity and
+ * grad_shs get depth and alpha gradient only through the weights, and grad_shs is exactly 0 when
+ * grad_color is NULL (the SH coefficients are then neither read nor their view-direction term
+ * evaluated).
+ *
+ * near, far, depth_mode: what the forward call took. out_color / out_depth / out_alpha: its outputs.
+ * Each of grad_color, grad_depth, grad_alpha may be NULL: it reads as zero and its saved output is
+ * not read. With grad_color alone the call is tsplat_raster_bwd. TSPLAT_EINVAL, before any launch,
+ * if all three gradients are NULL, a gradient is given without its saved output, grad_depth is given
+ * without near and far, depth_mode is not 0..3, all four gradient outputs are NULL, or anything
+ * tsplat_raster_bwd rejects (its other pointers are required, shs included). Profiling ids 17-19
+ * time this entry's launches as they time tsplat_raster_bwd's. */
+int tsplat_raster_depth_bwd(const tsplat_raster_desc* desc,
+                            const float* means, const float* cov, const float* shs,
+                            const float* opacity, const float* viewmat, const float* projmat,
+                            const float* campos, const float* tanfov, const float* bg,
+                            const float* scene_scale, const float* near, const float* far,
+                            int32_t depth_mode,
+                            const float* out_color, const float* out_depth, const float* out_alpha,
+                            const float* grad_color, const float* grad_depth,
+                            const float* grad_alpha, const int32_t* radii,
+                            void* fwd_workspace, void* bwd_workspace,
+                            float* grad_means, float* grad_cov, float* grad_shs, float* grad_opacity,
+                            void* stream);
 
 
 /* Depth-candidate softmax head (reference depth_predictor_trans.py:170-180): logits [n, depths, hw]

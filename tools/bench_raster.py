@@ -12,7 +12,15 @@ one process for --rounds samples each; prints the median, lowest and highest per
 
 --backward: what the backward (tsplat_raster_bwd through rasterize_differentiable) costs at the same
 shape beside the forward call of the same process, its two kernels separately, and the render-backward
-kernel's atomic bytes over its time against the chip-wide float-atomic rate."""
+kernel's atomic bytes over its time against the chip-wide float-atomic rate.
+
+--backward --depth MODE: forward + backward of the depth routes in one process, the routes alternating:
+the colour-only pair (rasterize_differentiable), the fused pairs (rasterize_with_depth_differentiable:
+colour + depth, and colour + depth + alpha; tsplat_raster_depth_bwd) and the two-pass composition the
+fused call retires (rasterize_differentiable on the colour, plus depth_fake_color under autograd and a
+second rasterize_differentiable over the Gaussians repeated per view at sh_degree = 0). HIP events around
+--iters eager pairs per sample; then the library's own events around the forward and backward launch
+sequences and the two backward kernels of the colour-only and the fused route."""
 import argparse
 import os
 import sys
@@ -152,6 +160,107 @@ def backward_cost() -> None:
           f"of about 1.3 TB/s (floor {nbytes / 1.3e12 * 1e6:.1f} us)", flush=True)
 
 
+def backward_depth_routes(mode: str) -> None:
+    from statistics import median
+
+    from transplat_amd import synthetic as S
+    from transplat_amd.model.decoder.decoder_splatting_hip import depth_fake_color
+    from transplat_amd.model.decoder.hip_splatting import (prepare_cameras, rasterize_differentiable,
+                                                           rasterize_with_depth_differentiable)
+
+    hw = (256, 256)
+    g = S.make_gaussians(1, image_shape=hw, device=dev)
+    tb = S.make_batch(1, image_shape=hw, device=dev)["target"]
+    b, v = tb["near"].shape
+    ext, intr = tb["extrinsics"].reshape(b * v, 4, 4), tb["intrinsics"].reshape(b * v, 3, 3)
+    near, far = tb["near"].reshape(-1), tb["far"].reshape(-1)
+    black = torch.zeros(b * v, 3, device=dev)
+    cams = prepare_cameras(ext, intr, near, far, black)
+    leaves = [g[k].clone().requires_grad_() for k in ("means", "covariances", "harmonics", "opacities")]
+    gen = torch.Generator(device=dev).manual_seed(1)
+    grad_color = torch.randn((b * v, 3, *hw), generator=gen, device=dev)
+    grad_depth = torch.randn((b * v, *hw), generator=gen, device=dev)
+    grad_alpha = torch.randn((b * v, *hw), generator=gen, device=dev)
+
+    def clear():
+        for t in leaves:
+            t.grad = None
+
+    def colour_pair():
+        clear()
+        color, _ = rasterize_differentiable(*leaves, cams, hw, v, check=False)
+        color.backward(grad_color)
+
+    def fused_pair(alpha):
+        clear()
+        out = rasterize_with_depth_differentiable(*leaves, cams, hw, v, check=False, near=near, far=far,
+                                                  depth_mode=mode, alpha=alpha)
+        outs, grads = [out.color, out.depth], [grad_color, grad_depth]
+        if alpha:
+            outs.append(out.alpha)
+            grads.append(grad_alpha)
+        torch.autograd.backward(outs, grads)
+
+    def two_pass_pair():
+        clear()
+        m, k, sh, o = leaves
+        color, _ = rasterize_differentiable(m, k, sh, o, cams, hw, v, check=False)
+        rep = lambda t: t.repeat_interleave(v, dim=0)
+        means = rep(m)
+        fake = depth_fake_color(ext, means, near, far, mode)
+        fc, _ = rasterize_differentiable(means, rep(k), fake[:, :, None, None].expand(-1, -1, 3, 1).contiguous(), rep(o),
+                                         cams, hw, 1, sh_degree=0, check=False)
+        torch.autograd.backward([color, fc.mean(dim=1)], [grad_color, grad_depth])
+
+    routes = {"colour only": colour_pair, "fused colour + depth": lambda: fused_pair(False),
+              "fused colour + depth + alpha": lambda: fused_pair(True), "two-pass colour + depth": two_pass_pair}
+    for f in routes.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    routes["fused colour + depth"]()
+    fused = [t.grad.clone() for t in leaves]
+    two_pass_pair()
+    torch.cuda.synchronize()
+    print(f"depth mode {mode}: fused vs two-pass gradients, max |diff| / max |two-pass|: " + ", ".join(
+        f"{float((a - t.grad).abs().max() / t.grad.abs().max()):.2e}" for a, t in zip(fused, leaves)), flush=True)
+    us = {k: [] for k in routes}
+    for _ in range(args.rounds):
+        for k, f in routes.items():
+            a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(args.iters):
+                f()
+            e.record()
+            e.synchronize()
+            us[k].append(a.elapsed_time(e) / args.iters * 1e3)
+    for k, t in us.items():
+        print(f"{k:>30}: median {median(t):8.1f} us per forward + backward (min {min(t):.1f}, max {max(t):.1f}; {len(t)} "
+              f"samples x {args.iters} eager pairs, {b * v} views, G = {g['means'].shape[1]}, 256x256)", flush=True)
+    ids = ("raster", "raster_bwd", "raster_bwd_render", "raster_bwd_preprocess")
+    label = {"raster": "forward call", "raster_bwd": "backward call", "raster_bwd_render": "  render_bwd_kernel",
+             "raster_bwd_preprocess": "  preprocess_bwd_kernel"}
+    timed = ("colour only", "fused colour + depth", "fused colour + depth + alpha")
+    lib_us = {(r, k): [] for r in timed for k in ids}
+    for _ in range(args.rounds):
+        for r in timed:
+            for k in ids:
+                _lib.prof_enable(k)
+                for _ in range(args.iters):
+                    routes[r]()
+                ms, n = _lib.prof_read()
+                _lib.prof_enable(None)
+                lib_us[(r, k)].append(ms / n * 1e3)
+    for r in timed:
+        for k in ids:
+            t = lib_us[(r, k)]
+            print(f"{r:>30} {label[k]:<24}: median {median(t):8.1f} us (min {min(t):.1f}, max {max(t):.1f}; "
+                  f"{args.rounds} samples x {args.iters} calls)", flush=True)
+
+
+if args.backward and args.depth:
+    backward_depth_routes(args.depth)
+    sys.exit(0)
 if args.backward:
     backward_cost()
     sys.exit(0)

@@ -55,6 +55,10 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.POINTER(RasterDesc)] + [_P] * 20,
     ),
+    "tsplat_raster_depth_bwd": (
+        ctypes.c_int,
+        [ctypes.POINTER(RasterDesc)] + [_P] * 12 + [_I32] + [_P] * 14,
+    ),
     "tsplat_uv_coarse_fwd": (ctypes.c_int, [_P] * 4 + [_I32] * 5 + [_P]),
     "tsplat_uv_cross_fwd": (ctypes.c_int, [_P] * 7 + [_I32] * 6 + [_P]),
     "tsplat_uv_cross_table_fwd": (ctypes.c_int, [_P] * 6 + [_I32] * 6 + [_P]),

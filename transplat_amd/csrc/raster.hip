@@ -1,6 +1,7 @@
-// Gaussian-splat rasterizer for gfx950 (MI355X): the forward, and the backward of its colour render
-// in the Gaussians (tsplat_raster_bwd: render_bwd_kernel and preprocess_bwd_kernel, after the forward
-// kernels below, which it leaves as they are and whose steps it reuses).
+// Gaussian-splat rasterizer for gfx950 (MI355X): the forward, and the backward of its colour, depth and
+// alpha renders in the Gaussians (tsplat_raster_bwd, tsplat_raster_depth_bwd: render_bwd_kernel and
+// preprocess_bwd_kernel, after the forward kernels below, which they leave as they are and whose steps
+// they reuse).
 //
 // Algorithm = the graphdeco forward rasterizer behind `GaussianRasterizer` as called by
 // `render_cuda` (reference src/model/decoder/cuda_splatting.py:56-136): preprocess (cull at
@@ -997,9 +998,10 @@ constexpr int kGradRecFloats = 16;  // gradient record of a (view, Gaussian): 64
 // fields of a gradient record: 0 px, 1 py (pixel-space mean); 2 3 4 the PLAIN conic (a, b, c) of
 // power = -(a dx^2 + c dy^2) / 2 - b dx dy (not the log2-scaled form the forward stores: the
 // factors log2(e) ln(2) cancel here, so preprocess_bwd_kernel needs no constant); 5 opacity;
-// 6 7 8 the clamped colour max(r + 0.5, 0); 9..15 padding
-constexpr int kGradFields = 9;
-constexpr int kAccStride = 12;      // floats per entry of a wave's LDS sums (9 used)
+// 6 7 8 the clamped colour max(r + 0.5, 0); 9 the depth value d = max(C0 f + 0.5, 0)
+// (tsplat_raster_depth_bwd only, else 0); 10..15 padding
+constexpr int kGradFields = 9;      // fields of the colour-only backward; field kGradFields is d's
+constexpr int kAccStride = 12;      // floats per entry of a wave's LDS sums (up to 10 used)
 
 // Data-parallel-primitive reads of another lane's value inside the VALU (no LDS crossbar trip, unlike
 // __shfl_xor's ds_bpermute): a lane with no source lane reads 0. Controls: quad_perm [1, 0, 3, 2] and
@@ -1031,12 +1033,30 @@ __device__ __forceinline__ float dpp_f32(float x) {
 // instead of 24), lanes 0-3 park the sums in the wave's LDS slot, and after the chunk the wave adds them to the
 // gradient records: 16 lanes per record, 4 records per wave instruction (contiguous 36-byte
 // segments of 64-byte records), at most one add per (wave, entry, field), none for an exact 0.
+//
+// <kColor, kExtra>, as the forward's: <true, false> is the colour-only backward of tsplat_raster_bwd.
+// kExtra (tsplat_raster_depth_bwd): depth and alpha are two more blended channels over a zero
+// background, the entry "colour" being (r, g, b, d, 1) and the pixel gradient (g0, g1, g2, gd, ga),
+// so O gains out_depth gd + out_alpha ga, c_i . g gains d_i gd + ga (d from rec[3].w, one more
+// compacted field; alpha's share of both is folded into one constant of S, see its load below), and
+// there is one more sum, w gd, in field 9 of the gradient record: ten sums
+// through the same reduce-scatter, 40 contiguous bytes per record. grad_depth / grad_alpha NULL read
+// as zero (their saved outputs are not read). Without kColor (no colour gradient) the rgb fields,
+// their three sums and the colour reads are gone: seven sums, fields 0-5 and 9.
+template <bool kColor, bool kExtra>
 __global__ void __launch_bounds__(kTileThreads)
 render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __restrict__ grad_color,
-                  float* __restrict__ grec, Workspace ws) {
-    constexpr int kRgbField = kGeomFields;
-    constexpr int kIdField = kGeomFields + 3;  // the entry's Gaussian id (bits)
-    constexpr int kRecFields = kIdField + 1;   // 10
+                  float* __restrict__ grec, Workspace ws,
+                  // kExtra only, and last: the colour-only instantiation's argument block is unchanged
+                  const float* __restrict__ out_depth, const float* __restrict__ grad_depth,
+                  const float* __restrict__ out_alpha, const float* __restrict__ grad_alpha) {
+    constexpr int kRgbField = kGeomFields;                        // r g b (kColor)
+    constexpr int kDepthField = kGeomFields + (kColor ? 3 : 0);   // d (kExtra)
+    constexpr int kIdField = kDepthField + (kExtra ? 1 : 0);      // the entry's Gaussian id (bits)
+    constexpr int kRecFields = kIdField + 1;                      // 10, 11 or 8
+    constexpr int kSums = kGeomFields + (kColor ? 3 : 0) + (kExtra ? 1 : 0);  // 9, 10 or 7
+    constexpr int kDepthSum = kSums - 1;                          // kExtra: the local index of sum w gd
+    static_assert(kSums <= kAccStride && kGradFields + 1 <= kGradRecFloats, "sums fit their slots");
     __shared__ uint64_t skeys[kSortCap];
     __shared__ uint32_t s_cnt[kBuckets];
     __shared__ uint32_t s_red[4];
@@ -1079,14 +1099,34 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
     const float pfx = (float)pxi, pfy = (float)pyi;
     float T = 1.0f;
     float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+    float gd = 0.f;  // kExtra
     float S = 0.f;  // out . g minus the entries walked so far
     if (inside) {
         const size_t hw = (size_t)p.H * p.W;
-        const size_t at = (size_t)v * 3 * hw + (size_t)pyi * p.W + pxi;
-        g0 = grad_color[at];
-        g1 = grad_color[at + hw];
-        g2 = grad_color[at + 2 * hw];
-        S = out_color[at] * g0 + out_color[at + hw] * g1 + out_color[at + 2 * hw] * g2;
+        if constexpr (kColor) {
+            const size_t at = (size_t)v * 3 * hw + (size_t)pyi * p.W + pxi;
+            g0 = grad_color[at];
+            g1 = grad_color[at + hw];
+            g2 = grad_color[at + 2 * hw];
+            S = out_color[at] * g0 + out_color[at + hw] * g1 + out_color[at + 2 * hw] * g2;
+        }
+        if constexpr (kExtra) {
+            const size_t at1 = (size_t)v * hw + (size_t)pyi * p.W + pxi;
+            if (grad_depth) {
+                gd = grad_depth[at1];
+                S = S + out_depth[at1] * gd;
+            }
+            if (grad_alpha) {
+                // alpha's channel value is 1 for every entry, so its part of S_i has a closed form:
+                // ga sum_{j > i} w_j = ga (T_{i+1} - T_final), and T_i ga - ga (T_{i+1} - T_final) /
+                // (1 - alpha_i) = ga T_final / (1 - alpha_i). S carries the constant -ga T_final and
+                // c_i . g no ga term. Walked as a channel (S = out_alpha ga - sum w_j ga) every
+                // alpha gradient is a difference of O(1) sums that leaves O(T_final): measured
+                // e = 3.9e-4 on an alpha-only loss, against 1e-5 this way.
+                const float ga = grad_alpha[at1];
+                S = S - ga * (1.0f - out_alpha[at1]);
+            }
+        }
     }
     const size_t vbase = (size_t)v * p.G;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
@@ -1097,7 +1137,7 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
 
     // one entry at this lane's pixel: the forward's blend() decisions, then the nine contributions
     auto entry = [&](float x, float y, float ca, float cb, float cc, float o, float r, float g, float bl,
-                     float (&val)[kGradFields]) {
+                     float d, float (&val)[kSums]) {
         const float dx = x - pfx, dy = y - pfy;
         const float power2 = fmaf(dy, fmaf(cc, dy, cb * dx), (ca * dx) * dx);
         const float ex = __builtin_amdgcn_exp2f(power2);
@@ -1108,7 +1148,9 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
         const bool stop = contrib && (test_T < 0.0001f);
         const bool acc = contrib && !stop;
         const float w = acc ? alpha * T : 0.0f;
-        const float cg = r * g0 + g * g1 + bl * g2;
+        float cg = 0.0f;
+        if constexpr (kColor) cg = r * g0 + g * g1 + bl * g2;
+        if constexpr (kExtra) cg = cg + d * gd;  // alpha's term: the constant in S
         S = fmaf(-w, cg, S);
         const float dalpha = acc ? T * cg - S * __builtin_amdgcn_rcpf(1.0f - alpha) : 0.0f;
         const bool pass = acc && !(oe > 0.99f);  // the 0.99 cap passes nothing to conic, mean, opacity
@@ -1121,9 +1163,12 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
         val[3] = gp * (-dx * dy);
         val[4] = gp * (-0.5f * dy * dy);
         val[5] = pass ? dalpha * ex : 0.0f;
-        val[6] = w * g0;
-        val[7] = w * g1;
-        val[8] = w * g2;
+        if constexpr (kColor) {
+            val[6] = w * g0;
+            val[7] = w * g1;
+            val[8] = w * g2;
+        }
+        if constexpr (kExtra) val[kDepthSum] = w * gd;
         T = acc ? test_T : T;
         done = done || stop;
     };
@@ -1169,9 +1214,12 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
                 w_rec[3][pos] = co.y;
                 w_rec[4][pos] = co.z;
                 w_rec[5][pos] = co.w;
-                w_rec[kRgbField][pos] = rgb.x;
-                w_rec[kRgbField + 1][pos] = rgb.y;
-                w_rec[kRgbField + 2][pos] = rgb.z;
+                if constexpr (kColor) {
+                    w_rec[kRgbField][pos] = rgb.x;
+                    w_rec[kRgbField + 1][pos] = rgb.y;
+                    w_rec[kRgbField + 2][pos] = rgb.z;
+                }
+                if constexpr (kExtra) w_rec[kDepthField][pos] = cull.w;
                 w_rec[kIdField][pos] = __uint_as_float(gid);
             }
             // pad the last quad with entries that contribute nothing (opacity 0: alpha < 1/255)
@@ -1186,16 +1234,19 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
                 float4 q[kIdField];
 #pragma unroll
                 for (int f = 0; f < kIdField; ++f) q[f] = *reinterpret_cast<const float4*>(&w_rec[f][i]);
-                float va[4][kGradFields];
-                entry(q[0].x, q[1].x, q[2].x, q[3].x, q[4].x, q[5].x, q[6].x, q[7].x, q[8].x, va[0]);
-                entry(q[0].y, q[1].y, q[2].y, q[3].y, q[4].y, q[5].y, q[6].y, q[7].y, q[8].y, va[1]);
-                entry(q[0].z, q[1].z, q[2].z, q[3].z, q[4].z, q[5].z, q[6].z, q[7].z, q[8].z, va[2]);
-                entry(q[0].w, q[1].w, q[2].w, q[3].w, q[4].w, q[5].w, q[6].w, q[7].w, q[8].w, va[3]);
+                float va[4][kSums];
+                // fields an instantiation does not carry are read from field 0 and never used
+                constexpr int iR = kColor ? kRgbField : 0, iG = kColor ? kRgbField + 1 : 0,
+                              iB = kColor ? kRgbField + 2 : 0, iD = kExtra ? kDepthField : 0;
+                entry(q[0].x, q[1].x, q[2].x, q[3].x, q[4].x, q[5].x, q[iR].x, q[iG].x, q[iB].x, q[iD].x, va[0]);
+                entry(q[0].y, q[1].y, q[2].y, q[3].y, q[4].y, q[5].y, q[iR].y, q[iG].y, q[iB].y, q[iD].y, va[1]);
+                entry(q[0].z, q[1].z, q[2].z, q[3].z, q[4].z, q[5].z, q[iR].z, q[iG].z, q[iB].z, q[iD].z, va[2]);
+                entry(q[0].w, q[1].w, q[2].w, q[3].w, q[4].w, q[5].w, q[iR].w, q[iG].w, q[iB].w, q[iD].w, va[3]);
                 // reduce-scatter: lanes with bit 0 clear keep entries {0, 1}, the others {2, 3};
                 // then bit 1 picks one of the pair; then the 16 lane quads are summed onto lanes 0-3
-                float tot[kGradFields];
+                float tot[kSums];
 #pragma unroll
-                for (int f = 0; f < kGradFields; ++f) {
+                for (int f = 0; f < kSums; ++f) {
                     const float keep0 = b0 ? va[2][f] : va[0][f], keep1 = b0 ? va[3][f] : va[1][f];
                     const float send0 = b0 ? va[0][f] : va[2][f], send1 = b0 ? va[1][f] : va[3][f];
                     const float u0 = keep0 + dpp_f32<kDppQuadXor1>(send0);
@@ -1210,8 +1261,15 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
                 if (lane < 4) {
                     float* a = w_acc[i + my_e];
                     *reinterpret_cast<float4*>(a) = make_float4(tot[0], tot[1], tot[2], tot[3]);
-                    *reinterpret_cast<float4*>(a + 4) = make_float4(tot[4], tot[5], tot[6], tot[7]);
-                    a[8] = tot[8];
+                    if constexpr (kColor) {
+                        *reinterpret_cast<float4*>(a + 4) = make_float4(tot[4], tot[5], tot[6], tot[7]);
+                        if constexpr (kExtra)
+                            *reinterpret_cast<float2*>(a + 8) = make_float2(tot[8], tot[9]);
+                        else
+                            a[8] = tot[8];
+                    } else {
+                        *reinterpret_cast<float4*>(a + 4) = make_float4(tot[4], tot[5], tot[6], 0.0f);
+                    }
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1222,10 +1280,12 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
                 const int f = lane & 15;
                 for (int j = 0; j < m; j += 4) {
                     const int e = j + (lane >> 4);
-                    if (e < m && f < kGradFields) {
+                    if (e < m && f < kSums) {
                         const float val = w_acc[e][f];
                         const uint32_t id = __float_as_uint(w_rec[kIdField][e]);
-                        if (val != 0.0f) atomicAdd(grec + (vbase + id) * kGradRecFloats + f, val);
+                        // the record's field: the local sum's own index, but for the depth sum without colour
+                        const int rf = (!kColor && f == kDepthSum) ? kGradFields : f;
+                        if (val != 0.0f) atomicAdd(grec + (vbase + id) * kGradRecFloats + rf, val);
                     }
                 }
             }
@@ -1248,6 +1308,33 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
 // two [threads][75] float LDS arrays (coefficients and their gradients), 76,800 bytes.
 constexpr int kPreBwdThreads = 128;
 
+// The derivative f'(z) of the fake colour behind depth_value(), times C0, where the clamp of
+// d = max(C0 f + 0.5, 0) is open; 0 where it is active (C0 f + 0.5 <= 0). z = vz / s, the forward's
+// expression. "log": f = log(max(min(z, near), far)) follows z only where far < z < near strictly.
+__device__ __forceinline__ float depth_value_dz(int mode, float vz, float s, float near, float far) {
+    const float z = vz / s;
+    float f = z, df = 1.0f;
+    if (mode == 1) {
+        f = 1.0f / z;
+        df = -1.0f / (z * z);
+    } else if (mode == 2) {
+        const float eps = 1e-10f;
+        const float disp_near = 1.0f / (near + eps), disp_far = 1.0f / (far + eps);
+        const float den = disp_near - disp_far + eps;
+        f = 1.0f - (1.0f / (z + eps) - disp_far) / den;
+        df = 1.0f / ((z + eps) * (z + eps)) / den;
+    } else if (mode == 3) {
+        f = logf(fmaxf(fminf(z, near), far));
+        df = (z > far && z < near) ? 1.0f / z : 0.0f;
+    }
+    return kSH_C0 * f + 0.5f > 0.0f ? kSH_C0 * df : 0.0f;
+}
+
+// <kColor, kExtra>, as render_bwd_kernel's: <true, false> is tsplat_raster_bwd's. kExtra chains field
+// 9 of the record (sum w gd) through the depth value into d vz, when p.depth_mode >= 0. Without kColor
+// the SH block is neither staged nor evaluated, the view direction has no part in d means, and
+// grad_shs is written as zeros.
+template <bool kColor, bool kExtra>
 __global__ void __launch_bounds__(kPreBwdThreads)
 preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __restrict__ cov,
                       const float* __restrict__ shs, const float* __restrict__ opacity,
@@ -1256,9 +1343,11 @@ preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __
                       const float* __restrict__ scene_scale, const int32_t* __restrict__ radii,
                       const float* __restrict__ grec, float* __restrict__ grad_means,
                       float* __restrict__ grad_cov, float* __restrict__ grad_shs,
-                      float* __restrict__ grad_opacity) {
-    __shared__ float s_sh[kPreBwdThreads * kMaxShFloats];
-    __shared__ float s_dsh[kPreBwdThreads * kMaxShFloats];
+                      float* __restrict__ grad_opacity,
+                      // kExtra only, and last: the colour-only instantiation's argument block is unchanged
+                      const float* __restrict__ near, const float* __restrict__ far) {
+    __shared__ float s_sh[kColor ? kPreBwdThreads * kMaxShFloats : 1];
+    __shared__ float s_dsh[kColor ? kPreBwdThreads * kMaxShFloats : 1];
     const int scene = blockIdx.y;
     const int lane = threadIdx.x % kWave, wid = threadIdx.x / kWave;
     const int g = blockIdx.x * kPreBwdThreads + threadIdx.x;
@@ -1269,7 +1358,7 @@ preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __
     const int gw0 = blockIdx.x * kPreBwdThreads + wid * kWave;
     const int sh_total = max(0, min(kWave, p.G - gw0)) * nf;
     const size_t sh_off = (size_t)nf * ((size_t)scene * p.G + gw0);
-    {
+    if constexpr (kColor) {
         const float* sh_src = shs + sh_off;
         float* sh_dst = s_sh + (size_t)wid * kWave * nf;
         float* dsh_dst = s_dsh + (size_t)wid * kWave * nf;
@@ -1370,9 +1459,15 @@ preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __
             const float itz = 1.0f / tz, itz2 = itz * itz;
             const float dvx = in_x ? -dj02 * fx * itz2 : 0.0f;
             const float dvy = in_y ? -dj12 * fy * itz2 : 0.0f;
-            const float dvz = -(dj00 * fx + dj11 * fy) * itz2 +
-                              dj02 * (fx * rx * itz2 + (in_x ? fx * vx * itz2 * itz : 0.0f)) +
-                              dj12 * (fy * ry * itz2 + (in_y ? fy * vy * itz2 * itz : 0.0f));
+            float dvz = -(dj00 * fx + dj11 * fy) * itz2 +
+                        dj02 * (fx * rx * itz2 + (in_x ? fx * vx * itz2 * itz : 0.0f)) +
+                        dj12 * (fy * ry * itz2 + (in_y ? fy * vy * itz2 * itz : 0.0f));
+            if constexpr (kExtra) {
+                // the depth value d = max(C0 f(vz / s) + 0.5, 0): field 9 of the record is dL/dd
+                const float g_d = gr[2].y;
+                if (p.depth_mode >= 0 && g_d != 0.0f)
+                    dvz = dvz + g_d * depth_value_dz(p.depth_mode, vz, s, near[v], far[v]) / s;
+            }
             float dmx = vm[0] * dvx + vm[1] * dvy + vm[2] * dvz;
             float dmy = vm[4] * dvx + vm[5] * dvy + vm[6] * dvz;
             float dmz = vm[8] * dvx + vm[9] * dvy + vm[10] * dvz;
@@ -1384,79 +1479,81 @@ preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __
             dmy += pm[4] * dhx + pm[5] * dhy + pm[7] * dhw;
             dmz += pm[8] * dhx + pm[9] * dhy + pm[11] * dhw;
 
-            // colour: rgb_c = max(sum_k B_k(n) sh[c][k] + 0.5, 0), n = d / |d|, d = mean s - campos
-            const float* cp = campos + 3 * v;
-            const float ddx = mx - cp[0], ddy = my - cp[1], ddz = mz - cp[2];
-            float rgb[3];
-            sh_to_rgb(my_sh, p.M, p.deg, ddx, ddy, ddz, rgb);
-            float tc[3];
+            if constexpr (kColor) {
+                // colour: rgb_c = max(sum_k B_k(n) sh[c][k] + 0.5, 0), n = d / |d|, d = mean s - campos
+                const float* cp = campos + 3 * v;
+                const float ddx = mx - cp[0], ddy = my - cp[1], ddz = mz - cp[2];
+                float rgb[3];
+                sh_to_rgb(my_sh, p.M, p.deg, ddx, ddy, ddz, rgb);
+                float tc[3];
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) tc[ch] = rgb[ch] > 0.0f ? g_rgb[ch] : 0.0f;  // the clamp at 0
-            const float len = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
-            const float x = ddx / len, y = ddy / len, z = ddz / len;
-            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            float dnx = 0.f, dny = 0.f, dnz = 0.f;
-            // one basis function: value B and its gradient (bx, by, bz) in the unit direction
-            auto term = [&](int k, float B, float bx, float by, float bz) {
-                const float ak = tc[0] * my_sh[k] + tc[1] * my_sh[p.M + k] + tc[2] * my_sh[2 * p.M + k];
-                dnx += bx * ak;
-                dny += by * ak;
-                dnz += bz * ak;
-                my_dsh[k] += tc[0] * B;
-                my_dsh[p.M + k] += tc[1] * B;
-                my_dsh[2 * p.M + k] += tc[2] * B;
-            };
-            term(0, kSH_C0, 0.f, 0.f, 0.f);
-            if (nb > 1) {
-                term(1, -kSH_C1 * y, 0.f, -kSH_C1, 0.f);
-                term(2, kSH_C1 * z, 0.f, 0.f, kSH_C1);
-                term(3, -kSH_C1 * x, -kSH_C1, 0.f, 0.f);
+                for (int ch = 0; ch < 3; ++ch) tc[ch] = rgb[ch] > 0.0f ? g_rgb[ch] : 0.0f;  // the clamp at 0
+                const float len = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+                const float x = ddx / len, y = ddy / len, z = ddz / len;
+                const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+                float dnx = 0.f, dny = 0.f, dnz = 0.f;
+                // one basis function: value B and its gradient (bx, by, bz) in the unit direction
+                auto term = [&](int k, float B, float bx, float by, float bz) {
+                    const float ak = tc[0] * my_sh[k] + tc[1] * my_sh[p.M + k] + tc[2] * my_sh[2 * p.M + k];
+                    dnx += bx * ak;
+                    dny += by * ak;
+                    dnz += bz * ak;
+                    my_dsh[k] += tc[0] * B;
+                    my_dsh[p.M + k] += tc[1] * B;
+                    my_dsh[2 * p.M + k] += tc[2] * B;
+                };
+                term(0, kSH_C0, 0.f, 0.f, 0.f);
+                if (nb > 1) {
+                    term(1, -kSH_C1 * y, 0.f, -kSH_C1, 0.f);
+                    term(2, kSH_C1 * z, 0.f, 0.f, kSH_C1);
+                    term(3, -kSH_C1 * x, -kSH_C1, 0.f, 0.f);
+                }
+                if (nb > 4) {
+                    term(4, kSH_C2[0] * xy, kSH_C2[0] * y, kSH_C2[0] * x, 0.f);
+                    term(5, kSH_C2[1] * yz, 0.f, kSH_C2[1] * z, kSH_C2[1] * y);
+                    term(6, kSH_C2[2] * (2.0f * zz - xx - yy), kSH_C2[2] * -2.0f * x, kSH_C2[2] * -2.0f * y,
+                         kSH_C2[2] * 4.0f * z);
+                    term(7, kSH_C2[3] * xz, kSH_C2[3] * z, 0.f, kSH_C2[3] * x);
+                    term(8, kSH_C2[4] * (xx - yy), kSH_C2[4] * 2.0f * x, kSH_C2[4] * -2.0f * y, 0.f);
+                }
+                if (nb > 9) {
+                    term(9, kSH_C3[0] * y * (3.0f * xx - yy), kSH_C3[0] * 6.0f * xy, kSH_C3[0] * (3.0f * xx - 3.0f * yy), 0.f);
+                    term(10, kSH_C3[1] * xy * z, kSH_C3[1] * yz, kSH_C3[1] * xz, kSH_C3[1] * xy);
+                    term(11, kSH_C3[2] * y * (4.0f * zz - xx - yy), kSH_C3[2] * -2.0f * xy,
+                         kSH_C3[2] * (4.0f * zz - xx - 3.0f * yy), kSH_C3[2] * 8.0f * yz);
+                    term(12, kSH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy), kSH_C3[3] * -6.0f * xz,
+                         kSH_C3[3] * -6.0f * yz, kSH_C3[3] * (6.0f * zz - 3.0f * xx - 3.0f * yy));
+                    term(13, kSH_C3[4] * x * (4.0f * zz - xx - yy), kSH_C3[4] * (4.0f * zz - 3.0f * xx - yy),
+                         kSH_C3[4] * -2.0f * xy, kSH_C3[4] * 8.0f * xz);
+                    term(14, kSH_C3[5] * z * (xx - yy), kSH_C3[5] * 2.0f * xz, kSH_C3[5] * -2.0f * yz,
+                         kSH_C3[5] * (xx - yy));
+                    term(15, kSH_C3[6] * x * (xx - 3.0f * yy), kSH_C3[6] * (3.0f * xx - 3.0f * yy), kSH_C3[6] * -6.0f * xy,
+                         0.f);
+                }
+                if (nb > 16) {
+                    const float s7 = 7.0f * zz - 1.0f, t7 = 7.0f * zz - 3.0f;
+                    term(16, kSH_C4[0] * xy * (xx - yy), kSH_C4[0] * y * (3.0f * xx - yy), kSH_C4[0] * x * (xx - 3.0f * yy),
+                         0.f);
+                    term(17, kSH_C4[1] * yz * (3.0f * xx - yy), kSH_C4[1] * 6.0f * xy * z,
+                         kSH_C4[1] * z * (3.0f * xx - 3.0f * yy), kSH_C4[1] * y * (3.0f * xx - yy));
+                    term(18, kSH_C4[2] * xy * s7, kSH_C4[2] * y * s7, kSH_C4[2] * x * s7, kSH_C4[2] * 14.0f * xy * z);
+                    term(19, kSH_C4[3] * yz * t7, 0.f, kSH_C4[3] * z * t7, kSH_C4[3] * y * (21.0f * zz - 3.0f));
+                    term(20, kSH_C4[4] * (zz * (35.0f * zz - 30.0f) + 3.0f), 0.f, 0.f,
+                         kSH_C4[4] * z * (140.0f * zz - 60.0f));
+                    term(21, kSH_C4[5] * xz * t7, kSH_C4[5] * z * t7, 0.f, kSH_C4[5] * x * (21.0f * zz - 3.0f));
+                    term(22, kSH_C4[6] * (xx - yy) * s7, kSH_C4[6] * 2.0f * x * s7, kSH_C4[6] * -2.0f * y * s7,
+                         kSH_C4[6] * 14.0f * z * (xx - yy));
+                    term(23, kSH_C4[7] * xz * (xx - 3.0f * yy), kSH_C4[7] * z * (3.0f * xx - 3.0f * yy),
+                         kSH_C4[7] * -6.0f * xy * z, kSH_C4[7] * x * (xx - 3.0f * yy));
+                    term(24, kSH_C4[8] * (xx * (xx - 3.0f * yy) - yy * (3.0f * xx - yy)),
+                         kSH_C4[8] * x * (4.0f * xx - 12.0f * yy), kSH_C4[8] * y * (4.0f * yy - 12.0f * xx), 0.f);
+                }
+                // through n = d / |d|: dL/dd = (dn - n (n . dn)) / |d|
+                const float ndot = x * dnx + y * dny + z * dnz;
+                dmx += (dnx - x * ndot) / len;
+                dmy += (dny - y * ndot) / len;
+                dmz += (dnz - z * ndot) / len;
             }
-            if (nb > 4) {
-                term(4, kSH_C2[0] * xy, kSH_C2[0] * y, kSH_C2[0] * x, 0.f);
-                term(5, kSH_C2[1] * yz, 0.f, kSH_C2[1] * z, kSH_C2[1] * y);
-                term(6, kSH_C2[2] * (2.0f * zz - xx - yy), kSH_C2[2] * -2.0f * x, kSH_C2[2] * -2.0f * y,
-                     kSH_C2[2] * 4.0f * z);
-                term(7, kSH_C2[3] * xz, kSH_C2[3] * z, 0.f, kSH_C2[3] * x);
-                term(8, kSH_C2[4] * (xx - yy), kSH_C2[4] * 2.0f * x, kSH_C2[4] * -2.0f * y, 0.f);
-            }
-            if (nb > 9) {
-                term(9, kSH_C3[0] * y * (3.0f * xx - yy), kSH_C3[0] * 6.0f * xy, kSH_C3[0] * (3.0f * xx - 3.0f * yy), 0.f);
-                term(10, kSH_C3[1] * xy * z, kSH_C3[1] * yz, kSH_C3[1] * xz, kSH_C3[1] * xy);
-                term(11, kSH_C3[2] * y * (4.0f * zz - xx - yy), kSH_C3[2] * -2.0f * xy,
-                     kSH_C3[2] * (4.0f * zz - xx - 3.0f * yy), kSH_C3[2] * 8.0f * yz);
-                term(12, kSH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy), kSH_C3[3] * -6.0f * xz,
-                     kSH_C3[3] * -6.0f * yz, kSH_C3[3] * (6.0f * zz - 3.0f * xx - 3.0f * yy));
-                term(13, kSH_C3[4] * x * (4.0f * zz - xx - yy), kSH_C3[4] * (4.0f * zz - 3.0f * xx - yy),
-                     kSH_C3[4] * -2.0f * xy, kSH_C3[4] * 8.0f * xz);
-                term(14, kSH_C3[5] * z * (xx - yy), kSH_C3[5] * 2.0f * xz, kSH_C3[5] * -2.0f * yz,
-                     kSH_C3[5] * (xx - yy));
-                term(15, kSH_C3[6] * x * (xx - 3.0f * yy), kSH_C3[6] * (3.0f * xx - 3.0f * yy), kSH_C3[6] * -6.0f * xy,
-                     0.f);
-            }
-            if (nb > 16) {
-                const float s7 = 7.0f * zz - 1.0f, t7 = 7.0f * zz - 3.0f;
-                term(16, kSH_C4[0] * xy * (xx - yy), kSH_C4[0] * y * (3.0f * xx - yy), kSH_C4[0] * x * (xx - 3.0f * yy),
-                     0.f);
-                term(17, kSH_C4[1] * yz * (3.0f * xx - yy), kSH_C4[1] * 6.0f * xy * z,
-                     kSH_C4[1] * z * (3.0f * xx - 3.0f * yy), kSH_C4[1] * y * (3.0f * xx - yy));
-                term(18, kSH_C4[2] * xy * s7, kSH_C4[2] * y * s7, kSH_C4[2] * x * s7, kSH_C4[2] * 14.0f * xy * z);
-                term(19, kSH_C4[3] * yz * t7, 0.f, kSH_C4[3] * z * t7, kSH_C4[3] * y * (21.0f * zz - 3.0f));
-                term(20, kSH_C4[4] * (zz * (35.0f * zz - 30.0f) + 3.0f), 0.f, 0.f,
-                     kSH_C4[4] * z * (140.0f * zz - 60.0f));
-                term(21, kSH_C4[5] * xz * t7, kSH_C4[5] * z * t7, 0.f, kSH_C4[5] * x * (21.0f * zz - 3.0f));
-                term(22, kSH_C4[6] * (xx - yy) * s7, kSH_C4[6] * 2.0f * x * s7, kSH_C4[6] * -2.0f * y * s7,
-                     kSH_C4[6] * 14.0f * z * (xx - yy));
-                term(23, kSH_C4[7] * xz * (xx - 3.0f * yy), kSH_C4[7] * z * (3.0f * xx - 3.0f * yy),
-                     kSH_C4[7] * -6.0f * xy * z, kSH_C4[7] * x * (xx - 3.0f * yy));
-                term(24, kSH_C4[8] * (xx * (xx - 3.0f * yy) - yy * (3.0f * xx - yy)),
-                     kSH_C4[8] * x * (4.0f * xx - 12.0f * yy), kSH_C4[8] * y * (4.0f * yy - 12.0f * xx), 0.f);
-            }
-            // through n = d / |d|: dL/dd = (dn - n (n . dn)) / |d|
-            const float ndot = x * dnx + y * dny + z * dnz;
-            dmx += (dnx - x * ndot) / len;
-            dmy += (dny - y * ndot) / len;
-            dmz += (dnz - z * ndot) / len;
             // scale-invariant rendering: mean s (cov s^2 is in gk above)
             gm0 += s * dmx;
             gm1 += s * dmy;
@@ -1486,8 +1583,12 @@ preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (grad_shs) {
         float* dst = grad_shs + sh_off;
-        const float* src = s_dsh + (size_t)wid * kWave * nf;
-        for (int i = lane; i < sh_total; i += kWave) dst[i] = src[i];
+        if constexpr (kColor) {
+            const float* src = s_dsh + (size_t)wid * kWave * nf;
+            for (int i = lane; i < sh_total; i += kWave) dst[i] = src[i];
+        } else {
+            for (int i = lane; i < sh_total; i += kWave) dst[i] = 0.0f;
+        }
     }
 }
 
@@ -1659,25 +1760,19 @@ extern "C" size_t tsplat_raster_bwd_workspace_bytes(int32_t G, int32_t V) {
     return align_up((size_t)G * V * kGradRecFloats * sizeof(float), 256);
 }
 
-// Backward of tsplat_raster_fwd: zero fill of the gradient records, render_bwd_kernel,
-// preprocess_bwd_kernel. Every check comes before the first launch.
-extern "C" int tsplat_raster_bwd(const tsplat_raster_desc* d, const float* means, const float* cov,
-                                 const float* shs, const float* opacity, const float* viewmat,
-                                 const float* projmat, const float* campos, const float* tanfov,
-                                 const float* bg, const float* scene_scale, const float* out_color,
-                                 const float* grad_color, const int32_t* radii, void* fwd_workspace,
-                                 void* bwd_workspace, float* grad_means, float* grad_cov,
-                                 float* grad_shs, float* grad_opacity, void* stream_) {
-    if (!d || !means || !cov || !shs || !opacity || !viewmat || !projmat || !campos || !tanfov ||
-        !bg || !scene_scale || !out_color || !grad_color || !radii || !fwd_workspace || !bwd_workspace)
-        return TSPLAT_EINVAL;
-    if (!grad_means && !grad_cov && !grad_shs && !grad_opacity) return TSPLAT_EINVAL;
-    Params p;
-    if (!raster_params(d, -1, &p)) return TSPLAT_EINVAL;
-    p.diag = 0;  // the forward's timing diagnostics have no backward
-    hipStream_t stream = (hipStream_t)stream_;
-    Workspace ws = carve(fwd_workspace, p.G, p.V, p.T, p.capacity, nullptr);
-    float* grec = (float*)bwd_workspace;
+// The launch sequence of both backward entry points: zero fill of the gradient records,
+// render_bwd_kernel, preprocess_bwd_kernel, in the <kColor, kExtra> instantiations. <true, false> is
+// tsplat_raster_bwd's, and tsplat_raster_depth_bwd's with a colour gradient alone; <true, true> adds a
+// depth and / or alpha gradient to the colour's; <false, true> runs without a colour gradient.
+template <bool kColor, bool kExtra>
+static int raster_bwd_launch(Params p, const float* means, const float* cov, const float* shs,
+                             const float* opacity, const float* viewmat, const float* projmat,
+                             const float* campos, const float* tanfov, const float* scene_scale,
+                             const float* near, const float* far, const float* out_color,
+                             const float* grad_color, const float* out_depth, const float* grad_depth,
+                             const float* out_alpha, const float* grad_alpha, const int32_t* radii,
+                             Workspace ws, float* grec, float* grad_means, float* grad_cov,
+                             float* grad_shs, float* grad_opacity, hipStream_t stream) {
     TSPLAT_PROF_BEGIN(prof::kRasterBwdAll, stream);
     {
         const size_t n4 = (size_t)p.G * p.V * kGradRecFloats / 4;
@@ -1686,20 +1781,88 @@ extern "C" int tsplat_raster_bwd(const tsplat_raster_desc* d, const float* means
         TSPLAT_CHECK_LAUNCH();
     }
     TSPLAT_PROF_BEGIN(prof::kRasterBwdRender, stream);
-    hipLaunchKernelGGL(render_bwd_kernel, dim3(p.T, p.V), dim3(kTileThreads), 0, stream, p, out_color,
-                       grad_color, grec, ws);
+    hipLaunchKernelGGL((render_bwd_kernel<kColor, kExtra>), dim3(p.T, p.V), dim3(kTileThreads), 0, stream,
+                       p, out_color, grad_color, grec, ws, out_depth, grad_depth, out_alpha, grad_alpha);
     TSPLAT_PROF_END(prof::kRasterBwdRender, stream);
     TSPLAT_CHECK_LAUNCH();
     const int scenes = p.V / p.vps;
     TSPLAT_PROF_BEGIN(prof::kRasterBwdPreprocess, stream);
-    hipLaunchKernelGGL(preprocess_bwd_kernel, dim3(ceil_div(p.G, kPreBwdThreads), scenes),
+    hipLaunchKernelGGL((preprocess_bwd_kernel<kColor, kExtra>), dim3(ceil_div(p.G, kPreBwdThreads), scenes),
                        dim3(kPreBwdThreads), 0, stream, p, means, cov, shs, opacity, viewmat, projmat,
                        campos, tanfov, scene_scale, radii, (const float*)grec, grad_means, grad_cov,
-                       grad_shs, grad_opacity);
+                       grad_shs, grad_opacity, near, far);
     TSPLAT_PROF_END(prof::kRasterBwdPreprocess, stream);
     TSPLAT_PROF_END(prof::kRasterBwdAll, stream);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
+}
+
+// Argument checks shared by tsplat_raster_bwd (no depth or alpha gradient, depth_mode = 0) and
+// tsplat_raster_depth_bwd. Every check comes before the first launch.
+static int raster_bwd_run(const tsplat_raster_desc* d, const float* means, const float* cov,
+                          const float* shs, const float* opacity, const float* viewmat,
+                          const float* projmat, const float* campos, const float* tanfov,
+                          const float* bg, const float* scene_scale, const float* near,
+                          const float* far, int depth_mode, const float* out_color,
+                          const float* out_depth, const float* out_alpha, const float* grad_color,
+                          const float* grad_depth, const float* grad_alpha, const int32_t* radii,
+                          void* fwd_workspace, void* bwd_workspace, float* grad_means,
+                          float* grad_cov, float* grad_shs, float* grad_opacity, void* stream_) {
+    if (!d || !means || !cov || !shs || !opacity || !viewmat || !projmat || !campos || !tanfov ||
+        !bg || !scene_scale || !radii || !fwd_workspace || !bwd_workspace)
+        return TSPLAT_EINVAL;
+    if (!grad_color && !grad_depth && !grad_alpha) return TSPLAT_EINVAL;
+    if ((grad_color && !out_color) || (grad_depth && !out_depth) || (grad_alpha && !out_alpha))
+        return TSPLAT_EINVAL;
+    if (grad_depth && (!near || !far)) return TSPLAT_EINVAL;
+    if (depth_mode < 0 || depth_mode > 3) return TSPLAT_EINVAL;
+    if (!grad_means && !grad_cov && !grad_shs && !grad_opacity) return TSPLAT_EINVAL;
+    Params p;
+    if (!raster_params(d, grad_depth ? depth_mode : -1, &p)) return TSPLAT_EINVAL;
+    p.diag = 0;  // the forward's timing diagnostics have no backward
+    hipStream_t stream = (hipStream_t)stream_;
+    Workspace ws = carve(fwd_workspace, p.G, p.V, p.T, p.capacity, nullptr);
+    float* grec = (float*)bwd_workspace;
+#define TSPLAT_RASTER_BWD_ARGS                                                                      \
+    p, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, scene_scale, near, far,          \
+        out_color, grad_color, out_depth, grad_depth, out_alpha, grad_alpha, radii, ws, grec,       \
+        grad_means, grad_cov, grad_shs, grad_opacity, stream
+    if (!grad_depth && !grad_alpha) return raster_bwd_launch<true, false>(TSPLAT_RASTER_BWD_ARGS);
+    if (grad_color) return raster_bwd_launch<true, true>(TSPLAT_RASTER_BWD_ARGS);
+    return raster_bwd_launch<false, true>(TSPLAT_RASTER_BWD_ARGS);
+#undef TSPLAT_RASTER_BWD_ARGS
+}
+
+extern "C" int tsplat_raster_bwd(const tsplat_raster_desc* d, const float* means, const float* cov,
+                                 const float* shs, const float* opacity, const float* viewmat,
+                                 const float* projmat, const float* campos, const float* tanfov,
+                                 const float* bg, const float* scene_scale, const float* out_color,
+                                 const float* grad_color, const int32_t* radii, void* fwd_workspace,
+                                 void* bwd_workspace, float* grad_means, float* grad_cov,
+                                 float* grad_shs, float* grad_opacity, void* stream_) {
+    if (!out_color || !grad_color) return TSPLAT_EINVAL;
+    return raster_bwd_run(d, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale,
+                          nullptr, nullptr, 0, out_color, nullptr, nullptr, grad_color, nullptr, nullptr,
+                          radii, fwd_workspace, bwd_workspace, grad_means, grad_cov, grad_shs,
+                          grad_opacity, stream_);
+}
+
+extern "C" int tsplat_raster_depth_bwd(const tsplat_raster_desc* d, const float* means,
+                                       const float* cov, const float* shs, const float* opacity,
+                                       const float* viewmat, const float* projmat,
+                                       const float* campos, const float* tanfov, const float* bg,
+                                       const float* scene_scale, const float* near, const float* far,
+                                       int32_t depth_mode, const float* out_color,
+                                       const float* out_depth, const float* out_alpha,
+                                       const float* grad_color, const float* grad_depth,
+                                       const float* grad_alpha, const int32_t* radii,
+                                       void* fwd_workspace, void* bwd_workspace, float* grad_means,
+                                       float* grad_cov, float* grad_shs, float* grad_opacity,
+                                       void* stream_) {
+    return raster_bwd_run(d, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale,
+                          near, far, depth_mode, out_color, out_depth, out_alpha, grad_color, grad_depth,
+                          grad_alpha, radii, fwd_workspace, bwd_workspace, grad_means, grad_cov,
+                          grad_shs, grad_opacity, stream_);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ from ..types import Gaussians
 from .decoder import Decoder, DecoderOutput, DepthRenderingMode
 from .hip_splatting import (RasterCameras, RasterOutput, check_status, merge_view_groups, plan_view_groups,
                             prepare_cameras, rasterize, rasterize_differentiable, rasterize_with_depth,
-                            select_view_rows)
+                            rasterize_with_depth_differentiable, select_view_rows)
 
 
 @dataclass
@@ -34,9 +34,18 @@ class DecoderSplattingHIPCfg:
     # scene 16 keeps the worst-case instance keys at 4 GiB, half the MAX_CAPACITY cap
     views_per_call: int = 16
     # True: while grad is enabled and a Gaussian tensor requires grad, the colour comes from
-    # rasterize_differentiable (tsplat_raster_bwd as its backward) and carries a grad_fn. No depth
-    # gradients: depth_mode then raises NotImplementedError. False: the forward-only calls.
+    # rasterize_differentiable (tsplat_raster_bwd as its backward) and carries a grad_fn. Without
+    # differentiable_depth there are no depth gradients: depth_mode then raises NotImplementedError.
+    # False: the forward-only calls.
     differentiable: bool = False
+    # True (needs differentiable=True): under the same conditions forward(depth_mode=m) returns colour
+    # and depth from one rasterize_with_depth_differentiable call per view group (tsplat_raster_depth_bwd
+    # as its backward), both with a grad_fn, and render_depth() the depth-only call's.
+    differentiable_depth: bool = False
+
+    def __post_init__(self):
+        if self.differentiable_depth and not self.differentiable:
+            raise ValueError("DecoderSplattingHIPCfg: differentiable_depth=True needs differentiable=True")
 
 
 def _depth_fused() -> bool:
@@ -85,12 +94,15 @@ class DecoderSplattingHIP(Decoder[DecoderSplattingHIPCfg]):
     ) -> DecoderOutput:
         b, v, _, _ = extrinsics.shape
         if self._wants_grad(gaussians):
-            if depth_mode is not None:
+            if depth_mode is not None and not self.cfg.differentiable_depth:
                 raise NotImplementedError(
-                    "DecoderSplattingHIP(differentiable=True): gradients of the depth render are not built; "
-                    "call with depth_mode=None, or under torch.no_grad() for a depth without gradients")
-            rgb = self._render_differentiable(gaussians, extrinsics, intrinsics, near, far, image_shape)
-            return DecoderOutput(rearrange(rgb, "(b v) c h w -> b v c h w", b=b, v=v), None)
+                    "DecoderSplattingHIP(differentiable=True): gradients of the depth render need "
+                    "differentiable_depth=True; call with depth_mode=None, or under torch.no_grad() for a depth "
+                    "without gradients")
+            rgb, depth = self._render_differentiable(gaussians, extrinsics, intrinsics, near, far, image_shape,
+                                                     depth_mode)
+            return DecoderOutput(rearrange(rgb, "(b v) c h w -> b v c h w", b=b, v=v),
+                                 None if depth is None else rearrange(depth, "(b v) h w -> b v h w", b=b, v=v))
         fused = depth_mode is not None and _depth_fused()
         out = self._render(gaussians, extrinsics, intrinsics, near, far, image_shape,
                            depth_mode if fused else None, color=True)
@@ -108,32 +120,43 @@ class DecoderSplattingHIP(Decoder[DecoderSplattingHIPCfg]):
             t.requires_grad for t in (gaussians.means, gaussians.covariances, gaussians.harmonics,
                                       gaussians.opacities)))
 
-    def _render_differentiable(self, gaussians, extrinsics, intrinsics, near, far, image_shape) -> Tensor:
-        """The colour of _render() through rasterize_differentiable -> [(b v), 3, H, W] with a grad_fn.
-        More than 32 views per scene go group by group, each call on a workspace of its own; autograd
-        sums the groups' gradients."""
+    def _render_differentiable(self, gaussians, extrinsics, intrinsics, near, far, image_shape, depth_mode=None,
+                               color=True):
+        """The outputs of _render() with a grad_fn -> (colour [(b v), 3, H, W] or None, depth [(b v), H, W] or
+        None): rasterize_differentiable without a depth mode, else one rasterize_with_depth_differentiable call
+        for colour and depth together (color=False: the depth-only call). More than 32 views per scene go group
+        by group, each call on a workspace of its own; autograd sums the groups' gradients."""
         b, v, _, _ = extrinsics.shape
+        nr = rearrange(near, "b v -> (b v)")
+        fr = rearrange(far, "b v -> (b v)")
         cams = prepare_cameras(
             rearrange(extrinsics, "b v i j -> (b v) i j"),
             rearrange(intrinsics, "b v i j -> (b v) i j"),
-            rearrange(near, "b v -> (b v)"),
-            rearrange(far, "b v -> (b v)"),
+            nr,
+            fr,
             repeat(self.background_color, "c -> (b v) c", b=b, v=v),
         )
+        gauss = (gaussians.means, gaussians.covariances, gaussians.harmonics, gaussians.opacities)
         groups = plan_view_groups(b, v, self.cfg.views_per_call)
         single = len(groups) == 1
-        parts = []
+        colors, depths = [], []
         for views in groups:
-            c = cams if single else RasterCameras(*(select_view_rows(getattr(cams, f), b, v, views)
-                                                    for f in cams.__dataclass_fields__))
-            rgb, _ = rasterize_differentiable(
-                gaussians.means, gaussians.covariances, gaussians.harmonics, gaussians.opacities, c, image_shape,
-                views_per_scene=views.stop - views.start, sh_degree=self.cfg.sh_eval_degree,
-                check=self.cfg.check_overflow and single, debug=self.cfg.debug)
-            parts.append(rgb)
+            pick = lambda t: select_view_rows(t, b, v, views)
+            c = cams if single else RasterCameras(*(pick(getattr(cams, f)) for f in cams.__dataclass_fields__))
+            kw = dict(views_per_scene=views.stop - views.start, sh_degree=self.cfg.sh_eval_degree,
+                      check=self.cfg.check_overflow and single, debug=self.cfg.debug)
+            if depth_mode is None:
+                rgb, _ = rasterize_differentiable(*gauss, c, image_shape, **kw)
+                colors.append(rgb)
+            else:
+                out = rasterize_with_depth_differentiable(*gauss, c, image_shape, near=pick(nr), far=pick(fr),
+                                                          depth_mode=depth_mode, color=color, **kw)
+                colors.append(out.color)
+                depths.append(out.depth)
         if not single and self.cfg.check_overflow:
             check_status(gaussians.means.device)
-        return merge_view_groups(parts, b)
+        return (merge_view_groups(colors, b) if color else None,
+                merge_view_groups(depths, b) if depths else None)
 
     def _render(self, gaussians, extrinsics, intrinsics, near, far, image_shape, depth_mode, color):
         """One rasterizer call over the un-repeated Gaussians for all (b v) views: colour and / or
@@ -185,8 +208,14 @@ class DecoderSplattingHIP(Decoder[DecoderSplattingHIPCfg]):
         """The reference's depth render (render_depth_cuda, cuda_splatting.py:375-417): one
         depth-only rasterizer call for every view (the fake colour is computed per (view, Gaussian)
         in the preprocess kernel). TSPLAT_DEPTH_FUSED=0 keeps the two-pass route: the Gaussians
-        repeated per view and rendered with depth_fake_color as their colour."""
+        repeated per view and rendered with depth_fake_color as their colour. With both differentiable
+        flags on and grad wanted the depth carries a grad_fn (the depth-only differentiable call; the
+        environment switch governs the forward-only calls alone)."""
         b, v, _, _ = extrinsics.shape
+        if self.cfg.differentiable_depth and self._wants_grad(gaussians):
+            _, depth = self._render_differentiable(gaussians, extrinsics, intrinsics, near, far, image_shape, mode,
+                                                   color=False)
+            return rearrange(depth, "(b v) h w -> b v h w", b=b, v=v)
         if _depth_fused():
             out = self._render(gaussians, extrinsics, intrinsics, near, far, image_shape, mode, color=False)
             return rearrange(out.depth, "(b v) h w -> b v h w", b=b, v=v)

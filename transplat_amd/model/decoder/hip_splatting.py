@@ -162,9 +162,9 @@ def _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, v
     """The call behind rasterize() (extra None: tsplat_raster_fwd) and rasterize_with_depth()
     (extra = (near, far, mode id, color, depth, alpha): tsplat_raster_depth_fwd), with the same
     capacity, overflow and debug rules. keep: a list that receives what a backward needs (the
-    descriptor, the fp32 contiguous inputs and camera arrays the call read, its workspace); the call
-    then runs on a workspace tensor of its own instead of the device's shared one, which the next
-    call overwrites."""
+    descriptor, the fp32 contiguous inputs and camera arrays the call read, its workspace, its near and
+    far planes); the call then runs on a workspace tensor of its own instead of the device's shared
+    one, which the next call overwrites."""
     lib = _lib.load()
     s, g, _ = means.shape
     m = harmonics.shape[-1]
@@ -226,7 +226,7 @@ def _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, v
     if check:
         check_status(dev)
     if keep is not None:
-        keep[:] = [desc, (means, covariances, harmonics, opacities), cams, ws]
+        keep[:] = [desc, (means, covariances, harmonics, opacities), cams, ws, planes]
     return RasterOutput(color, radii, depth, alpha)
 
 
@@ -310,7 +310,7 @@ class _RasterizeFn(torch.autograd.Function):
         keep = []
         out = _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
                          capacity, check, debug, keep=keep)
-        desc, gauss, cams, ws = keep
+        desc, gauss, cams, ws, _ = keep
         ctx.desc, ctx.workspace = desc, ws
         ctx.dtypes = tuple(t.dtype for t in (means, covariances, harmonics, opacities))
         ctx.save_for_backward(*gauss, *cams, out.color, out.radii)
@@ -364,6 +364,96 @@ def rasterize_differentiable(
     """
     return _RasterizeFn.apply(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene,
                               sh_degree, capacity, check, debug)
+
+
+class _RasterizeDepthFn(torch.autograd.Function):
+    """rasterize_with_depth() with a backward: tsplat_raster_depth_fwd on a private workspace,
+    tsplat_raster_depth_bwd on what that call left in it. An output that was not asked for is None; an
+    output the loss does not use arrives in backward() as None and goes to the library as NULL."""
+
+    @staticmethod
+    def forward(ctx, means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
+                capacity, check, debug, near, far, mode, want_color, want_depth, want_alpha):
+        keep = []
+        out = _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
+                         capacity, check, debug, (near, far, mode, want_color, want_depth, want_alpha), keep=keep)
+        desc, gauss, cams, ws, planes = keep
+        ctx.desc, ctx.workspace, ctx.mode = desc, ws, mode
+        ctx.dtypes = tuple(t.dtype for t in (means, covariances, harmonics, opacities))
+        ctx.save_for_backward(*gauss, *cams, *planes, out.color, out.depth, out.alpha, out.radii)
+        ctx.mark_non_differentiable(out.radii)
+        ctx.set_materialize_grads(False)
+        return out.color, out.depth, out.alpha, out.radii
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_color, grad_depth, grad_alpha, _grad_radii):
+        lib = _lib.load()
+        t = ctx.saved_tensors
+        gauss, cams, planes, outs, radii = t[:4], t[4:10], t[10:12], t[12:15], t[15]
+        dev = radii.device
+        desc = ctx.desc
+        none = (None,) * 17
+        gin = [None if g is None or o is None else g.float().contiguous()
+               for g, o in zip((grad_color, grad_depth, grad_alpha), outs)]
+        grads = [torch.empty_like(x) if need else None for x, need in zip(gauss, ctx.needs_input_grad[:4])]
+        if all(g is None for g in grads) or all(g is None for g in gin):
+            return none
+        outs = [o if g is not None else None for o, g in zip(outs, gin)]
+        bws = torch.empty(int(lib.tsplat_raster_bwd_workspace_bytes(desc.num_gaussians, desc.num_views)),
+                          dtype=torch.uint8, device=dev)
+        p = _lib.ptr
+        rc = lib.tsplat_raster_depth_bwd(desc, *(p(x) for x in gauss), *(p(x) for x in cams), *(p(x) for x in planes),
+                                         ctx.mode, *(p(x) for x in outs), *(p(x) for x in gin), p(radii),
+                                         p(ctx.workspace), p(bws), *(p(g) for g in grads), _lib.stream_ptr(dev))
+        _lib.check(rc, "tsplat_raster_depth_bwd")
+        grads = [None if g is None else g.to(dt) for g, dt in zip(grads, ctx.dtypes)]
+        return (*grads, *none[4:])
+
+
+def rasterize_with_depth_differentiable(
+    means: Tensor,
+    covariances: Tensor,
+    harmonics: Tensor,
+    opacities: Tensor,
+    cameras: RasterCameras,
+    image_shape: tuple[int, int],
+    views_per_scene: int,
+    sh_degree: int | None = None,
+    capacity: int | None = None,
+    check: bool = True,
+    debug: bool = False,
+    *,
+    near: Tensor | None = None,
+    far: Tensor | None = None,
+    depth_mode: str | None = "depth",
+    color: bool = True,
+    alpha: bool = False,
+) -> RasterOutput:
+    """rasterize_with_depth() whose colour, depth and alpha are differentiable in the four Gaussian
+    tensors (the reference trains through render_depth_cuda's depth as through the colour).
+
+    Same arguments and the same RasterOutput, bit for bit. The forward runs on a workspace tensor of
+    its own, kept with the inputs, the camera arrays, near and far, the outputs and radii for the
+    backward (tsplat_raster_depth_bwd): one fused pass over colour, depth and alpha gradients, the
+    exact vector-Jacobian product with every discrete decision of the forward held fixed. The depth
+    value's own derivative reaches the means; covariances, opacities and harmonics get depth and alpha
+    gradient through the blend weights only. An output the loss does not use costs nothing. radii is
+    not differentiable; there is no double backward; cameras, background, near and far get no
+    gradient. The per-pixel sums are float atomic adds, so the last bits of a gradient can differ
+    between two runs.
+    """
+    if depth_mode is not None and depth_mode not in DEPTH_MODES:
+        raise ValueError(f"depth_mode {depth_mode!r}: expected one of {sorted(DEPTH_MODES)} or None")
+    want_depth = depth_mode is not None
+    if not (color or want_depth or alpha):
+        raise ValueError("rasterize_with_depth_differentiable: no output asked for")
+    if want_depth and (near is None or far is None):
+        raise ValueError("a depth render needs the views' near and far planes")
+    c, d, a, radii = _RasterizeDepthFn.apply(
+        means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree, capacity, check,
+        debug, near, far, DEPTH_MODES[depth_mode] if want_depth else 0, bool(color), want_depth, bool(alpha))
+    return RasterOutput(c, radii, d, a)
 
 
 MAX_VIEWS_PER_CALL = 32  # the rasterizer's per-scene view mask is 32 bits wide
