@@ -41,6 +41,30 @@ def case(name):
                 views=[1] if name == "B" else [0])
 
 
+ONE_TILE_HW = (8, 16)
+
+
+def one_tile_case(num_gaussians, scenes=2, vps=2, sh_coeffs=16, seed=0):
+    """A seeded scene rendered at H = 8, W = 16 with every Gaussian projected inside the image: ONE tile and two
+    live waves (the tile's lower 8 rows are outside the image), each adding at most once per (entry, field). So a
+    gradient record receives at most two float atomic adds onto its zero fill, and since IEEE addition of two
+    values is commutative the gradients repeat bit for bit between runs: the one place where they do (used by
+    tools/raster_bits.py and pinned by test_raster_grad.py). -> (g dict [S, G, ...], ext, K, near, far [S vps])"""
+    gen = torch.Generator().manual_seed(7000 + seed)
+    rand = lambda *shape: torch.rand(shape, generator=gen)
+    s, n, v = scenes, num_gaussians, scenes * vps
+    means = torch.stack(((rand(s, n) - 0.5) * 2.0, (rand(s, n) - 0.5) * 2.0, 3.5 + rand(s, n)), dim=-1)
+    a = (rand(s, n, 3, 3) - 0.5) * 0.3
+    cov = a @ a.transpose(-1, -2) + 0.002 * torch.eye(3)
+    sh = torch.randn((s, n, 3, sh_coeffs), generator=gen) * 0.3
+    op = 0.01 + rand(s, n) * min(0.6, 60.0 / n)
+    ext = torch.eye(4).repeat(v, 1, 1)
+    ext[:, 0, 3] = (rand(v) - 0.5) * 0.1  # the views differ by a small shift; scale s = 1 and 2 alternate
+    near = torch.tensor([1.0, 0.5]).repeat(v)[:v].contiguous()
+    g = {"means": means, "covariances": cov.contiguous(), "harmonics": sh, "opacities": op}
+    return g, ext, S.intrinsics(v), near, torch.full((v,), 100.0)
+
+
 def cameras(name, device="cpu"):
     c = case(name)
     d = lambda t: t.to(device)

@@ -25,7 +25,7 @@ import torch
 
 import raster_grad_cases as cases
 from transplat_amd.model.decoder.decoder_splatting_hip import DecoderSplattingHIP, DecoderSplattingHIPCfg
-from transplat_amd.model.decoder.hip_splatting import rasterize, rasterize_differentiable
+from transplat_amd.model.decoder.hip_splatting import prepare_cameras, rasterize, rasterize_differentiable
 from transplat_amd.model.types import Gaussians
 
 KINDS = ("means", "covariances", "harmonics", "opacities")
@@ -132,6 +132,30 @@ def test_rows_that_get_no_gradient_are_exactly_zero(device, name):
 def test_degree_four_fills_all_25_coefficients(device):
     gh = _run("tiny_deg4", device)[2]["harmonics"]
     assert gh.shape[-1] == 25 and float(gh[..., 16:].abs().max()) > 0
+
+
+# ------------------------------------------------------------------------------ one tile: repeatable bits
+@pytest.mark.gpu
+def test_one_tile_gradients_repeat_bit_for_bit(device):
+    """H = 8, W = 16, G = 600 (the counting sort), 1 scene x 2 views: one tile, two live waves, at most two atomic
+    adds per gradient record field (cases.one_tile_case), so two runs give the same bits. tools/raster_bits.py
+    compares two builds of the library on such scenes."""
+    g, ext, K, near, far = cases.one_tile_case(600, scenes=1, vps=2)
+    d = lambda x: x.to(device)
+    bg = torch.tensor(cases.BG).expand(2, 3).contiguous()
+    cams = prepare_cameras(d(ext), d(K), d(near), d(far), d(bg))
+    seed = torch.randn((2, 3, *cases.ONE_TILE_HW), generator=torch.Generator().manual_seed(9)).to(device)
+    runs = []
+    for _ in range(2):
+        t = {k: d(g[k]).clone().requires_grad_(True) for k in KINDS}
+        color, radii = rasterize_differentiable(t["means"], t["covariances"], t["harmonics"], t["opacities"], cams,
+                                                cases.ONE_TILE_HW, 2)
+        color.backward(seed)
+        torch.cuda.synchronize()
+        assert int((radii > 0).sum()) == radii.numel()
+        runs.append([t[k].grad for k in KINDS])
+    for k, a, b in zip(KINDS, *runs):
+        assert float(a.abs().max()) > 0 and torch.equal(a, b), k
 
 
 # ------------------------------------------------------------------------------ 4: workspace independence

@@ -1,7 +1,8 @@
 // Gaussian-splat rasterizer for gfx950 (MI355X): the forward, and the backward of its colour, depth and
 // alpha renders in the Gaussians (tsplat_raster_bwd, tsplat_raster_depth_bwd: render_bwd_kernel and
-// preprocess_bwd_kernel, after the forward kernels below, which they leave as they are and whose steps
-// they reuse).
+// preprocess_bwd_kernel). Forward and backward run the same steps, each defined once: the sorts in
+// raster_sort.h; projection and EWA covariance, SH basis, depth value, tile prologue, chunk walk and blend
+// decision in raster_steps.h.
 //
 // Algorithm = the graphdeco forward rasterizer behind `GaussianRasterizer` as called by
 // `render_cuda` (reference src/model/decoder/cuda_splatting.py:56-136): preprocess (cull at
@@ -48,7 +49,6 @@ constexpr int kSortCap = 4096;            // tile lists up to this length are so
 constexpr int kPreThreads = 256;
 constexpr size_t kMaxLdsBytes = 160 * 1024;  // gfx950 LDS per workgroup
 constexpr int kRecBytes = 64;             // per-(view, Gaussian) record (Workspace::rec)
-constexpr int kGeomFields = 6;            // x, y, conic a b c, opacity (then r g b, then the depth value)
 
 __constant__ float kSH_C0 = 0.28209479177387814f;
 __constant__ float kSH_C1 = 0.4886025119029199f;
@@ -108,25 +108,10 @@ struct Params {
     int depth_mode;  // preprocess: -1 no depth value; 0 depth, 1 disparity, 2 relative disparity, 3 log
 };
 
-// The value the depth output blends for one (view, Gaussian): the reference renders depth as a
-// colour (render_depth_cuda, cuda_splatting.py:375-417): fake colour f of the UNSCALED camera-space
-// depth z (:388-400) as the degree-0 SH coefficient, so d = max(C0 f + 0.5, 0). z = vz / s undoes
-// the scale-invariant rendering (vz is the depth of the scaled scene). "log" keeps the reference's
-// minimum(near).maximum(far) order, which gives log(far) for every Gaussian. IEEE division and logf.
-__device__ __forceinline__ float depth_value(int mode, float vz, float s, float near, float far) {
-    const float z = vz / s;
-    float f = z;
-    if (mode == 1) {
-        f = 1.0f / z;
-    } else if (mode == 2) {
-        const float eps = 1e-10f;  // depth_to_relative_disparity (matching/conversions.py:18-28)
-        const float disp_near = 1.0f / (near + eps), disp_far = 1.0f / (far + eps);
-        f = 1.0f - (1.0f / (z + eps) - disp_far) / (disp_near - disp_far + eps);
-    } else if (mode == 3) {
-        f = logf(fmaxf(fminf(z, near), far));
-    }
-    return fmaxf(kSH_C0 * f + 0.5f, 0.0f);
-}
+// The tile-list sorts, and the steps the forward kernels and their backward share, one definition each.
+// Sections of this translation unit (contraction stays off in them), not headers for anyone else.
+#include "raster_sort.h"
+#include "raster_steps.h"
 
 __device__ __forceinline__ void get_rect(float px, float py, int r, int tx, int ty, int& x0,
                                          int& y0, int& x1, int& y1) {
@@ -135,48 +120,6 @@ __device__ __forceinline__ void get_rect(float px, float py, int r, int tx, int 
     y0 = min(ty, max(0, (int)((py - (float)r) / (float)kTile)));
     x1 = min(tx, max(0, (int)((px + (float)r + (float)(kTile - 1)) / (float)kTile)));
     y1 = min(ty, max(0, (int)((py + (float)r + (float)(kTile - 1)) / (float)kTile)));
-}
-
-__device__ __forceinline__ void sh_to_rgb(const float* __restrict__ sh, int M, int deg, float dx,
-                                          float dy, float dz, float out[3]) {
-    // sh is colour-major [3][M]; coefficient k of channel c is sh[c*M + k]
-    float len = sqrtf(dx * dx + dy * dy + dz * dz);
-    float x = dx / len, y = dy / len, z = dz / len;
-    float xx = x * x, yy = y * y, zz = z * z;
-    float xy = x * y, yz = y * z, xz = x * z;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* s = sh + c * M;
-        float r = kSH_C0 * s[0];
-        if (deg > 0) {
-            r = r - kSH_C1 * y * s[1] + kSH_C1 * z * s[2] - kSH_C1 * x * s[3];
-            if (deg > 1) {
-                r = r + kSH_C2[0] * xy * s[4] + kSH_C2[1] * yz * s[5] +
-                    kSH_C2[2] * (2.0f * zz - xx - yy) * s[6] + kSH_C2[3] * xz * s[7] +
-                    kSH_C2[4] * (xx - yy) * s[8];
-                if (deg > 2) {
-                    r = r + kSH_C3[0] * y * (3.0f * xx - yy) * s[9] + kSH_C3[1] * xy * z * s[10] +
-                        kSH_C3[2] * y * (4.0f * zz - xx - yy) * s[11] +
-                        kSH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * s[12] +
-                        kSH_C3[4] * x * (4.0f * zz - xx - yy) * s[13] +
-                        kSH_C3[5] * z * (xx - yy) * s[14] + kSH_C3[6] * x * (xx - 3.0f * yy) * s[15];
-                    if (deg > 3) {
-                        r = r + kSH_C4[0] * xy * (xx - yy) * s[16] +
-                            kSH_C4[1] * yz * (3.0f * xx - yy) * s[17] +
-                            kSH_C4[2] * xy * (7.0f * zz - 1.0f) * s[18] +
-                            kSH_C4[3] * yz * (7.0f * zz - 3.0f) * s[19] +
-                            kSH_C4[4] * (zz * (35.0f * zz - 30.0f) + 3.0f) * s[20] +
-                            kSH_C4[5] * xz * (7.0f * zz - 3.0f) * s[21] +
-                            kSH_C4[6] * (xx - yy) * (7.0f * zz - 1.0f) * s[22] +
-                            kSH_C4[7] * xz * (xx - 3.0f * yy) * s[23] +
-                            kSH_C4[8] * (xx * (xx - 3.0f * yy) - yy * (3.0f * xx - yy)) * s[24];
-                    }
-                }
-            }
-        }
-        r = r + 0.5f;
-        out[c] = fmaxf(r, 0.0f);
-    }
 }
 
 // --- K0: clear the per-tile counters (a kernel, not hipMemsetAsync: a memset captured into a
@@ -264,58 +207,25 @@ preprocess_kernel(Params p, const float* __restrict__ means, const float* __rest
             const float* pm = projmat + 16 * v;
             const float s = scene_scale[2 * v], s2 = scene_scale[2 * v + 1];
             int radius = 0;
-            // scale-invariant rendering: means * s, cov * s^2 (cuda_splatting.py:73-80)
-            const float mx = m0 * s, my = m1 * s, mz = m2 * s;
-            // in_frustum: view-space depth test (auxiliary.h in_frustum)
-            const float vx = vm[0] * mx + vm[4] * my + vm[8] * mz + vm[12];
-            const float vy = vm[1] * mx + vm[5] * my + vm[9] * mz + vm[13];
-            const float vz = vm[2] * mx + vm[6] * my + vm[10] * mz + vm[14];
+            const ViewPoint q = view_point(m0, m1, m2, s, vm);
+            const float vz = q.vz;
             bool ok = vz > 0.2f;
             float px = 0.f, py = 0.f, conic_a = 0.f, conic_b = 0.f, conic_c = 0.f;
             float cov_a = 0.f, cov_c = 0.f;
             int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
             if (ok) {
-                const float hx = pm[0] * mx + pm[4] * my + pm[8] * mz + pm[12];
-                const float hy = pm[1] * mx + pm[5] * my + pm[9] * mz + pm[13];
-                const float hw = pm[3] * mx + pm[7] * my + pm[11] * mz + pm[15];
-                const float pw = 1.0f / (hw + 0.0000001f);
-                const float ndc_x = hx * pw, ndc_y = hy * pw;
-                const float c00 = k00 * s2, c01 = k01 * s2, c02 = k02 * s2;
-                const float c11 = k11 * s2, c12 = k12 * s2, c22 = k22 * s2;
-                // EWA splatting (computeCov2D)
-                const float tfx = tanfov[2 * v], tfy = tanfov[2 * v + 1];
-                const float fx = (float)p.W / (2.0f * tfx), fy = (float)p.H / (2.0f * tfy);
-                const float limx = 1.3f * tfx, limy = 1.3f * tfy;
-                const float tz = vz;
-                const float tx = fminf(limx, fmaxf(-limx, vx / tz)) * tz;
-                const float ty = fminf(limy, fmaxf(-limy, vy / tz)) * tz;
-                const float j00 = fx / tz, j02 = -(fx * tx) / (tz * tz);
-                const float j11 = fy / tz, j12 = -(fy * ty) / (tz * tz);
-                // M = J * R_w2c, R[r][c] = vm[c*4 + r]
-                const float n00 = j00 * vm[0] + j02 * vm[2];
-                const float n01 = j00 * vm[4] + j02 * vm[6];
-                const float n02 = j00 * vm[8] + j02 * vm[10];
-                const float n10 = j11 * vm[1] + j12 * vm[2];
-                const float n11 = j11 * vm[5] + j12 * vm[6];
-                const float n12 = j11 * vm[9] + j12 * vm[10];
-                const float u00 = n00 * c00 + n01 * c01 + n02 * c02;
-                const float u01 = n00 * c01 + n01 * c11 + n02 * c12;
-                const float u02 = n00 * c02 + n01 * c12 + n02 * c22;
-                const float u10 = n10 * c00 + n11 * c01 + n12 * c02;
-                const float u11 = n10 * c01 + n11 * c11 + n12 * c12;
-                const float u12 = n10 * c02 + n11 * c12 + n12 * c22;
-                const float a = u00 * n00 + u01 * n01 + u02 * n02 + 0.3f;
-                const float b = u00 * n10 + u01 * n11 + u02 * n12;
-                const float c = u10 * n10 + u11 * n11 + u12 * n12 + 0.3f;
-                const float det = a * c - b * b;
+                const Projection pr = project(q, k00, k01, k02, k11, k12, k22, s2, vm, pm, tanfov[2 * v],
+                                              tanfov[2 * v + 1], p.W, p.H);
+                const float ndc_x = pr.hx * pr.pw, ndc_y = pr.hy * pr.pw;
+                const float a = pr.a, c = pr.c, det = pr.det;
                 cov_a = a;
                 cov_c = c;
                 ok = det != 0.0f;
                 if (ok) {
-                    const float det_inv = 1.0f / det;
-                    conic_a = c * det_inv;
-                    conic_b = -b * det_inv;
-                    conic_c = a * det_inv;
+                    const Conic co = conic_of(pr);
+                    conic_a = co.a;
+                    conic_b = co.b;
+                    conic_c = co.c;
                     const float mid = 0.5f * (a + c);
                     const float l1 = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
                     const float l2 = mid - sqrtf(fmaxf(0.1f, mid * mid - det));
@@ -349,7 +259,7 @@ preprocess_kernel(Params p, const float* __restrict__ means, const float* __rest
                 // cull threshold in the same log2 units as the stored conic: 2 log2(255 o), + margins
                 float d = 0.0f;
                 if constexpr (kExtra)
-                    if (p.depth_mode >= 0) d = depth_value(p.depth_mode, vz, s, near[v], far[v]);
+                    if (p.depth_mode >= 0) d = depth_value(p.depth_mode, vz, s, near[v], far[v]).d;
                 rec[3] = make_float4(2.0f * __log2f(255.0f * o) * 1.001f + 1.5e-3f,
                                      -conic_b * __builtin_amdgcn_rcpf(conic_a),
                                      -conic_b * __builtin_amdgcn_rcpf(conic_c), d);
@@ -386,12 +296,11 @@ preprocess_kernel(Params p, const float* __restrict__ means, const float* __rest
         const int v = scene * p.vps + vv;
         const float* vm = viewmat + 16 * v;
         const float s = scene_scale[2 * v];
-        const float mx = m0 * s, my = m1 * s, mz = m2 * s;
-        const float vz = vm[2] * mx + vm[6] * my + vm[10] * mz + vm[14];  // as in pass 1, bit for bit
+        const ViewPoint q = view_point(m0, m1, m2, s, vm);  // pass 1's, bit for bit: q.vz is the sort key
         float rgb[3] = {0.5f, 0.5f, 0.5f};
         const float* cp = campos + 3 * v;
-        if (!no_sh) sh_to_rgb(my_sh, p.M, p.deg, mx - cp[0], my - cp[1], mz - cp[2], rgb);
-        ws.rec[4 * ((size_t)v * p.G + g) + 2] = make_float4(rgb[0], rgb[1], rgb[2], vz);
+        if (!no_sh) sh_to_rgb(my_sh, p.M, p.deg, sh_dir(q.mx - cp[0], q.my - cp[1], q.mz - cp[2]), rgb);
+        ws.rec[4 * ((size_t)v * p.G + g) + 2] = make_float4(rgb[0], rgb[1], rgb[2], q.vz);
     }
 }
 
@@ -488,279 +397,6 @@ scatter_kernel(Params p, const int32_t* __restrict__ radii, Workspace ws, int32_
     }
 }
 
-// Bitonic sort (all-ascending "mirror" network) of n keys held in `buf`, virtual length
-// next_pow2(n); positions >= n behave as +inf and never move, so no padding is written.
-template <typename Ptr>
-__device__ __forceinline__ void bitonic_sort(Ptr buf, int n) {
-    int logP = 0;
-    while ((1 << logP) < n) ++logP;
-    const int half = (1 << logP) >> 1;
-    for (int lk = 1; lk <= logP; ++lk) {
-        for (int lj = lk - 1; lj >= 0; --lj) {
-            const int j = 1 << lj;
-            for (int i = threadIdx.x; i < half; i += kTileThreads) {
-                const int blk = i >> lj, q = i & (j - 1);
-                int a, b;
-                if (lj == lk - 1) {  // first step of a merge: compare mirrored pairs
-                    a = (blk << (lj + 1)) + q;
-                    b = (blk << (lj + 1)) + (2 * j - 1 - q);
-                } else {
-                    a = (blk << (lj + 1)) + q;
-                    b = a + j;
-                }
-                if (b < n) {
-                    const uint64_t ka = buf[a], kb = buf[b];
-                    if (ka > kb) {
-                        buf[a] = kb;
-                        buf[b] = ka;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// Register-resident bitonic sort of the n <= kSortCap keys in `buf` (LDS), ascending. Thread t
-// holds positions t*E .. t*E + E - 1 (E = P / 256 for P = next_pow2(n) >= 256; positions >= n
-// are +inf). The network is unrolled at compile time (template over log2 P), so every register
-// index is static: stages whose partner distance j is below E run in registers, j < 64 E
-// exchange with the partner lane by shuffles, and only j >= 64 E (at most 3 stages for 4096
-// keys) go through LDS with barriers -- instead of one barrier-separated LDS pass per stage.
-template <int E>
-__device__ __forceinline__ void cas_step(uint64_t (&v)[E], int t, int k, int j, uint64_t* buf) {
-    if (j < E) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int f = e ^ j;
-            if (f > e) {
-                const bool asc = (((t * E + e) & k) == 0);
-                const uint64_t a = v[e], b = v[f];
-                const bool sw = asc ? (a > b) : (a < b);
-                v[e] = sw ? b : a;
-                v[f] = sw ? a : b;
-            }
-        }
-    } else if (j < 64 * E) {
-        const int lane_xor = j / E;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int i = t * E + e;
-            const uint32_t lo = __shfl_xor((uint32_t)v[e], lane_xor);
-            const uint32_t hi = __shfl_xor((uint32_t)(v[e] >> 32), lane_xor);
-            const uint64_t other = ((uint64_t)hi << 32) | lo;
-            const bool take_min = ((i & j) == 0) == ((i & k) == 0);
-            const uint64_t mn = v[e] < other ? v[e] : other, mx = v[e] < other ? other : v[e];
-            v[e] = take_min ? mn : mx;
-        }
-    } else {
-        __syncthreads();  // previous readers of buf are done
-#pragma unroll
-        for (int e = 0; e < E; ++e) buf[t * E + e] = v[e];
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int i = t * E + e;
-            const uint64_t other = buf[i ^ j];
-            const bool take_min = ((i & j) == 0) == ((i & k) == 0);
-            const uint64_t mn = v[e] < other ? v[e] : other, mx = v[e] < other ? other : v[e];
-            v[e] = take_min ? mn : mx;
-        }
-    }
-}
-
-template <int LOGP>
-__device__ __forceinline__ void bitonic_sort_regs_p(uint64_t* buf, int n) {
-    constexpr int P = 1 << LOGP;
-    constexpr int E = P / kTileThreads;
-    const int t = threadIdx.x;
-    uint64_t v[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = t * E + e;
-        v[e] = i < n ? buf[i] : ~0ull;
-    }
-#pragma unroll
-    for (int lk = 1; lk <= LOGP; ++lk)
-#pragma unroll
-        for (int lj = lk - 1; lj >= 0; --lj) cas_step<E>(v, t, 1 << lk, 1 << lj, buf);
-    __syncthreads();
-    // sorted gaussian ids (the keys' low words) as a uint32 list at the start of buf
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = t * E + e;
-        if (i < n) reinterpret_cast<uint32_t*>(buf)[i] = (uint32_t)v[e];
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void bitonic_sort_regs(uint64_t* buf, int n) {
-    if (n <= 256) bitonic_sort_regs_p<8>(buf, n);
-    else if (n <= 512) bitonic_sort_regs_p<9>(buf, n);
-    else if (n <= 1024) bitonic_sort_regs_p<10>(buf, n);
-    else if (n <= 2048) bitonic_sort_regs_p<11>(buf, n);
-    else bitonic_sort_regs_p<12>(buf, n);
-}
-
-// Counting sort of a tile list on its depth bits, for lists longer than one bitonic register pass.
-// Depths are positive floats, so their bit patterns order like the depths. bucket(d) = (d - dmin)
-// >> s, with s the smallest shift that maps the tile's depth-bit range onto <= kBuckets buckets:
-// monotone in depth, so concatenating the buckets in order is a depth order. Each thread holds E
-// keys in registers (key i = t + 256 e, one coalesced load batch); the keys are scattered to their
-// bucket's slice of `out` by LDS atomics, and a key's final slot in its bucket -- almost always 0-2
-// keys -- is its bucket start + the number of bucket members with a smaller (depth bits << 32 | id)
-// key, so the result is exactly the ascending key order the bitonic network produces. A tile
-// whose depths cluster (some bucket holds more than kFixMax keys) returns false before anything
-// is written and takes the bitonic path.
-constexpr int kBuckets = 2048;
-constexpr int kBucketBits = 11;
-constexpr int kFixMax = 32;
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = min(x, (uint32_t)__shfl_xor((int)x, o));
-    return x;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = max(x, (uint32_t)__shfl_xor((int)x, o));
-    return x;
-}
-
-template <int E>
-__device__ bool counting_sort_e(const uint64_t* __restrict__ keys, int n, uint64_t* out, uint32_t* cnt,
-                                uint32_t* red) {
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
-    constexpr int kPer = kBuckets / kTileThreads;  // consecutive buckets per thread in the scan
-    uint64_t k[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = tid + e * kTileThreads;
-        k[e] = i < n ? keys[i] : ~0ull;
-    }
-    for (int i = tid; i < kBuckets; i += kTileThreads) cnt[i] = 0;
-    if (tid == 0) {
-        red[0] = 0xffffffffu;
-        red[1] = 0u;
-        red[2] = 0u;
-    }
-    uint32_t lo = 0xffffffffu, hi = 0u;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        if (tid + e * kTileThreads < n) {
-            const uint32_t d = (uint32_t)(k[e] >> 32);
-            lo = min(lo, d);
-            hi = max(hi, d);
-        }
-    }
-    lo = wave_min_u32(lo);
-    hi = wave_max_u32(hi);
-    __syncthreads();  // red and cnt initialised
-    if (lane == 0) {
-        atomicMin(&red[0], lo);
-        atomicMax(&red[1], hi);
-    }
-    __syncthreads();
-    const uint32_t dmin = red[0], range = red[1] - dmin;
-    const int bits = range ? 32 - __clz(range) : 0;
-    const int sh = bits > kBucketBits ? bits - kBucketBits : 0;
-    uint32_t bk[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const bool valid = tid + e * kTileThreads < n;
-        bk[e] = valid ? ((uint32_t)(k[e] >> 32) - dmin) >> sh : 0u;
-        if (valid) atomicAdd(&cnt[bk[e]], 1u);
-    }
-    __syncthreads();
-    // exclusive scan of the bucket counts (thread t owns buckets kPer t .. kPer t + kPer - 1) and
-    // the largest bucket
-    uint32_t c[kPer];
-    uint32_t sum = 0, mx = 0;
-#pragma unroll
-    for (int e = 0; e < kPer; ++e) {
-        c[e] = cnt[tid * kPer + e];
-        sum += c[e];
-        mx = max(mx, c[e]);
-    }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t y = __shfl_up(incl, d, kWave);
-        if (lane >= d) incl += y;
-    }
-    mx = wave_max_u32(mx);
-    __shared__ uint32_t wtot[kTileThreads / kWave];
-    if (lane == kWave - 1) wtot[wid] = incl;
-    if (lane == 0) atomicMax(&red[2], mx);
-    __syncthreads();
-    if (red[2] > (uint32_t)kFixMax) return false;  // uniform: every thread read the same value
-    uint32_t run = incl - sum;
-    for (int w = 0; w < wid; ++w) run += wtot[w];
-#pragma unroll
-    for (int e = 0; e < kPer; ++e) {
-        cnt[tid * kPer + e] = run;
-        run += c[e];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-        if (tid + e * kTileThreads < n) out[atomicAdd(&cnt[bk[e]], 1u)] = k[e];
-    __syncthreads();  // cnt[b] is now the end of bucket b
-    uint32_t slot[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const uint32_t b = tid + e * kTileThreads < n ? bk[e] : 0u;  // padding keys: any bucket
-        const uint32_t s0 = b ? cnt[b - 1] : 0u, s1 = cnt[b];
-        uint32_t r = 0;
-        for (uint32_t j = s0; j < s1; ++j) r += out[j] < k[e];
-        slot[e] = s0 + r;
-    }
-    __syncthreads();
-    // every read of the 64-bit keys is done: leave the sorted gaussian ids (the keys' low words)
-    // as a uint32 list at the start of the same LDS region
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-        if (tid + e * kTileThreads < n) reinterpret_cast<uint32_t*>(out)[slot[e]] = (uint32_t)k[e];
-    __syncthreads();
-    return true;
-}
-
-__device__ __forceinline__ bool counting_sort(const uint64_t* __restrict__ keys, int n, uint64_t* out,
-                                              uint32_t* cnt, uint32_t* red) {
-    if (n <= 2 * kTileThreads) return counting_sort_e<2>(keys, n, out, cnt, red);
-    if (n <= 4 * kTileThreads) return counting_sort_e<4>(keys, n, out, cnt, red);
-    if (n <= 8 * kTileThreads) return counting_sort_e<8>(keys, n, out, cnt, red);
-    return counting_sort_e<16>(keys, n, out, cnt, red);
-}
-
-// Exact culling of one Gaussian against a pixel block: does the alpha >= 1/255 ellipse
-// {d : a dx^2 + 2 b dx dy + c dy^2 <= q}, q = 2 ln(255 o), meet the rectangle of pixel centres
-// [x0, x1] x [y0, y1]? The minimum of the (convex) quadratic over the rectangle is 0 when the
-// centre is inside, else it lies on an edge (1-D minimisation, clamped). Conservative margins
-// (relative 1e-3 on q plus 1e-3 absolute) keep every contributing Gaussian (the blend's float
-// arithmetic differs from this by a few ulps), so images are unchanged; culls the corners the
-// axis-aligned box test keeps for rotated / elongated splats.
-__device__ __forceinline__ bool ellipse_meets_block(float mx, float my, float4 co, float4 cull, float x0, float x1,
-                                                    float y0, float y1) {
-    // co = log2(e) (-a/2, -b, -c/2) and o as stored; cull = (2 log2(255 o) * 1.001 + 1.5e-3, -b/a,
-    // -b/c): Q and q both carry the log2(e) factor,
-    // precomputed per (view, Gaussian) by the preprocess kernel (approximate reciprocals: a clamped
-    // minimiser off by an ulp raises Q by O(ulp^2), far inside the margins above)
-    const float a = -2.0f * co.x, b = -co.y, c = -2.0f * co.z;
-    const float q = cull.x, kba = cull.y, kbc = cull.z;
-    const float X0 = x0 - mx, X1 = x1 - mx, Y0 = y0 - my, Y1 = y1 - my;
-    if (X0 <= 0.f && X1 >= 0.f && Y0 <= 0.f && Y1 >= 0.f) return true;
-    if (!(a > 0.f && c > 0.f)) return true;  // degenerate: keep (the box test decided)
-    // Q(dx, dy) = dx (a dx + 2 b dy) + c dy^2; along x = X the minimiser is dy = X (-b / c)
-    const float b2 = 2.0f * b;
-    auto Qf = [&](float dx, float dy) { return fmaf(dx, fmaf(b2, dy, a * dx), c * dy * dy); };
-    const float qx0 = Qf(X0, fminf(fmaxf(X0 * kbc, Y0), Y1));
-    const float qx1 = Qf(X1, fminf(fmaxf(X1 * kbc, Y0), Y1));
-    const float qy0 = Qf(fminf(fmaxf(Y0 * kba, X0), X1), Y0);
-    const float qy1 = Qf(fminf(fmaxf(Y1 * kba, X0), X1), Y1);
-    return fminf(fminf(qx0, qx1), fminf(qy0, qy1)) <= q;
-}
-
 // --- K4: per-tile depth sort + front-to-back alpha blending ---------------------------------
 // One workgroup per (tile, view); the tile list is sorted in LDS (counting sort, or the bitonic
 // network), then each wave owns
@@ -781,194 +417,61 @@ template <bool kColor, bool kExtra>
 __global__ void __launch_bounds__(kTileThreads)
 render_kernel(Params p, const float* __restrict__ bg, float* __restrict__ out_color,
               float* __restrict__ out_depth, float* __restrict__ out_alpha, Workspace ws) {
-    constexpr int kRgbField = kGeomFields;                          // r g b (kColor)
-    constexpr int kDepthField = kGeomFields + (kColor ? 3 : 0);     // d (kExtra)
-    constexpr int kRecFields = kDepthField + (kExtra ? 1 : 0);      // 9, 10 or 7
+    using L = RecLayout<kColor, kExtra, false>;  // 9, 10 or 7 fields
     __shared__ uint64_t skeys[kSortCap];
     __shared__ uint32_t s_cnt[kBuckets];
     __shared__ uint32_t s_red[4];
     // per-wave compacted records of the current 64-entry chunk (waves progress independently),
     // field-major: one ds_read_b128 of a field gives 4 consecutive entries = 2 packed pairs
-    __shared__ __attribute__((aligned(16))) float s_rec[kTileThreads / kWave][kRecFields][kWave];
+    __shared__ __attribute__((aligned(16))) float s_rec[kTileThreads / kWave][L::kRecFields][kWave];
 
     const int v = blockIdx.y;
-    // Workgroup (tile, v) and (tile, v') share an XCD and a CU slot in dispatch order, and a
-    // tile's cost is similar across the target views of a scene (central tiles are the heavy
-    // ones), so without the per-view rotation every CU would get the same tile three times.
-    // Rotating by whole tile rows keeps each XCD's band of rows contiguous (L2 reuse of records).
-    int tile = xcd_remap(blockIdx.x, gridDim.x) + v * p.view_rot;
-    tile %= p.T;
     const uint64_t t_begin = p.diag == 5 ? __builtin_amdgcn_s_memtime() : 0;
     int d_entries = 0, d_chunks = 0;  // diag 5 only
-    const int tx = tile % p.tiles_x, ty = tile / p.tiles_x;
-    const int t_idx = v * p.T + tile;
-    uint32_t start = ws.offsets[t_idx];
-    uint32_t end = ws.offsets[t_idx + 1];
-    if (end > (uint32_t)p.capacity) end = (uint32_t)p.capacity;
-    if (start > end) start = end;
-    const int n = (int)(end - start);
+    TileList tl;
+    if (!tile_prologue(p, ws, v, {skeys, s_cnt, s_red}, tl)) return;
 
-    uint64_t* gkeys = ws.keys + start;
-    const bool in_lds = n <= kSortCap;
-    if (in_lds) {
-        // lists longer than one register pass: counting sort on the depth bits (falls back to the
-        // bitonic network when the tile's depths cluster)
-        const bool try_count = p.count_sort && n > kTileThreads && p.diag != 3;
-        const bool counted = try_count && counting_sort(gkeys, n, skeys, s_cnt, s_red);
-        if (!counted) {
-            for (int i = threadIdx.x; i < n; i += kTileThreads) skeys[i] = gkeys[i];
-            __syncthreads();
-            if (p.diag == 3) return;  // key load only
-            bitonic_sort_regs(skeys, n);
-        }
-        if (p.diag == 2) return;  // key load + sort
-    } else {
-        bitonic_sort(gkeys, n);  // rare: very long tile list, sorted in place in global memory
-    }
-    // no workgroup barrier below this point: each wave walks the sorted list on its own
-
-    const int wid = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    const int lx = (wid & 1) * 8 + (lane & 7), ly = (wid >> 1) * 8 + (lane >> 3);
-    const int pxi = tx * kTile + lx, pyi = ty * kTile + ly;
-    const float wx0 = (float)(tx * kTile + (wid & 1) * 8), wx1 = wx0 + 7.0f;
-    const float wy0 = (float)(ty * kTile + (wid >> 1) * 8), wy1 = wy0 + 7.0f;
-    const bool inside = pxi < p.W && pyi < p.H;
-    bool done = !inside;
-    const float pfx = (float)pxi, pfy = (float)pyi;
+    const WavePixel wp = wave_pixel(p, tl.tile);
+    bool done = !wp.inside;
     float T = 1.0f;
     float C0 = 0.f, C1 = 0.f, C2 = 0.f;
     float D = 0.f;  // kExtra: sum of d w
-    const size_t vbase = (size_t)v * p.G;
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    float (*w_rec)[kWave] = s_rec[wid];
+    float (*w_rec)[kWave] = s_rec[wp.wid];
 
-    // power = -0.5 (a dx^2 + c dy^2) - b dx dy, alpha = min(0.99, o e^power), T' = T (1 - alpha),
-    // C += rgb alpha T (reference renderCUDA), here with the power scaled by log2(e) so that
-    // e^power = 2^power2 is one v_exp_f32, and the quadratic in Horner form (2 FMAs + 3 multiplies).
-    // Scalar fp32 on purpose: v_pk_fma_f32 has the same FLOP rate as v_fma_f32 (twice the cycles),
-    // and packing the operands costs register moves.
-    auto blend = [&](float x, float y, float ca, float cb, float cc, float o, float r, float g, float bl,
+    // C += rgb w and D += d w with the entry's weight w = alpha T of blend_step()
+    auto blend = [&](auto, float x, float y, float ca, float cb, float cc, float o, float r, float g, float bl,
                      float d) {
-        // (ca, cb, cc) = log2(e) (-a/2, -b, -c/2): power2 = dy (cc dy + cb dx) + (ca dx) dx
-        const float dx = x - pfx, dy = y - pfy;
-        const float power2 = fmaf(dy, fmaf(cc, dy, cb * dx), (ca * dx) * dx);
-        const float alpha = fminf(0.99f, o * __builtin_amdgcn_exp2f(power2));
-        const float test_T = fmaf(-alpha, T, T);
-        // reference order: skip power > 0, skip alpha < 1/255, stop if test_T < 1e-4
-        const bool contrib = !done && !(power2 > 0.0f) && !(alpha < 1.0f / 255.0f);
-        const bool stop = contrib && (test_T < 0.0001f);
-        const bool acc = contrib && !stop;
-        const float w = acc ? alpha * T : 0.0f;  // a skipped entry adds c * 0 = +0: C unchanged
+        const BlendStep b = blend_step(x, y, ca, cb, cc, o, wp.pfx, wp.pfy, T, done);
         if constexpr (kColor) {
-            C0 = fmaf(r, w, C0);
-            C1 = fmaf(g, w, C1);
-            C2 = fmaf(bl, w, C2);
+            C0 = fmaf(r, b.w, C0);
+            C1 = fmaf(g, b.w, C1);
+            C2 = fmaf(bl, b.w, C2);
         }
-        if constexpr (kExtra) D = fmaf(d, w, D);
-        T = acc ? test_T : T;
-        done = done || stop;
+        if constexpr (kExtra) D = fmaf(d, b.w, D);
     };
-    // fields an instantiation does not carry are read from field 0 and never used
-    constexpr int iR = kColor ? kRgbField : 0, iG = kColor ? kRgbField + 1 : 0, iB = kColor ? kRgbField + 2 : 0;
-    constexpr int iD = kExtra ? kDepthField : 0;
-
-    struct Quad {
-        float4 f[kRecFields];
-    };
-    auto load_quad = [&](int i, Quad& q) {
-#pragma unroll
-        for (int f = 0; f < kRecFields; ++f) q.f[f] = *reinterpret_cast<const float4*>(&w_rec[f][i]);
-    };
-    auto blend_quad = [&](const Quad& q) {
-        const float4* f = q.f;
-        blend(f[0].x, f[1].x, f[2].x, f[3].x, f[4].x, f[5].x, f[iR].x, f[iG].x, f[iB].x, f[iD].x);
-        blend(f[0].y, f[1].y, f[2].y, f[3].y, f[4].y, f[5].y, f[iR].y, f[iG].y, f[iB].y, f[iD].y);
-        blend(f[0].z, f[1].z, f[2].z, f[3].z, f[4].z, f[5].z, f[iR].z, f[iG].z, f[iB].z, f[iD].z);
-        blend(f[0].w, f[1].w, f[2].w, f[3].w, f[4].w, f[5].w, f[iR].w, f[iG].w, f[iB].w, f[iD].w);
-    };
-
-    const uint32_t* sids = reinterpret_cast<const uint32_t*>(skeys);  // sorted ids (n <= kSortCap)
-    auto walk = [&](auto lds_tag) {
-        constexpr bool kInLds = decltype(lds_tag)::value;
-        // this lane's record of the next 64-entry chunk, fetched one chunk ahead
-        float4 r_xy = make_float4(0.f, 0.f, 0.f, 0.f), r_co = r_xy, r_rgb = r_xy, r_cull = r_xy;
-        bool r_valid = false;
-        auto fetch = [&](int k) {
-            r_valid = k < n;
-            if (r_valid) {
-                // the list's address space is static here, so the LDS read is a ds_read (a generic
-                // load would wait on every outstanding load, the previous chunk's prefetch included)
-                uint32_t gid;
-                if constexpr (kInLds)
-                    gid = sids[k];
-                else
-                    gid = (uint32_t)gkeys[k];
-                const float4* rec = ws.rec + 4 * (vbase + gid);
-                r_xy = rec[0];
-                r_co = rec[1];
-                r_rgb = rec[2];
-                r_cull = rec[3];
-            }
-        };
-        fetch(lane);
-        for (int c0 = 0; c0 < n; c0 += kWave) {
-            if (__all(done)) break;
-            const float4 xy = r_xy, co = r_co, rgb = r_rgb, cull = r_cull;
-            const bool valid = r_valid;
-            fetch(c0 + kWave + lane);
-            // order-preserving compaction of the chunk's entries whose alpha >= 1/255 box touches
-            // this wave's 8x8 block
-            bool hit = valid && !(xy.x + xy.z < wx0 || xy.x - xy.z > wx1 || xy.y + xy.w < wy0 ||
-                                  xy.y - xy.w > wy1);
-            if (hit) hit = ellipse_meets_block(xy.x, xy.y, co, cull, wx0, wx1, wy0, wy1);
-            const uint64_t mask = __ballot(hit);
-            const int m = p.diag == 4 ? 0 : __popcll(mask);
-            d_entries += m;
-            ++d_chunks;
-            if (hit) {
-                const int pos = __popcll(mask & lt_mask);
-                w_rec[0][pos] = xy.x;
-                w_rec[1][pos] = xy.y;
-                w_rec[2][pos] = co.x;
-                w_rec[3][pos] = co.y;
-                w_rec[4][pos] = co.z;
-                w_rec[5][pos] = co.w;
-                if constexpr (kColor) {
-                    w_rec[kRgbField][pos] = rgb.x;
-                    w_rec[kRgbField + 1][pos] = rgb.y;
-                    w_rec[kRgbField + 2][pos] = rgb.z;
-                }
-                if constexpr (kExtra) w_rec[kDepthField][pos] = cull.w;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // groups of 4 entries: one ds_read_b128 per field
-            const int m4 = m & ~3;
-            for (int i = 0; i < m4; i += 4) {
-                Quad q;
-                load_quad(i, q);
-                blend_quad(q);
-            }
-            for (int i = m4; i < m; ++i)
-                blend(w_rec[0][i], w_rec[1][i], w_rec[2][i], w_rec[3][i], w_rec[4][i], w_rec[5][i], w_rec[iR][i],
-                      w_rec[iG][i], w_rec[iB][i], w_rec[iD][i]);
-            __builtin_amdgcn_wave_barrier();  // reads of this chunk's records precede the next writes
+    walk_tile<L>(p, ws, v, tl, skeys, wp, w_rec, done, [&](int m) {
+        d_entries += m;
+        ++d_chunks;
+        // groups of 4 entries: one ds_read_b128 per field
+        const int m4 = m & ~3;
+        for (int i = 0; i < m4; i += 4) {
+            float4 q[L::kDataFields];
+            load_quad<L>(w_rec, i, q);
+            quad_each<L>(q, blend);
         }
-    };
-    if (in_lds)
-        walk(std::true_type{});
-    else
-        walk(std::false_type{});
+        for (int i = m4; i < m; ++i)
+            blend(0, w_rec[0][i], w_rec[1][i], w_rec[2][i], w_rec[3][i], w_rec[4][i], w_rec[5][i], w_rec[L::iR][i],
+                  w_rec[L::iG][i], w_rec[L::iB][i], w_rec[L::iD][i]);
+    });
     if (p.diag == 5) {  // per-wave cost instead of colours: cycles since the start, entries, chunks
         C0 = (float)(__builtin_amdgcn_s_memtime() - t_begin);
         C1 = (float)d_entries;
         C2 = (float)d_chunks;
         T = 0.0f;
     }
-    if (inside) {
+    if (wp.inside) {
         const size_t hw = (size_t)p.H * p.W;
-        const size_t pix = (size_t)pyi * p.W + pxi;
+        const size_t pix = (size_t)wp.pyi * p.W + wp.pxi;
         if constexpr (kColor) {
             float* o = out_color + (size_t)v * 3 * hw + pix;
             const float* bgv = bg + 3 * v;
@@ -1014,10 +517,10 @@ __device__ __forceinline__ float dpp_f32(float x) {
 
 // --- B1: per-tile re-sort + front-to-back walk with the saved forward colour -------------------
 // One workgroup per (tile, view), the forward's mapping. The tile list is re-sorted from the
-// forward's workspace through the forward's own three paths (same functions, same total order on
-// (depth bits, id)), and each wave walks it with the forward's cull, compaction and blend decisions
-// (the same expressions under this file's contraction-off rule, so T, alpha and every branch are
-// the forward's bit for bit; early exit included). Walk direction: FRONT TO BACK. With g the
+// forward's workspace by the forward's tile_prologue() (same total order on (depth bits, id)), and each
+// wave walks it through the forward's chunk_walk() and blend_step() (one definition each, under this
+// file's contraction-off rule, so T, alpha and every branch are the forward's bit for bit; early exit
+// included). Walk direction: FRONT TO BACK. With g the
 // colour gradient at the pixel, O = out . g from the saved forward output (background term
 // included) and S_i = O - sum_{j <= i} w_j (c_j . g) the part of O behind entry i,
 //   dL/d alpha_i = T_i (c_i . g) - S_i / (1 - alpha_i),
@@ -1050,58 +553,28 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
                   // kExtra only, and last: the colour-only instantiation's argument block is unchanged
                   const float* __restrict__ out_depth, const float* __restrict__ grad_depth,
                   const float* __restrict__ out_alpha, const float* __restrict__ grad_alpha) {
-    constexpr int kRgbField = kGeomFields;                        // r g b (kColor)
-    constexpr int kDepthField = kGeomFields + (kColor ? 3 : 0);   // d (kExtra)
-    constexpr int kIdField = kDepthField + (kExtra ? 1 : 0);      // the entry's Gaussian id (bits)
-    constexpr int kRecFields = kIdField + 1;                      // 10, 11 or 8
-    constexpr int kSums = kGeomFields + (kColor ? 3 : 0) + (kExtra ? 1 : 0);  // 9, 10 or 7
-    constexpr int kDepthSum = kSums - 1;                          // kExtra: the local index of sum w gd
+    using L = RecLayout<kColor, kExtra, true>;  // 10, 11 or 8 fields, the id last
+    constexpr int kSums = L::kDataFields;       // 9, 10 or 7: one sum per data field
+    constexpr int kDepthSum = kSums - 1;        // kExtra: the local index of sum w gd
     static_assert(kSums <= kAccStride && kGradFields + 1 <= kGradRecFloats, "sums fit their slots");
     __shared__ uint64_t skeys[kSortCap];
     __shared__ uint32_t s_cnt[kBuckets];
     __shared__ uint32_t s_red[4];
-    __shared__ __attribute__((aligned(16))) float s_rec[kTileThreads / kWave][kRecFields][kWave];
+    __shared__ __attribute__((aligned(16))) float s_rec[kTileThreads / kWave][L::kRecFields][kWave];
     __shared__ __attribute__((aligned(16))) float s_acc[kTileThreads / kWave][kWave][kAccStride];
 
     const int v = blockIdx.y;
-    int tile = xcd_remap(blockIdx.x, gridDim.x) + v * p.view_rot;
-    tile %= p.T;
-    const int tx = tile % p.tiles_x, ty = tile / p.tiles_x;
-    const int t_idx = v * p.T + tile;
-    uint32_t start = ws.offsets[t_idx];
-    uint32_t end = ws.offsets[t_idx + 1];
-    if (end > (uint32_t)p.capacity) end = (uint32_t)p.capacity;
-    if (start > end) start = end;
-    const int n = (int)(end - start);
+    TileList tl;
+    if (!tile_prologue(p, ws, v, {skeys, s_cnt, s_red}, tl)) return;  // never: p.diag is 0 in the backward
 
-    uint64_t* gkeys = ws.keys + start;
-    const bool in_lds = n <= kSortCap;
-    if (in_lds) {
-        const bool try_count = p.count_sort && n > kTileThreads;
-        const bool counted = try_count && counting_sort(gkeys, n, skeys, s_cnt, s_red);
-        if (!counted) {
-            for (int i = threadIdx.x; i < n; i += kTileThreads) skeys[i] = gkeys[i];
-            __syncthreads();
-            bitonic_sort_regs(skeys, n);
-        }
-    } else {
-        bitonic_sort(gkeys, n);  // already sorted in place by the forward: the network leaves it as it is
-    }
-    // no workgroup barrier below this point
-
-    const int wid = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    const int lx = (wid & 1) * 8 + (lane & 7), ly = (wid >> 1) * 8 + (lane >> 3);
-    const int pxi = tx * kTile + lx, pyi = ty * kTile + ly;
-    const float wx0 = (float)(tx * kTile + (wid & 1) * 8), wx1 = wx0 + 7.0f;
-    const float wy0 = (float)(ty * kTile + (wid >> 1) * 8), wy1 = wy0 + 7.0f;
-    const bool inside = pxi < p.W && pyi < p.H;
-    bool done = !inside;
-    const float pfx = (float)pxi, pfy = (float)pyi;
+    const WavePixel wp = wave_pixel(p, tl.tile);
+    const int lane = wp.lane, pxi = wp.pxi, pyi = wp.pyi;
+    bool done = !wp.inside;
     float T = 1.0f;
     float g0 = 0.f, g1 = 0.f, g2 = 0.f;
     float gd = 0.f;  // kExtra
     float S = 0.f;  // out . g minus the entries walked so far
-    if (inside) {
+    if (wp.inside) {
         const size_t hw = (size_t)p.H * p.W;
         if constexpr (kColor) {
             const size_t at = (size_t)v * 3 * hw + (size_t)pyi * p.W + pxi;
@@ -1129,31 +602,24 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
         }
     }
     const size_t vbase = (size_t)v * p.G;
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    float (*w_rec)[kWave] = s_rec[wid];
-    float (*w_acc)[kAccStride] = s_acc[wid];
+    float (*w_rec)[kWave] = s_rec[wp.wid];
+    float (*w_acc)[kAccStride] = s_acc[wp.wid];
     const bool b0 = (lane & 1) != 0, b1 = (lane & 2) != 0;
     const int my_e = (b0 ? 2 : 0) + (b1 ? 1 : 0);  // the quad entry whose sums this lane ends up with
 
-    // one entry at this lane's pixel: the forward's blend() decisions, then the nine contributions
-    auto entry = [&](float x, float y, float ca, float cb, float cc, float o, float r, float g, float bl,
-                     float d, float (&val)[kSums]) {
-        const float dx = x - pfx, dy = y - pfy;
-        const float power2 = fmaf(dy, fmaf(cc, dy, cb * dx), (ca * dx) * dx);
-        const float ex = __builtin_amdgcn_exp2f(power2);
-        const float oe = o * ex;
-        const float alpha = fminf(0.99f, oe);
-        const float test_T = fmaf(-alpha, T, T);
-        const bool contrib = !done && !(power2 > 0.0f) && !(alpha < 1.0f / 255.0f);
-        const bool stop = contrib && (test_T < 0.0001f);
-        const bool acc = contrib && !stop;
-        const float w = acc ? alpha * T : 0.0f;
+    // one entry at this lane's pixel: the forward's decisions (blend_step), then its contributions
+    float va[4][kSums];
+    auto entry = [&](auto e, float x, float y, float ca, float cb, float cc, float o, float r, float g, float bl,
+                     float d) {
+        float (&val)[kSums] = va[decltype(e)::value];
+        const BlendStep b = blend_step(x, y, ca, cb, cc, o, wp.pfx, wp.pfy, T, done);
+        const float dx = b.dx, dy = b.dy, alpha = b.alpha, w = b.w;
         float cg = 0.0f;
         if constexpr (kColor) cg = r * g0 + g * g1 + bl * g2;
         if constexpr (kExtra) cg = cg + d * gd;  // alpha's term: the constant in S
         S = fmaf(-w, cg, S);
-        const float dalpha = acc ? T * cg - S * __builtin_amdgcn_rcpf(1.0f - alpha) : 0.0f;
-        const bool pass = acc && !(oe > 0.99f);  // the 0.99 cap passes nothing to conic, mean, opacity
+        const float dalpha = b.acc ? b.T_in * cg - S * __builtin_amdgcn_rcpf(1.0f - alpha) : 0.0f;
+        const bool pass = b.acc && !(b.oe > 0.99f);  // the 0.99 cap passes nothing to conic, mean, opacity
         const float gp = pass ? dalpha * alpha : 0.0f;  // dL/d power (natural log domain)
         constexpr float kLn2 = 0.69314718055994531f;
         const float gl = gp * kLn2;  // the stored conic carries log2(e)
@@ -1162,173 +628,78 @@ render_bwd_kernel(Params p, const float* __restrict__ out_color, const float* __
         val[2] = gp * (-0.5f * dx * dx);
         val[3] = gp * (-dx * dy);
         val[4] = gp * (-0.5f * dy * dy);
-        val[5] = pass ? dalpha * ex : 0.0f;
+        val[5] = pass ? dalpha * b.ex : 0.0f;
         if constexpr (kColor) {
             val[6] = w * g0;
             val[7] = w * g1;
             val[8] = w * g2;
         }
         if constexpr (kExtra) val[kDepthSum] = w * gd;
-        T = acc ? test_T : T;
-        done = done || stop;
     };
 
-    const uint32_t* sids = reinterpret_cast<const uint32_t*>(skeys);
-    auto walk = [&](auto lds_tag) {
-        constexpr bool kInLds = decltype(lds_tag)::value;
-        float4 r_xy = make_float4(0.f, 0.f, 0.f, 0.f), r_co = r_xy, r_rgb = r_xy, r_cull = r_xy;
-        uint32_t r_gid = 0;
-        bool r_valid = false;
-        auto fetch = [&](int k) {
-            r_valid = k < n;
-            if (r_valid) {
-                if constexpr (kInLds)
-                    r_gid = sids[k];
-                else
-                    r_gid = (uint32_t)gkeys[k];
-                const float4* rec = ws.rec + 4 * (vbase + r_gid);
-                r_xy = rec[0];
-                r_co = rec[1];
-                r_rgb = rec[2];
-                r_cull = rec[3];
+    walk_tile<L>(p, ws, v, tl, skeys, wp, w_rec, done, [&](int m) {
+        const int m4 = (m + 3) & ~3;  // the walk padded the last quad
+        for (int i = 0; i < m4; i += 4) {
+            float4 q[L::kDataFields];
+            load_quad<L>(w_rec, i, q);
+            quad_each<L>(q, entry);
+            // reduce-scatter: lanes with bit 0 clear keep entries {0, 1}, the others {2, 3};
+            // then bit 1 picks one of the pair; then the 16 lane quads are summed onto lanes 0-3
+            float tot[kSums];
+#pragma unroll
+            for (int f = 0; f < kSums; ++f) {
+                const float keep0 = b0 ? va[2][f] : va[0][f], keep1 = b0 ? va[3][f] : va[1][f];
+                const float send0 = b0 ? va[0][f] : va[2][f], send1 = b0 ? va[1][f] : va[3][f];
+                const float u0 = keep0 + dpp_f32<kDppQuadXor1>(send0);
+                const float u1 = keep1 + dpp_f32<kDppQuadXor1>(send1);
+                float t = (b1 ? u1 : u0) + dpp_f32<kDppQuadXor2>(b1 ? u0 : u1);
+                t += dpp_f32<kDppRowShl4>(t);  // lanes 0-11 of a 16-lane row: + lane l + 4
+                t += dpp_f32<kDppRowShl8>(t);  // lanes 0-3 of a row: the row's four quads
+                t += __shfl_xor(t, 16);
+                t += __shfl_xor(t, 32);        // lanes 0-3: all four rows
+                tot[f] = t;
             }
-        };
-        fetch(lane);
-        for (int c0 = 0; c0 < n; c0 += kWave) {
-            if (__all(done)) break;
-            const float4 xy = r_xy, co = r_co, rgb = r_rgb, cull = r_cull;
-            const uint32_t gid = r_gid;
-            const bool valid = r_valid;
-            fetch(c0 + kWave + lane);
-            bool hit = valid && !(xy.x + xy.z < wx0 || xy.x - xy.z > wx1 || xy.y + xy.w < wy0 ||
-                                  xy.y - xy.w > wy1);
-            if (hit) hit = ellipse_meets_block(xy.x, xy.y, co, cull, wx0, wx1, wy0, wy1);
-            const uint64_t mask = __ballot(hit);
-            const int m = __popcll(mask);
-            const int m4 = (m + 3) & ~3;
-            if (hit) {
-                const int pos = __popcll(mask & lt_mask);
-                w_rec[0][pos] = xy.x;
-                w_rec[1][pos] = xy.y;
-                w_rec[2][pos] = co.x;
-                w_rec[3][pos] = co.y;
-                w_rec[4][pos] = co.z;
-                w_rec[5][pos] = co.w;
+            if (lane < 4) {
+                float* a = w_acc[i + my_e];
+                *reinterpret_cast<float4*>(a) = make_float4(tot[0], tot[1], tot[2], tot[3]);
                 if constexpr (kColor) {
-                    w_rec[kRgbField][pos] = rgb.x;
-                    w_rec[kRgbField + 1][pos] = rgb.y;
-                    w_rec[kRgbField + 2][pos] = rgb.z;
-                }
-                if constexpr (kExtra) w_rec[kDepthField][pos] = cull.w;
-                w_rec[kIdField][pos] = __uint_as_float(gid);
-            }
-            // pad the last quad with entries that contribute nothing (opacity 0: alpha < 1/255)
-            if (lane < m4 - m) {
-#pragma unroll
-                for (int f = 0; f < kRecFields; ++f) w_rec[f][m + lane] = 0.0f;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            for (int i = 0; i < m4; i += 4) {
-                float4 q[kIdField];
-#pragma unroll
-                for (int f = 0; f < kIdField; ++f) q[f] = *reinterpret_cast<const float4*>(&w_rec[f][i]);
-                float va[4][kSums];
-                // fields an instantiation does not carry are read from field 0 and never used
-                constexpr int iR = kColor ? kRgbField : 0, iG = kColor ? kRgbField + 1 : 0,
-                              iB = kColor ? kRgbField + 2 : 0, iD = kExtra ? kDepthField : 0;
-                entry(q[0].x, q[1].x, q[2].x, q[3].x, q[4].x, q[5].x, q[iR].x, q[iG].x, q[iB].x, q[iD].x, va[0]);
-                entry(q[0].y, q[1].y, q[2].y, q[3].y, q[4].y, q[5].y, q[iR].y, q[iG].y, q[iB].y, q[iD].y, va[1]);
-                entry(q[0].z, q[1].z, q[2].z, q[3].z, q[4].z, q[5].z, q[iR].z, q[iG].z, q[iB].z, q[iD].z, va[2]);
-                entry(q[0].w, q[1].w, q[2].w, q[3].w, q[4].w, q[5].w, q[iR].w, q[iG].w, q[iB].w, q[iD].w, va[3]);
-                // reduce-scatter: lanes with bit 0 clear keep entries {0, 1}, the others {2, 3};
-                // then bit 1 picks one of the pair; then the 16 lane quads are summed onto lanes 0-3
-                float tot[kSums];
-#pragma unroll
-                for (int f = 0; f < kSums; ++f) {
-                    const float keep0 = b0 ? va[2][f] : va[0][f], keep1 = b0 ? va[3][f] : va[1][f];
-                    const float send0 = b0 ? va[0][f] : va[2][f], send1 = b0 ? va[1][f] : va[3][f];
-                    const float u0 = keep0 + dpp_f32<kDppQuadXor1>(send0);
-                    const float u1 = keep1 + dpp_f32<kDppQuadXor1>(send1);
-                    float t = (b1 ? u1 : u0) + dpp_f32<kDppQuadXor2>(b1 ? u0 : u1);
-                    t += dpp_f32<kDppRowShl4>(t);  // lanes 0-11 of a 16-lane row: + lane l + 4
-                    t += dpp_f32<kDppRowShl8>(t);  // lanes 0-3 of a row: the row's four quads
-                    t += __shfl_xor(t, 16);
-                    t += __shfl_xor(t, 32);        // lanes 0-3: all four rows
-                    tot[f] = t;
-                }
-                if (lane < 4) {
-                    float* a = w_acc[i + my_e];
-                    *reinterpret_cast<float4*>(a) = make_float4(tot[0], tot[1], tot[2], tot[3]);
-                    if constexpr (kColor) {
-                        *reinterpret_cast<float4*>(a + 4) = make_float4(tot[4], tot[5], tot[6], tot[7]);
-                        if constexpr (kExtra)
-                            *reinterpret_cast<float2*>(a + 8) = make_float2(tot[8], tot[9]);
-                        else
-                            a[8] = tot[8];
-                    } else {
-                        *reinterpret_cast<float4*>(a + 4) = make_float4(tot[4], tot[5], tot[6], 0.0f);
-                    }
+                    *reinterpret_cast<float4*>(a + 4) = make_float4(tot[4], tot[5], tot[6], tot[7]);
+                    if constexpr (kExtra)
+                        *reinterpret_cast<float2*>(a + 8) = make_float2(tot[8], tot[9]);
+                    else
+                        a[8] = tot[8];
+                } else {
+                    *reinterpret_cast<float4*>(a + 4) = make_float4(tot[4], tot[5], tot[6], 0.0f);
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // the chunk's sums to the gradient records: 16 lanes per record, 4 records per instruction
-            {
-                const int f = lane & 15;
-                for (int j = 0; j < m; j += 4) {
-                    const int e = j + (lane >> 4);
-                    if (e < m && f < kSums) {
-                        const float val = w_acc[e][f];
-                        const uint32_t id = __float_as_uint(w_rec[kIdField][e]);
-                        // the record's field: the local sum's own index, but for the depth sum without colour
-                        const int rf = (!kColor && f == kDepthSum) ? kGradFields : f;
-                        if (val != 0.0f) atomicAdd(grec + (vbase + id) * kGradRecFloats + rf, val);
-                    }
-                }
-            }
-            __builtin_amdgcn_wave_barrier();  // reads of this chunk's LDS slots precede the next writes
         }
-    };
-    if (in_lds)
-        walk(std::true_type{});
-    else
-        walk(std::false_type{});
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // the chunk's sums to the gradient records: 16 lanes per record, 4 records per instruction
+        const int f = lane & 15;
+        for (int j = 0; j < m; j += 4) {
+            const int e = j + (lane >> 4);
+            if (e < m && f < kSums) {
+                const float val = w_acc[e][f];
+                const uint32_t id = __float_as_uint(w_rec[L::kIdField][e]);
+                // the record's field: the local sum's own index, but for the depth sum without colour
+                const int rf = (!kColor && f == kDepthSum) ? kGradFields : f;
+                if (val != 0.0f) atomicAdd(grec + (vbase + id) * kGradRecFloats + rf, val);
+            }
+        }
+    });
 }
 
 // --- B2: gradient records -> gradients of the Gaussians ----------------------------------------
 // One thread per Gaussian for all views of its scene (blockIdx.y = scene), the mirror of
-// preprocess_kernel: the forward geometry of each view is recomputed with the forward's
-// expressions, the view's gradient record is chained through them, and the contributions of the
+// preprocess_kernel: the forward geometry of each view is recomputed by the forward's view_point(),
+// project(), conic_of() and sh_basis(), the view's gradient record is chained through them, and the contributions of the
 // views are summed in registers (SH: in the thread's LDS slot) and written once. No atomics. Views
 // with radii == 0 are skipped. The SH block of a wave's 64 Gaussians is staged to LDS and its
 // gradient written back by coalesced loops, as the forward reads it. 128 threads per workgroup:
 // two [threads][75] float LDS arrays (coefficients and their gradients), 76,800 bytes.
 constexpr int kPreBwdThreads = 128;
-
-// The derivative f'(z) of the fake colour behind depth_value(), times C0, where the clamp of
-// d = max(C0 f + 0.5, 0) is open; 0 where it is active (C0 f + 0.5 <= 0). z = vz / s, the forward's
-// expression. "log": f = log(max(min(z, near), far)) follows z only where far < z < near strictly.
-__device__ __forceinline__ float depth_value_dz(int mode, float vz, float s, float near, float far) {
-    const float z = vz / s;
-    float f = z, df = 1.0f;
-    if (mode == 1) {
-        f = 1.0f / z;
-        df = -1.0f / (z * z);
-    } else if (mode == 2) {
-        const float eps = 1e-10f;
-        const float disp_near = 1.0f / (near + eps), disp_far = 1.0f / (far + eps);
-        const float den = disp_near - disp_far + eps;
-        f = 1.0f - (1.0f / (z + eps) - disp_far) / den;
-        df = 1.0f / ((z + eps) * (z + eps)) / den;
-    } else if (mode == 3) {
-        f = logf(fmaxf(fminf(z, near), far));
-        df = (z > far && z < near) ? 1.0f / z : 0.0f;
-    }
-    return kSH_C0 * f + 0.5f > 0.0f ? kSH_C0 * df : 0.0f;
-}
 
 // <kColor, kExtra>, as render_bwd_kernel's: <true, false> is tsplat_raster_bwd's. kExtra chains field
 // 9 of the record (sum w gd) through the depth value into d vz, when p.depth_mode >= 0. Without kColor
@@ -1377,7 +748,6 @@ preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __
         const float k00 = C[0], k01 = C[1], k02 = C[2], k11 = C[4], k12 = C[5], k22 = C[8];
         float gm0 = 0.f, gm1 = 0.f, gm2 = 0.f, go = 0.f;
         float gk00 = 0.f, gk01 = 0.f, gk02 = 0.f, gk11 = 0.f, gk12 = 0.f, gk22 = 0.f;
-        const int nb = (p.deg + 1) * (p.deg + 1);  // SH coefficients evaluated per channel
         for (int vv = 0; vv < p.vps; ++vv) {
             const int v = scene * p.vps + vv;
             const size_t vg = (size_t)v * p.G + g;
@@ -1392,45 +762,17 @@ preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __
             const float* vm = viewmat + 16 * v;
             const float* pm = projmat + 16 * v;
             const float s = scene_scale[2 * v], s2 = scene_scale[2 * v + 1];
-            // forward geometry, the expressions of preprocess_kernel
-            const float mx = m0 * s, my = m1 * s, mz = m2 * s;
-            const float vx = vm[0] * mx + vm[4] * my + vm[8] * mz + vm[12];
-            const float vy = vm[1] * mx + vm[5] * my + vm[9] * mz + vm[13];
-            const float vz = vm[2] * mx + vm[6] * my + vm[10] * mz + vm[14];
-            const float hx = pm[0] * mx + pm[4] * my + pm[8] * mz + pm[12];
-            const float hy = pm[1] * mx + pm[5] * my + pm[9] * mz + pm[13];
-            const float hw = pm[3] * mx + pm[7] * my + pm[11] * mz + pm[15];
-            const float pw = 1.0f / (hw + 0.0000001f);
-            const float c00 = k00 * s2, c01 = k01 * s2, c02 = k02 * s2;
-            const float c11 = k11 * s2, c12 = k12 * s2, c22 = k22 * s2;
-            const float tfx = tanfov[2 * v], tfy = tanfov[2 * v + 1];
-            const float fx = (float)p.W / (2.0f * tfx), fy = (float)p.H / (2.0f * tfy);
-            const float limx = 1.3f * tfx, limy = 1.3f * tfy;
-            const float tz = vz;
-            const float rxu = vx / tz, ryu = vy / tz;
-            const float rx = fminf(limx, fmaxf(-limx, rxu)), ry = fminf(limy, fmaxf(-limy, ryu));
-            const bool in_x = rxu >= -limx && rxu <= limx, in_y = ryu >= -limy && ryu <= limy;
-            const float tx = rx * tz, ty = ry * tz;
-            const float j00 = fx / tz, j02 = -(fx * tx) / (tz * tz);
-            const float j11 = fy / tz, j12 = -(fy * ty) / (tz * tz);
-            const float n00 = j00 * vm[0] + j02 * vm[2];
-            const float n01 = j00 * vm[4] + j02 * vm[6];
-            const float n02 = j00 * vm[8] + j02 * vm[10];
-            const float n10 = j11 * vm[1] + j12 * vm[2];
-            const float n11 = j11 * vm[5] + j12 * vm[6];
-            const float n12 = j11 * vm[9] + j12 * vm[10];
-            const float u00 = n00 * c00 + n01 * c01 + n02 * c02;
-            const float u01 = n00 * c01 + n01 * c11 + n02 * c12;
-            const float u02 = n00 * c02 + n01 * c12 + n02 * c22;
-            const float u10 = n10 * c00 + n11 * c01 + n12 * c02;
-            const float u11 = n10 * c01 + n11 * c11 + n12 * c12;
-            const float u12 = n10 * c02 + n11 * c12 + n12 * c22;
-            const float a = u00 * n00 + u01 * n01 + u02 * n02 + 0.3f;
-            const float b = u00 * n10 + u01 * n11 + u02 * n12;
-            const float c = u10 * n10 + u11 * n11 + u12 * n12 + 0.3f;
-            const float det = a * c - b * b;
-            const float det_inv = 1.0f / det;
-            const float qa = c * det_inv, qb = -b * det_inv, qc = a * det_inv;
+            // forward geometry: the forward's own steps
+            const ViewPoint q = view_point(m0, m1, m2, s, vm);
+            const Projection pr = project(q, k00, k01, k02, k11, k12, k22, s2, vm, pm, tanfov[2 * v],
+                                          tanfov[2 * v + 1], p.W, p.H);
+            const Conic co = conic_of(pr);
+            const float mx = q.mx, my = q.my, mz = q.mz, vx = q.vx, vy = q.vy, vz = q.vz, tz = q.vz;
+            const float hx = pr.hx, hy = pr.hy, pw = pr.pw, fx = pr.fx, fy = pr.fy, rx = pr.rx, ry = pr.ry;
+            const bool in_x = pr.in_x, in_y = pr.in_y;
+            const float n00 = pr.n00, n01 = pr.n01, n02 = pr.n02, n10 = pr.n10, n11 = pr.n11, n12 = pr.n12;
+            const float u00 = pr.u00, u01 = pr.u01, u02 = pr.u02, u10 = pr.u10, u11 = pr.u11, u12 = pr.u12;
+            const float qa = co.a, qb = co.b, qc = co.c;
 
             // conic Q = Sigma2^-1: dL/dSigma2 = -Q G Q with G = [[g_qa, g_qb / 2], [g_qb / 2, g_qc]]
             const float hb = 0.5f * g_qb;
@@ -1466,7 +808,7 @@ preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __
                 // the depth value d = max(C0 f(vz / s) + 0.5, 0): field 9 of the record is dL/dd
                 const float g_d = gr[2].y;
                 if (p.depth_mode >= 0 && g_d != 0.0f)
-                    dvz = dvz + g_d * depth_value_dz(p.depth_mode, vz, s, near[v], far[v]) / s;
+                    dvz = dvz + g_d * depth_value(p.depth_mode, vz, s, near[v], far[v]).dz / s;
             }
             float dmx = vm[0] * dvx + vm[1] * dvy + vm[2] * dvz;
             float dmy = vm[4] * dvx + vm[5] * dvy + vm[6] * dvz;
@@ -1482,18 +824,16 @@ preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __
             if constexpr (kColor) {
                 // colour: rgb_c = max(sum_k B_k(n) sh[c][k] + 0.5, 0), n = d / |d|, d = mean s - campos
                 const float* cp = campos + 3 * v;
-                const float ddx = mx - cp[0], ddy = my - cp[1], ddz = mz - cp[2];
+                const ShDir n = sh_dir(mx - cp[0], my - cp[1], mz - cp[2]);
                 float rgb[3];
-                sh_to_rgb(my_sh, p.M, p.deg, ddx, ddy, ddz, rgb);
+                sh_to_rgb(my_sh, p.M, p.deg, n, rgb);
                 float tc[3];
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) tc[ch] = rgb[ch] > 0.0f ? g_rgb[ch] : 0.0f;  // the clamp at 0
-                const float len = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
-                const float x = ddx / len, y = ddy / len, z = ddz / len;
-                const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
                 float dnx = 0.f, dny = 0.f, dnz = 0.f;
                 // one basis function: value B and its gradient (bx, by, bz) in the unit direction
-                auto term = [&](int k, float B, float bx, float by, float bz) {
+                sh_basis(p.deg, n.x, n.y, n.z, [&](auto k_, float B, float bx, float by, float bz) {
+                    constexpr int k = decltype(k_)::value;
                     const float ak = tc[0] * my_sh[k] + tc[1] * my_sh[p.M + k] + tc[2] * my_sh[2 * p.M + k];
                     dnx += bx * ak;
                     dny += by * ak;
@@ -1501,58 +841,12 @@ preprocess_bwd_kernel(Params p, const float* __restrict__ means, const float* __
                     my_dsh[k] += tc[0] * B;
                     my_dsh[p.M + k] += tc[1] * B;
                     my_dsh[2 * p.M + k] += tc[2] * B;
-                };
-                term(0, kSH_C0, 0.f, 0.f, 0.f);
-                if (nb > 1) {
-                    term(1, -kSH_C1 * y, 0.f, -kSH_C1, 0.f);
-                    term(2, kSH_C1 * z, 0.f, 0.f, kSH_C1);
-                    term(3, -kSH_C1 * x, -kSH_C1, 0.f, 0.f);
-                }
-                if (nb > 4) {
-                    term(4, kSH_C2[0] * xy, kSH_C2[0] * y, kSH_C2[0] * x, 0.f);
-                    term(5, kSH_C2[1] * yz, 0.f, kSH_C2[1] * z, kSH_C2[1] * y);
-                    term(6, kSH_C2[2] * (2.0f * zz - xx - yy), kSH_C2[2] * -2.0f * x, kSH_C2[2] * -2.0f * y,
-                         kSH_C2[2] * 4.0f * z);
-                    term(7, kSH_C2[3] * xz, kSH_C2[3] * z, 0.f, kSH_C2[3] * x);
-                    term(8, kSH_C2[4] * (xx - yy), kSH_C2[4] * 2.0f * x, kSH_C2[4] * -2.0f * y, 0.f);
-                }
-                if (nb > 9) {
-                    term(9, kSH_C3[0] * y * (3.0f * xx - yy), kSH_C3[0] * 6.0f * xy, kSH_C3[0] * (3.0f * xx - 3.0f * yy), 0.f);
-                    term(10, kSH_C3[1] * xy * z, kSH_C3[1] * yz, kSH_C3[1] * xz, kSH_C3[1] * xy);
-                    term(11, kSH_C3[2] * y * (4.0f * zz - xx - yy), kSH_C3[2] * -2.0f * xy,
-                         kSH_C3[2] * (4.0f * zz - xx - 3.0f * yy), kSH_C3[2] * 8.0f * yz);
-                    term(12, kSH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy), kSH_C3[3] * -6.0f * xz,
-                         kSH_C3[3] * -6.0f * yz, kSH_C3[3] * (6.0f * zz - 3.0f * xx - 3.0f * yy));
-                    term(13, kSH_C3[4] * x * (4.0f * zz - xx - yy), kSH_C3[4] * (4.0f * zz - 3.0f * xx - yy),
-                         kSH_C3[4] * -2.0f * xy, kSH_C3[4] * 8.0f * xz);
-                    term(14, kSH_C3[5] * z * (xx - yy), kSH_C3[5] * 2.0f * xz, kSH_C3[5] * -2.0f * yz,
-                         kSH_C3[5] * (xx - yy));
-                    term(15, kSH_C3[6] * x * (xx - 3.0f * yy), kSH_C3[6] * (3.0f * xx - 3.0f * yy), kSH_C3[6] * -6.0f * xy,
-                         0.f);
-                }
-                if (nb > 16) {
-                    const float s7 = 7.0f * zz - 1.0f, t7 = 7.0f * zz - 3.0f;
-                    term(16, kSH_C4[0] * xy * (xx - yy), kSH_C4[0] * y * (3.0f * xx - yy), kSH_C4[0] * x * (xx - 3.0f * yy),
-                         0.f);
-                    term(17, kSH_C4[1] * yz * (3.0f * xx - yy), kSH_C4[1] * 6.0f * xy * z,
-                         kSH_C4[1] * z * (3.0f * xx - 3.0f * yy), kSH_C4[1] * y * (3.0f * xx - yy));
-                    term(18, kSH_C4[2] * xy * s7, kSH_C4[2] * y * s7, kSH_C4[2] * x * s7, kSH_C4[2] * 14.0f * xy * z);
-                    term(19, kSH_C4[3] * yz * t7, 0.f, kSH_C4[3] * z * t7, kSH_C4[3] * y * (21.0f * zz - 3.0f));
-                    term(20, kSH_C4[4] * (zz * (35.0f * zz - 30.0f) + 3.0f), 0.f, 0.f,
-                         kSH_C4[4] * z * (140.0f * zz - 60.0f));
-                    term(21, kSH_C4[5] * xz * t7, kSH_C4[5] * z * t7, 0.f, kSH_C4[5] * x * (21.0f * zz - 3.0f));
-                    term(22, kSH_C4[6] * (xx - yy) * s7, kSH_C4[6] * 2.0f * x * s7, kSH_C4[6] * -2.0f * y * s7,
-                         kSH_C4[6] * 14.0f * z * (xx - yy));
-                    term(23, kSH_C4[7] * xz * (xx - 3.0f * yy), kSH_C4[7] * z * (3.0f * xx - 3.0f * yy),
-                         kSH_C4[7] * -6.0f * xy * z, kSH_C4[7] * x * (xx - 3.0f * yy));
-                    term(24, kSH_C4[8] * (xx * (xx - 3.0f * yy) - yy * (3.0f * xx - yy)),
-                         kSH_C4[8] * x * (4.0f * xx - 12.0f * yy), kSH_C4[8] * y * (4.0f * yy - 12.0f * xx), 0.f);
-                }
+                });
                 // through n = d / |d|: dL/dd = (dn - n (n . dn)) / |d|
-                const float ndot = x * dnx + y * dny + z * dnz;
-                dmx += (dnx - x * ndot) / len;
-                dmy += (dny - y * ndot) / len;
-                dmz += (dnz - z * ndot) / len;
+                const float ndot = n.x * dnx + n.y * dny + n.z * dnz;
+                dmx += (dnx - n.x * ndot) / n.len;
+                dmy += (dny - n.y * ndot) / n.len;
+                dmz += (dnz - n.z * ndot) / n.len;
             }
             // scale-invariant rendering: mean s (cov s^2 is in gk above)
             gm0 += s * dmx;
@@ -1612,16 +906,22 @@ extern "C" size_t tsplat_raster_num_rendered_offset(int32_t G, int32_t V, int32_
     return (size_t)((char*)(w.offsets + (size_t)V * T) - (char*)(uintptr_t)0x100000);
 }
 
+// The Gaussians and cameras every entry point reads, forward and backward. near / far: the depth entry
+// points' planes, NULL elsewhere (each entry point checks them where it needs them).
+struct Scene {
+    const float *means, *cov, *shs, *opacity, *viewmat, *projmat, *campos, *tanfov, *bg, *scene_scale, *near, *far;
+};
+static bool scene_ok(const Scene& s) {
+    return s.means && s.cov && s.shs && s.opacity && s.viewmat && s.projmat && s.campos && s.tanfov && s.bg &&
+           s.scene_scale;
+}
+
 // The launch sequence of both entry points. kColor / kExtra pick the preprocess and render
 // instantiations: <true, false> is tsplat_raster_fwd; tsplat_raster_depth_fwd takes <true, true>
 // with a colour output and <false, true> without one.
 template <bool kColor, bool kExtra>
-static int raster_launch(Params p, const float* means, const float* cov, const float* shs,
-                         const float* opacity, const float* viewmat, const float* projmat,
-                         const float* campos, const float* tanfov, const float* bg,
-                         const float* scene_scale, const float* near, const float* far,
-                         float* out_color, float* out_depth, float* out_alpha, int32_t* out_radii,
-                         Workspace ws, int32_t* status, hipStream_t stream) {
+static int raster_launch(Params p, const Scene& s, float* out_color, float* out_depth, float* out_alpha,
+                         int32_t* out_radii, Workspace ws, int32_t* status, hipStream_t stream) {
     TSPLAT_PROF_BEGIN(prof::kRasterAll, stream);
     {
         // counts + cursor: 2 V T uint32, padded by carve()'s 256-byte alignment to whole uint4s
@@ -1635,8 +935,8 @@ static int raster_launch(Params p, const float* means, const float* cov, const f
     TSPLAT_PROF_BEGIN(prof::kRasterPreprocess, stream);
     hipLaunchKernelGGL((preprocess_kernel<kColor, kExtra>), dim3(ceil_div(p.G, kPreThreads), scenes),
                        dim3(kPreThreads), p.T * sizeof(uint32_t),
-                       stream, p, means, cov, shs, opacity, viewmat, projmat, campos, tanfov,
-                       scene_scale, near, far, out_radii, ws);
+                       stream, p, s.means, s.cov, s.shs, s.opacity, s.viewmat, s.projmat, s.campos, s.tanfov,
+                       s.scene_scale, s.near, s.far, out_radii, ws);
     TSPLAT_PROF_END(prof::kRasterPreprocess, stream);
     TSPLAT_CHECK_LAUNCH();
     TSPLAT_PROF_BEGIN(prof::kRasterScatter, stream);
@@ -1646,7 +946,7 @@ static int raster_launch(Params p, const float* means, const float* cov, const f
     TSPLAT_CHECK_LAUNCH();
     TSPLAT_PROF_BEGIN(prof::kRasterRender, stream);
     hipLaunchKernelGGL((render_kernel<kColor, kExtra>), dim3(p.T, p.V), dim3(kTileThreads), 0, stream, p,
-                       bg, out_color, out_depth, out_alpha, ws);
+                       s.bg, out_color, out_depth, out_alpha, ws);
     TSPLAT_PROF_END(prof::kRasterRender, stream);
     TSPLAT_PROF_END(prof::kRasterAll, stream);
     TSPLAT_CHECK_LAUNCH();
@@ -1694,16 +994,10 @@ static bool raster_params(const tsplat_raster_desc* d, int depth_mode, Params* o
 // Argument checks and launch parameters shared by tsplat_raster_fwd (depth_mode = -1, no extra
 // outputs) and tsplat_raster_depth_fwd. Every check comes before the first launch: a rejected call
 // queues nothing.
-static int raster_run(const tsplat_raster_desc* d, const float* means, const float* cov,
-                      const float* shs, const float* opacity, const float* viewmat,
-                      const float* projmat, const float* campos, const float* tanfov,
-                      const float* bg, const float* scene_scale, const float* near, const float* far,
-                      int depth_mode, bool extra, float* out_color, float* out_depth,
-                      float* out_alpha, int32_t* out_radii, void* workspace, int32_t* status,
+static int raster_run(const tsplat_raster_desc* d, const Scene& s, int depth_mode, bool extra, float* out_color,
+                      float* out_depth, float* out_alpha, int32_t* out_radii, void* workspace, int32_t* status,
                       void* stream_) {
-    if (!d || !means || !cov || !shs || !opacity || !viewmat || !projmat || !campos || !tanfov ||
-        !bg || !scene_scale || !out_radii || !workspace || !status)
-        return TSPLAT_EINVAL;
+    if (!d || !scene_ok(s) || !out_radii || !workspace || !status) return TSPLAT_EINVAL;
     if (!out_color && !out_depth && !out_alpha) return TSPLAT_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     Params p;
@@ -1718,14 +1012,10 @@ static int raster_run(const tsplat_raster_desc* d, const float* means, const flo
     // a wave's SH block starts at 3 M (scene G + 64 k) floats: 16-byte aligned when the base is
     // and 3 M G is a multiple of 4 (or there is one scene)
     const int scenes = p.V / p.vps;
-    p.sh_vec4 = ((uintptr_t)shs % 16 == 0) && (scenes == 1 || ((size_t)3 * p.M * p.G) % 4 == 0);
-#define TSPLAT_RASTER_ARGS                                                                          \
-    p, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale, near, far,     \
-        out_color, out_depth, out_alpha, out_radii, ws, status, stream
-    if (!extra) return raster_launch<true, false>(TSPLAT_RASTER_ARGS);
-    if (out_color) return raster_launch<true, true>(TSPLAT_RASTER_ARGS);
-    return raster_launch<false, true>(TSPLAT_RASTER_ARGS);
-#undef TSPLAT_RASTER_ARGS
+    p.sh_vec4 = ((uintptr_t)s.shs % 16 == 0) && (scenes == 1 || ((size_t)3 * p.M * p.G) % 4 == 0);
+    const auto launch = !extra ? raster_launch<true, false>
+                               : out_color ? raster_launch<true, true> : raster_launch<false, true>;
+    return launch(p, s, out_color, out_depth, out_alpha, out_radii, ws, status, stream);
 }
 
 extern "C" int tsplat_raster_fwd(const tsplat_raster_desc* d, const float* means, const float* cov,
@@ -1735,9 +1025,8 @@ extern "C" int tsplat_raster_fwd(const tsplat_raster_desc* d, const float* means
                                  int32_t* out_radii, void* workspace, int32_t* status,
                                  void* stream_) {
     if (!out_color) return TSPLAT_EINVAL;
-    return raster_run(d, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale,
-                      nullptr, nullptr, -1, false, out_color, nullptr, nullptr, out_radii, workspace,
-                      status, stream_);
+    const Scene s{means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale, nullptr, nullptr};
+    return raster_run(d, s, -1, false, out_color, nullptr, nullptr, out_radii, workspace, status, stream_);
 }
 
 extern "C" int tsplat_raster_depth_fwd(const tsplat_raster_desc* d, const float* means,
@@ -1750,9 +1039,9 @@ extern "C" int tsplat_raster_depth_fwd(const tsplat_raster_desc* d, const float*
                                        int32_t* status, void* stream_) {
     if (depth_mode < 0 || depth_mode > 3) return TSPLAT_EINVAL;
     if (out_depth && (!near || !far)) return TSPLAT_EINVAL;
-    return raster_run(d, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale,
-                      near, far, out_depth ? depth_mode : -1, true, out_color, out_depth, out_alpha,
-                      out_radii, workspace, status, stream_);
+    const Scene s{means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale, near, far};
+    return raster_run(d, s, out_depth ? depth_mode : -1, true, out_color, out_depth, out_alpha, out_radii,
+                      workspace, status, stream_);
 }
 
 extern "C" size_t tsplat_raster_bwd_workspace_bytes(int32_t G, int32_t V) {
@@ -1760,19 +1049,20 @@ extern "C" size_t tsplat_raster_bwd_workspace_bytes(int32_t G, int32_t V) {
     return align_up((size_t)G * V * kGradRecFloats * sizeof(float), 256);
 }
 
+// What a backward call adds to the Scene: the saved outputs and the gradients at them (NULL: not part of
+// the loss), and the four gradient outputs (NULL: not asked for).
+struct BwdIo {
+    const float *out_color, *out_depth, *out_alpha, *grad_color, *grad_depth, *grad_alpha;
+    float *grad_means, *grad_cov, *grad_shs, *grad_opacity;
+};
+
 // The launch sequence of both backward entry points: zero fill of the gradient records,
 // render_bwd_kernel, preprocess_bwd_kernel, in the <kColor, kExtra> instantiations. <true, false> is
 // tsplat_raster_bwd's, and tsplat_raster_depth_bwd's with a colour gradient alone; <true, true> adds a
 // depth and / or alpha gradient to the colour's; <false, true> runs without a colour gradient.
 template <bool kColor, bool kExtra>
-static int raster_bwd_launch(Params p, const float* means, const float* cov, const float* shs,
-                             const float* opacity, const float* viewmat, const float* projmat,
-                             const float* campos, const float* tanfov, const float* scene_scale,
-                             const float* near, const float* far, const float* out_color,
-                             const float* grad_color, const float* out_depth, const float* grad_depth,
-                             const float* out_alpha, const float* grad_alpha, const int32_t* radii,
-                             Workspace ws, float* grec, float* grad_means, float* grad_cov,
-                             float* grad_shs, float* grad_opacity, hipStream_t stream) {
+static int raster_bwd_launch(Params p, const Scene& s, const BwdIo& io, const int32_t* radii, Workspace ws,
+                             float* grec, hipStream_t stream) {
     TSPLAT_PROF_BEGIN(prof::kRasterBwdAll, stream);
     {
         const size_t n4 = (size_t)p.G * p.V * kGradRecFloats / 4;
@@ -1782,15 +1072,16 @@ static int raster_bwd_launch(Params p, const float* means, const float* cov, con
     }
     TSPLAT_PROF_BEGIN(prof::kRasterBwdRender, stream);
     hipLaunchKernelGGL((render_bwd_kernel<kColor, kExtra>), dim3(p.T, p.V), dim3(kTileThreads), 0, stream,
-                       p, out_color, grad_color, grec, ws, out_depth, grad_depth, out_alpha, grad_alpha);
+                       p, io.out_color, io.grad_color, grec, ws, io.out_depth, io.grad_depth, io.out_alpha,
+                       io.grad_alpha);
     TSPLAT_PROF_END(prof::kRasterBwdRender, stream);
     TSPLAT_CHECK_LAUNCH();
     const int scenes = p.V / p.vps;
     TSPLAT_PROF_BEGIN(prof::kRasterBwdPreprocess, stream);
     hipLaunchKernelGGL((preprocess_bwd_kernel<kColor, kExtra>), dim3(ceil_div(p.G, kPreBwdThreads), scenes),
-                       dim3(kPreBwdThreads), 0, stream, p, means, cov, shs, opacity, viewmat, projmat,
-                       campos, tanfov, scene_scale, radii, (const float*)grec, grad_means, grad_cov,
-                       grad_shs, grad_opacity, near, far);
+                       dim3(kPreBwdThreads), 0, stream, p, s.means, s.cov, s.shs, s.opacity, s.viewmat, s.projmat,
+                       s.campos, s.tanfov, s.scene_scale, radii, (const float*)grec, io.grad_means, io.grad_cov,
+                       io.grad_shs, io.grad_opacity, s.near, s.far);
     TSPLAT_PROF_END(prof::kRasterBwdPreprocess, stream);
     TSPLAT_PROF_END(prof::kRasterBwdAll, stream);
     TSPLAT_CHECK_LAUNCH();
@@ -1799,38 +1090,24 @@ static int raster_bwd_launch(Params p, const float* means, const float* cov, con
 
 // Argument checks shared by tsplat_raster_bwd (no depth or alpha gradient, depth_mode = 0) and
 // tsplat_raster_depth_bwd. Every check comes before the first launch.
-static int raster_bwd_run(const tsplat_raster_desc* d, const float* means, const float* cov,
-                          const float* shs, const float* opacity, const float* viewmat,
-                          const float* projmat, const float* campos, const float* tanfov,
-                          const float* bg, const float* scene_scale, const float* near,
-                          const float* far, int depth_mode, const float* out_color,
-                          const float* out_depth, const float* out_alpha, const float* grad_color,
-                          const float* grad_depth, const float* grad_alpha, const int32_t* radii,
-                          void* fwd_workspace, void* bwd_workspace, float* grad_means,
-                          float* grad_cov, float* grad_shs, float* grad_opacity, void* stream_) {
-    if (!d || !means || !cov || !shs || !opacity || !viewmat || !projmat || !campos || !tanfov ||
-        !bg || !scene_scale || !radii || !fwd_workspace || !bwd_workspace)
+static int raster_bwd_run(const tsplat_raster_desc* d, const Scene& s, int depth_mode, const BwdIo& io,
+                          const int32_t* radii, void* fwd_workspace, void* bwd_workspace, void* stream_) {
+    if (!d || !scene_ok(s) || !radii || !fwd_workspace || !bwd_workspace) return TSPLAT_EINVAL;
+    if (!io.grad_color && !io.grad_depth && !io.grad_alpha) return TSPLAT_EINVAL;
+    if ((io.grad_color && !io.out_color) || (io.grad_depth && !io.out_depth) || (io.grad_alpha && !io.out_alpha))
         return TSPLAT_EINVAL;
-    if (!grad_color && !grad_depth && !grad_alpha) return TSPLAT_EINVAL;
-    if ((grad_color && !out_color) || (grad_depth && !out_depth) || (grad_alpha && !out_alpha))
-        return TSPLAT_EINVAL;
-    if (grad_depth && (!near || !far)) return TSPLAT_EINVAL;
+    if (io.grad_depth && (!s.near || !s.far)) return TSPLAT_EINVAL;
     if (depth_mode < 0 || depth_mode > 3) return TSPLAT_EINVAL;
-    if (!grad_means && !grad_cov && !grad_shs && !grad_opacity) return TSPLAT_EINVAL;
+    if (!io.grad_means && !io.grad_cov && !io.grad_shs && !io.grad_opacity) return TSPLAT_EINVAL;
     Params p;
-    if (!raster_params(d, grad_depth ? depth_mode : -1, &p)) return TSPLAT_EINVAL;
+    if (!raster_params(d, io.grad_depth ? depth_mode : -1, &p)) return TSPLAT_EINVAL;
     p.diag = 0;  // the forward's timing diagnostics have no backward
     hipStream_t stream = (hipStream_t)stream_;
     Workspace ws = carve(fwd_workspace, p.G, p.V, p.T, p.capacity, nullptr);
-    float* grec = (float*)bwd_workspace;
-#define TSPLAT_RASTER_BWD_ARGS                                                                      \
-    p, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, scene_scale, near, far,          \
-        out_color, grad_color, out_depth, grad_depth, out_alpha, grad_alpha, radii, ws, grec,       \
-        grad_means, grad_cov, grad_shs, grad_opacity, stream
-    if (!grad_depth && !grad_alpha) return raster_bwd_launch<true, false>(TSPLAT_RASTER_BWD_ARGS);
-    if (grad_color) return raster_bwd_launch<true, true>(TSPLAT_RASTER_BWD_ARGS);
-    return raster_bwd_launch<false, true>(TSPLAT_RASTER_BWD_ARGS);
-#undef TSPLAT_RASTER_BWD_ARGS
+    const auto launch = !io.grad_depth && !io.grad_alpha ? raster_bwd_launch<true, false>
+                        : io.grad_color                  ? raster_bwd_launch<true, true>
+                                                         : raster_bwd_launch<false, true>;
+    return launch(p, s, io, radii, ws, (float*)bwd_workspace, stream);
 }
 
 extern "C" int tsplat_raster_bwd(const tsplat_raster_desc* d, const float* means, const float* cov,
@@ -1841,10 +1118,10 @@ extern "C" int tsplat_raster_bwd(const tsplat_raster_desc* d, const float* means
                                  void* bwd_workspace, float* grad_means, float* grad_cov,
                                  float* grad_shs, float* grad_opacity, void* stream_) {
     if (!out_color || !grad_color) return TSPLAT_EINVAL;
-    return raster_bwd_run(d, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale,
-                          nullptr, nullptr, 0, out_color, nullptr, nullptr, grad_color, nullptr, nullptr,
-                          radii, fwd_workspace, bwd_workspace, grad_means, grad_cov, grad_shs,
-                          grad_opacity, stream_);
+    const Scene s{means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale, nullptr, nullptr};
+    const BwdIo io{out_color, nullptr, nullptr, grad_color, nullptr, nullptr,
+                   grad_means, grad_cov, grad_shs, grad_opacity};
+    return raster_bwd_run(d, s, 0, io, radii, fwd_workspace, bwd_workspace, stream_);
 }
 
 extern "C" int tsplat_raster_depth_bwd(const tsplat_raster_desc* d, const float* means,
@@ -1859,10 +1136,10 @@ extern "C" int tsplat_raster_depth_bwd(const tsplat_raster_desc* d, const float*
                                        void* fwd_workspace, void* bwd_workspace, float* grad_means,
                                        float* grad_cov, float* grad_shs, float* grad_opacity,
                                        void* stream_) {
-    return raster_bwd_run(d, means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale,
-                          near, far, depth_mode, out_color, out_depth, out_alpha, grad_color, grad_depth,
-                          grad_alpha, radii, fwd_workspace, bwd_workspace, grad_means, grad_cov,
-                          grad_shs, grad_opacity, stream_);
+    const Scene s{means, cov, shs, opacity, viewmat, projmat, campos, tanfov, bg, scene_scale, near, far};
+    const BwdIo io{out_color, out_depth, out_alpha, grad_color, grad_depth, grad_alpha,
+                   grad_means, grad_cov, grad_shs, grad_opacity};
+    return raster_bwd_run(d, s, depth_mode, io, radii, fwd_workspace, bwd_workspace, stream_);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -259,6 +259,19 @@ def rasterize(
     return out.color, out.radii
 
 
+def _depth_extra(caller: str, near, far, depth_mode, color, alpha) -> tuple:
+    """The checked `extra` of _rasterize() for rasterize_with_depth() and its differentiable form:
+    (near, far, mode id, color, depth, alpha)."""
+    if depth_mode is not None and depth_mode not in DEPTH_MODES:
+        raise ValueError(f"depth_mode {depth_mode!r}: expected one of {sorted(DEPTH_MODES)} or None")
+    want_depth = depth_mode is not None
+    if not (color or want_depth or alpha):
+        raise ValueError(f"{caller}: no output asked for")
+    if want_depth and (near is None or far is None):
+        raise ValueError("a depth render needs the views' near and far planes")
+    return near, far, DEPTH_MODES[depth_mode] if want_depth else 0, bool(color), want_depth, bool(alpha)
+
+
 def rasterize_with_depth(
     means: Tensor,
     covariances: Tensor,
@@ -288,55 +301,60 @@ def rasterize_with_depth(
     alpha [V, H, W] = 1 - T, the accumulated opacity. color=False skips the colours (the SH
     coefficients are not read). Colour and radii are bit-identical to rasterize()'s.
     """
-    if depth_mode is not None and depth_mode not in DEPTH_MODES:
-        raise ValueError(f"depth_mode {depth_mode!r}: expected one of {sorted(DEPTH_MODES)} or None")
-    want_depth = depth_mode is not None
-    if not (color or want_depth or alpha):
-        raise ValueError("rasterize_with_depth: no output asked for")
-    if want_depth and (near is None or far is None):
-        raise ValueError("a depth render needs the views' near and far planes")
-    extra = (near, far, DEPTH_MODES[depth_mode] if want_depth else 0, bool(color), want_depth, bool(alpha))
+    extra = _depth_extra("rasterize_with_depth", near, far, depth_mode, color, alpha)
     return _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
                       capacity, check, debug, extra)
 
 
 class _RasterizeFn(torch.autograd.Function):
-    """rasterize() with a backward: tsplat_raster_fwd on a private workspace, tsplat_raster_bwd on
-    what that call left in it."""
+    """_rasterize() with a backward, for both differentiable calls: the forward entry point on a private
+    workspace, then the matching backward on what that call left in it (extra None: tsplat_raster_fwd /
+    tsplat_raster_bwd, else tsplat_raster_depth_fwd / tsplat_raster_depth_bwd). Returns (color, depth,
+    alpha, radii); an output that was not asked for is None; an output the loss does not use arrives in
+    backward() as None and goes to the library as NULL."""
 
     @staticmethod
     def forward(ctx, means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
-                capacity, check, debug):
+                capacity, check, debug, extra):
         keep = []
         out = _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
-                         capacity, check, debug, keep=keep)
-        desc, gauss, cams, ws, _ = keep
-        ctx.desc, ctx.workspace = desc, ws
+                         capacity, check, debug, extra, keep=keep)
+        desc, gauss, cams, ws, planes = keep
+        ctx.desc, ctx.workspace, ctx.mode = desc, ws, None if extra is None else extra[2]
         ctx.dtypes = tuple(t.dtype for t in (means, covariances, harmonics, opacities))
-        ctx.save_for_backward(*gauss, *cams, out.color, out.radii)
+        ctx.save_for_backward(*gauss, *cams, *(planes or (None, None)), out.color, out.depth, out.alpha, out.radii)
         ctx.mark_non_differentiable(out.radii)
-        return out.color, out.radii
+        ctx.set_materialize_grads(False)
+        return out.color, out.depth, out.alpha, out.radii
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_color, _grad_radii):
+    def backward(ctx, grad_color, grad_depth, grad_alpha, _grad_radii):
         lib = _lib.load()
         t = ctx.saved_tensors
-        gauss, cams, color, radii = t[:4], t[4:10], t[10], t[11]
-        dev = color.device
+        gauss, cams, planes, outs, radii = t[:4], t[4:10], t[10:12], t[12:15], t[15]
+        dev = radii.device
         desc = ctx.desc
-        grad_color = grad_color.float().contiguous()
+        none = (None,) * 12
+        gin = [None if g is None or o is None else g.float().contiguous()
+               for g, o in zip((grad_color, grad_depth, grad_alpha), outs)]
         grads = [torch.empty_like(x) if need else None for x, need in zip(gauss, ctx.needs_input_grad[:4])]
-        if all(g is None for g in grads):
-            return (None,) * 11
+        if all(g is None for g in grads) or all(g is None for g in gin):
+            return none
+        outs = [o if g is not None else None for o, g in zip(outs, gin)]
         bws = torch.empty(int(lib.tsplat_raster_bwd_workspace_bytes(desc.num_gaussians, desc.num_views)),
                           dtype=torch.uint8, device=dev)
-        rc = lib.tsplat_raster_bwd(desc, *(_lib.ptr(x) for x in gauss), *(_lib.ptr(x) for x in cams),
-                                   _lib.ptr(color), _lib.ptr(grad_color), _lib.ptr(radii), _lib.ptr(ctx.workspace),
-                                   _lib.ptr(bws), *(_lib.ptr(g) for g in grads), _lib.stream_ptr(dev))
-        _lib.check(rc, "tsplat_raster_bwd")
+        p = _lib.ptr
+        head = (desc, *(p(x) for x in gauss), *(p(x) for x in cams))
+        tail = (p(radii), p(ctx.workspace), p(bws), *(p(g) for g in grads), _lib.stream_ptr(dev))
+        if ctx.mode is None:
+            name, rc = "tsplat_raster_bwd", lib.tsplat_raster_bwd(*head, p(outs[0]), p(gin[0]), *tail)
+        else:
+            name, rc = "tsplat_raster_depth_bwd", lib.tsplat_raster_depth_bwd(
+                *head, *(p(x) for x in planes), ctx.mode, *(p(x) for x in outs), *(p(x) for x in gin), *tail)
+        _lib.check(rc, name)
         grads = [None if g is None else g.to(dt) for g, dt in zip(grads, ctx.dtypes)]
-        return (*grads, None, None, None, None, None, None, None)
+        return (*grads, *none[4:])
 
 
 def rasterize_differentiable(
@@ -362,53 +380,9 @@ def rasterize_differentiable(
     double backward; cameras and background get no gradient. The per-pixel sums are float atomic
     adds, so the last bits of a gradient can differ between two runs.
     """
-    return _RasterizeFn.apply(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene,
-                              sh_degree, capacity, check, debug)
-
-
-class _RasterizeDepthFn(torch.autograd.Function):
-    """rasterize_with_depth() with a backward: tsplat_raster_depth_fwd on a private workspace,
-    tsplat_raster_depth_bwd on what that call left in it. An output that was not asked for is None; an
-    output the loss does not use arrives in backward() as None and goes to the library as NULL."""
-
-    @staticmethod
-    def forward(ctx, means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
-                capacity, check, debug, near, far, mode, want_color, want_depth, want_alpha):
-        keep = []
-        out = _rasterize(means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree,
-                         capacity, check, debug, (near, far, mode, want_color, want_depth, want_alpha), keep=keep)
-        desc, gauss, cams, ws, planes = keep
-        ctx.desc, ctx.workspace, ctx.mode = desc, ws, mode
-        ctx.dtypes = tuple(t.dtype for t in (means, covariances, harmonics, opacities))
-        ctx.save_for_backward(*gauss, *cams, *planes, out.color, out.depth, out.alpha, out.radii)
-        ctx.mark_non_differentiable(out.radii)
-        ctx.set_materialize_grads(False)
-        return out.color, out.depth, out.alpha, out.radii
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_color, grad_depth, grad_alpha, _grad_radii):
-        lib = _lib.load()
-        t = ctx.saved_tensors
-        gauss, cams, planes, outs, radii = t[:4], t[4:10], t[10:12], t[12:15], t[15]
-        dev = radii.device
-        desc = ctx.desc
-        none = (None,) * 17
-        gin = [None if g is None or o is None else g.float().contiguous()
-               for g, o in zip((grad_color, grad_depth, grad_alpha), outs)]
-        grads = [torch.empty_like(x) if need else None for x, need in zip(gauss, ctx.needs_input_grad[:4])]
-        if all(g is None for g in grads) or all(g is None for g in gin):
-            return none
-        outs = [o if g is not None else None for o, g in zip(outs, gin)]
-        bws = torch.empty(int(lib.tsplat_raster_bwd_workspace_bytes(desc.num_gaussians, desc.num_views)),
-                          dtype=torch.uint8, device=dev)
-        p = _lib.ptr
-        rc = lib.tsplat_raster_depth_bwd(desc, *(p(x) for x in gauss), *(p(x) for x in cams), *(p(x) for x in planes),
-                                         ctx.mode, *(p(x) for x in outs), *(p(x) for x in gin), p(radii),
-                                         p(ctx.workspace), p(bws), *(p(g) for g in grads), _lib.stream_ptr(dev))
-        _lib.check(rc, "tsplat_raster_depth_bwd")
-        grads = [None if g is None else g.to(dt) for g, dt in zip(grads, ctx.dtypes)]
-        return (*grads, *none[4:])
+    color, _, _, radii = _RasterizeFn.apply(means, covariances, harmonics, opacities, cameras, image_shape,
+                                            views_per_scene, sh_degree, capacity, check, debug, None)
+    return color, radii
 
 
 def rasterize_with_depth_differentiable(
@@ -443,16 +417,9 @@ def rasterize_with_depth_differentiable(
     gradient. The per-pixel sums are float atomic adds, so the last bits of a gradient can differ
     between two runs.
     """
-    if depth_mode is not None and depth_mode not in DEPTH_MODES:
-        raise ValueError(f"depth_mode {depth_mode!r}: expected one of {sorted(DEPTH_MODES)} or None")
-    want_depth = depth_mode is not None
-    if not (color or want_depth or alpha):
-        raise ValueError("rasterize_with_depth_differentiable: no output asked for")
-    if want_depth and (near is None or far is None):
-        raise ValueError("a depth render needs the views' near and far planes")
-    c, d, a, radii = _RasterizeDepthFn.apply(
-        means, covariances, harmonics, opacities, cameras, image_shape, views_per_scene, sh_degree, capacity, check,
-        debug, near, far, DEPTH_MODES[depth_mode] if want_depth else 0, bool(color), want_depth, bool(alpha))
+    extra = _depth_extra("rasterize_with_depth_differentiable", near, far, depth_mode, color, alpha)
+    c, d, a, radii = _RasterizeFn.apply(means, covariances, harmonics, opacities, cameras, image_shape,
+                                        views_per_scene, sh_degree, capacity, check, debug, extra)
     return RasterOutput(c, radii, d, a)
 
 
