@@ -844,11 +844,14 @@ def test_conv_bias_act(device, cin, cout, hw, act, res):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("form", ["16", "16x8", "32"])
-@pytest.mark.parametrize("b,n,heads", [(2, 325, 12), (1, 37, 12), (3, 5, 2), (1, 1025, 4)])
+@pytest.mark.parametrize("b,n,heads", [(2, 325, 12), (1, 37, 12), (3, 5, 2), (1, 1025, 4), (1, 1, 1), (1, 16, 2),
+                                       (2, 32, 1), (2, 33, 1), (1, 64, 3)])
 def test_mha_kernel(device, b, n, heads, form, monkeypatch):
     """DINOv2 multi-head attention (tsplat_mha_f32_fwd, straight from the qkv layout) vs torch SDPA
     math on the CPU, for each kernel form (TSPLAT_MHA: 16-query blocks with 4 or 8 waves, 32-query
-    blocks); N = 325 is the 256x256 token count, N = 5 leaves waves without keys."""
+    blocks); N = 325 is the 256x256 token count, N = 5 leaves waves without keys, N = 1 all but one;
+    N = 16 and 32 are whole tiles (nothing masked), N = 33 is one key past a tile, N = 64 is 4 tiles
+    over the 8 waves of form 16x8."""
     from transplat_amd import kernels as K
 
     monkeypatch.setenv("TSPLAT_MHA", form)
@@ -861,7 +864,7 @@ def test_mha_kernel(device, b, n, heads, form, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("b,n", [(2, 325), (1, 5)])
+@pytest.mark.parametrize("b,n", [(2, 325), (1, 5), (1, 33)])
 def test_mha_bias_folded(device, b, n):
     """tsplat_mha_bias_f32_fwd (qkv without the projection bias + the bias vector: q bias on load,
     k bias dropped -- the softmax cancels it -- v bias on the output) vs the CPU restatement on
@@ -878,7 +881,8 @@ def test_mha_bias_folded(device, b, n):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("bias", [False, True])
-@pytest.mark.parametrize("b,n,heads", [(2, 325, 12), (16, 325, 12), (1, 37, 12), (3, 5, 2), (1, 1025, 4)])
+@pytest.mark.parametrize("b,n,heads", [(2, 325, 12), (16, 325, 12), (1, 37, 12), (3, 5, 2), (1, 1025, 4), (1, 1, 1),
+                                       (1, 16, 2), (2, 32, 1), (2, 33, 1), (1, 64, 3)])
 def test_mha_x3_kernel(device, b, n, heads, bias):
     """DINOv2 attention in split-bf16 precision (tsplat_mha_x3_fwd: qkv + bias split once into hi / lo
     bf16, QK^T and PV as hi*hi + hi*lo + lo*hi on bf16 MFMA, fp32 softmax) vs the float64 SDPA
@@ -977,10 +981,11 @@ def test_upsample_bilinear_act_kernel(device, shape, scale, act, bias):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("vb,heads,views,t", [(2, 4, 2, 256), (2, 1, 2, 256), (3, 2, 1, 100), (4, 1, 2, 37),
-                                                  (6, 2, 3, 40), (6, 1, 3, 37)])
+                                                  (6, 2, 3, 40), (6, 1, 3, 37), (1, 1, 1, 1), (2, 1, 2, 16)])
 def test_qkv_attention_cf_kernel(device, vb, heads, views, t):
     """U-Net legacy QKV attention (head dim 32, views folded into the tokens) vs the oracle; the
-    vb = 6 cases fold 3 views of 2 scenes (row view * 2 + scene)."""
+    vb = 6 cases fold 3 views of 2 scenes (row view * 2 + scene); T = 1 is one key, T = 2 x 16 exactly
+    one tile (seven waves without keys)."""
     from transplat_amd import kernels as K
 
     qkv = seeded((vb, 3 * heads * 32, t), 81) * 2.0

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "mfma.h"
 #include "prof.h"
+#include "wave_reduce.h"
 #include "winattn_layout.h"
 
 namespace tsplat {
@@ -109,11 +110,6 @@ __device__ __forceinline__ floatx4 attn_x4(const Args& a, const AttnRow& r, int 
     for (int s = 0; s < kMaxSplit; ++s)
         if (s < a.win.ksplit) acc += r.w[s] * *reinterpret_cast<const floatx4*>(a.part.o + off + s * sstride);
     return acc;
-}
-
-__device__ __forceinline__ float halves_sum(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
 // One K chunk in flight in registers: thread = 16-B chunk (tid & 15) of rows (tid >> 4) + 32 i.

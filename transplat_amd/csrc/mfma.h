@@ -7,6 +7,7 @@
 namespace tsplat {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef float floatx8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -20,8 +21,8 @@ typedef short shortx4 __attribute__((ext_vector_type(4)));
 // first value of a pair in bits 0..15). |x - hi - lo| <= 2^-18 |x|, so a product taken as
 // hi*hi' + hi*lo' + lo*hi' (the dropped lo*lo' is another 2^-18) is within 3 * 2^-18 relative of x x'.
 // Kernels that split the same way with other instructions keep their form next to their use
-// (winattn.hip, uvfused.hip, linear.hip, mha.hip, split.hip), and each kernel orders its three
-// MFMAs itself: the order fixes the bits.
+// (winattn.hip, uvfused.hip, linear.hip, split.hip), and each kernel orders its three MFMAs
+// itself: the order fixes the bits.
 
 // (a, b) rounded to bf16 and packed (a in the low half): one v_cvt_pk_bf16_f32
 __device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
@@ -33,6 +34,13 @@ __device__ __forceinline__ void split_pair(float a, float b, uint32_t& hi, uint3
     hi = pack_bf16(a, b);
     const float ah = __builtin_bit_cast(float, hi << 16), bh = __builtin_bit_cast(float, hi & 0xffff0000u);
     lo = pack_bf16(a - ah, b - bh);
+}
+
+// the same rule on a whole vector (floatxN -> bf16xN hi, lo) written as vector converts (mha.hip)
+template <typename BV, typename FV>
+__device__ __forceinline__ void split_vec(FV f, BV& hi, BV& lo) {
+    hi = __builtin_convertvector(f, BV);
+    lo = __builtin_convertvector(f - __builtin_convertvector(hi, FV), BV);
 }
 
 // exact GELU (the device library's erff)

@@ -15,9 +15,12 @@
 // merged once through LDS. 24 x 11 query blocks = 264 workgroups, ~1 wave per SIMD.
 #include <string.h>
 
+#include <initializer_list>
+
 #include "common.h"
 #include "mfma.h"
 #include "prof.h"
+#include "wave_reduce.h"
 
 namespace tsplat {
 namespace mha {
@@ -28,24 +31,91 @@ constexpr int kKT = 32;  // keys per tile
 constexpr int kThreads = 256;
 constexpr float kLog2e = 1.4426950408889634f;
 
-__device__ __forceinline__ float halves_max(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+// ---------------------------------------------------------------------------------------------
+// Steps every kernel of this file shares. Each keeps the order of operations of the kernels it
+// came from: the order fixes the bits.
+
+// The lanes that hold one query's scores: the two half-waves in the 32-query kernels (query =
+// lane & 31), the four 16-lane rows in the 16-query ones (query = lane & 15).
+struct HalvesReduce {
+    static __device__ __forceinline__ float max(float x) { return halves_max(x); }
+    static __device__ __forceinline__ float sum(float x) { return halves_sum(x); }
+};
+struct RowsReduce {
+    static __device__ __forceinline__ float max(float x) { return halves_max(rows_max(x)); }
+    static __device__ __forceinline__ float sum(float x) { return halves_sum(rows_sum(x)); }
+};
+
+__device__ __forceinline__ float lane_max(const floatx16& s) {
+    float bmax = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bmax = fmaxf(bmax, s[r]);
+    return bmax;
 }
-__device__ __forceinline__ float halves_sum(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// lanes l and l ^ 16 (v_permlane16_swap exchanges 16-lane rows 0 <-> 1 and 2 <-> 3, VALU only)
-__device__ __forceinline__ float rows_max(float x) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float rows_sum(float x) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+__device__ __forceinline__ float lane_max(const floatx4& s) { return fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])); }
+
+// One online-softmax step on a tile of log2-domain scores: s becomes the probabilities 2^(s - m_run);
+// the running sum and every accumulator are rescaled only when some lane's maximum grew.
+template <class Reduce, class S, class O, int NO>
+__device__ __forceinline__ void softmax_step(S& s, O (&o)[NO], float& m_run, float& l_run) {
+    const float bmax = Reduce::max(lane_max(s));
+    const float m_new = fmaxf(m_run, bmax);
+    if (__any(m_new > m_run)) {
+        const float corr = __builtin_amdgcn_exp2f(m_run - m_new);
+        l_run *= corr;
+#pragma unroll
+        for (int i = 0; i < NO; ++i) o[i] *= corr;
+        m_run = m_new;
+    }
+    float bsum = 0.f;
+#pragma unroll
+    for (int r = 0; r < (int)(sizeof(S) / sizeof(float)); ++r) {
+        const float e = __builtin_amdgcn_exp2f(s[r] - m_run);
+        s[r] = e;
+        bsum += e;
+    }
+    l_run += Reduce::sum(bsum);
 }
 
+// 32-key tile at k0 of the 32-query kernels (s[r] = key k0 + 8(r >> 2) + 4h + (r & 3)): keys past
+// this wave's range score -inf (their exp is exactly 0)
+__device__ __forceinline__ void mask_past(floatx16& s, int k0, int h, int k_hi) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if (k0 + 8 * (r >> 2) + 4 * h + (r & 3) >= k_hi) s[r] = -INFINITY;
+}
+
+// Merge weights of the W key shares of query column c from their (max, sum) in sML: a[w] =
+// 2^(m_w - M), exactly 0 for a share that saw no key (m_w = -inf), and the return value
+// 1 / sum_w a[w] l_w. The merged output is (sum_w a[w] O_w) times that.
+template <int W, int Q>
+__device__ __forceinline__ float share_weights(const float (&sML)[W][2][Q], int c, float (&a)[W]) {
+    float mw[W], M = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        mw[w] = sML[w][0][c];
+        M = fmaxf(M, mw[w]);
+    }
+    float L = 0.f;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        a[w] = mw[w] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw[w] - M);
+        L += a[w] * sML[w][1][c];
+    }
+    return 1.0f / L;
+}
+
+// XCD-aware order: workgroups are dealt round-robin over the 8 XCDs, so consecutive linear ids
+// would spread one (image, head)'s query blocks over every XCD's L2; remapped, XCD x runs the
+// logical ids [x * total / 8, (x + 1) * total / 8), i.e. whole (image, head) K / V sets.
+// Only when the workgroup count is a multiple of 8, identity otherwise: the general bijection of
+// wino_steps.h also remaps the remainders, which would change the workgroup order at odd image
+// counts (252 workgroups at one image).
+__device__ __forceinline__ int xcd_block_order(int lin, int total) {
+    return (total & 7) == 0 ? (lin & 7) * (total >> 3) + (lin >> 3) : lin;
+}
+
+// ---------------------------------------------------------------------------------------------
 struct Tile {
     floatx4 k[8];  // this lane's key row, dims 32 h .. 32 h + 31
     float v[32];   // V[key 8u + 4h + j][32 dt + c] for (u, j, dt): index (u * 4 + j) * 2 + dt
@@ -123,30 +193,8 @@ mha_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int N, in
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.k[i].z, qr[4 * i + 2], s, 0, 0, 0);
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.k[i].w, qr[4 * i + 3], s, 0, 0, 0);
         }
-        // keys past this wave's range score -inf (their exp is exactly 0)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            if (k0 + 8 * (r >> 2) + 4 * h + (r & 3) >= k_hi) s[r] = -INFINITY;
-        float bmax = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) bmax = fmaxf(bmax, s[r]);
-        bmax = halves_max(bmax);
-        const float m_new = fmaxf(m_run, bmax);
-        if (__any(m_new > m_run)) {
-            const float corr = __builtin_amdgcn_exp2f(m_run - m_new);
-            l_run *= corr;
-            o[0] *= corr;
-            o[1] *= corr;
-            m_run = m_new;
-        }
-        float bsum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float e = __builtin_amdgcn_exp2f(s[r] - m_run);
-            s[r] = e;
-            bsum += e;
-        }
-        l_run += halves_sum(bsum);
+        mask_past(s, k0, h, k_hi);
+        softmax_step<HalvesReduce>(s, o, m_run, l_run);
         // O^T[d = 32 dt + 8(r >> 2) + 4h + (r & 3)][query c] += V^T P^T, k-step (u, j) contracts keys
         // {8u + j, 8u + 4 + j} (lane halves): B = the S^T register 4u + j itself
 #pragma unroll
@@ -170,19 +218,8 @@ mha_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int N, in
         for (int r = 0; r < 16; ++r) sO[wid][dt][r][lane] = o[dt][r];
     __syncthreads();
     if (wid >= 2 || !qvalid) return;
-    float mw[4], M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        mw[w] = sML[w][0][c];
-        M = fmaxf(M, mw[w]);
-    }
-    float a[4], L = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        a[w] = mw[w] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw[w] - M);
-        L += a[w] * sML[w][1][c];
-    }
-    const float inv = 1.0f / L;
+    float a[4];
+    const float inv = share_weights(sML, c, a);
     float acc[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -246,9 +283,9 @@ mha_cf32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int B, i
 #pragma unroll
         for (int t = 0; t < 16; ++t) qr[t] = qp[(size_t)t * tl] * qs;
     }
-    floatx16 o;
+    floatx16 o[1];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] = 0.f;
+    for (int r = 0; r < 16; ++r) o[0][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
     // this lane's K column (16 dims) and V row segment (16 keys) of a 32-key tile, the next tile's
     // loads issued before the current tile's MFMAs (a scheduling barrier keeps them there)
@@ -274,33 +311,14 @@ mha_cf32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int B, i
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
         for (int t = 0; t < 16; ++t) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[t], qr[t], s, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            if (k0 + 8 * (r >> 2) + 4 * h + (r & 3) >= k_hi) s[r] = -INFINITY;
-        float bmax = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) bmax = fmaxf(bmax, s[r]);
-        bmax = halves_max(bmax);
-        const float m_new = fmaxf(m_run, bmax);
-        if (__any(m_new > m_run)) {
-            const float corr = __builtin_amdgcn_exp2f(m_run - m_new);
-            l_run *= corr;
-            o *= corr;
-            m_run = m_new;
-        }
-        float bsum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float e = __builtin_amdgcn_exp2f(s[r] - m_run);
-            s[r] = e;
-            bsum += e;
-        }
-        l_run += halves_sum(bsum);
+        mask_past(s, k0, h, k_hi);
+        softmax_step<HalvesReduce>(s, o, m_run, l_run);
         // O^T[d = 8(r >> 2) + 4h + (r & 3)][query c] += V^T P^T; k-step (u, j): keys {8u + j, 8u + 4 + j}
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[u * 4 + j], s[4 * u + j], o, 0, 0, 0);
+            for (int j = 0; j < 4; ++j)
+                o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[u * 4 + j], s[4 * u + j], o[0], 0, 0, 0);
         if (has_next) {
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
@@ -315,21 +333,12 @@ mha_cf32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int B, i
         sML[wid][1][c] = l_run;
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) sO[wid][r][lane] = o[r];
+    for (int r = 0; r < 16; ++r) sO[wid][r][lane] = o[0][r];
     __syncthreads();
     // wave w finishes registers r = 2w, 2w + 1 of the merged tile
     if (!qvalid) return;
-    float M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < kCfWaves; ++w) M = fmaxf(M, sML[w][0][c]);
-    float a[kCfWaves], L = 0.f;
-#pragma unroll
-    for (int w = 0; w < kCfWaves; ++w) {
-        const float mw = sML[w][0][c];
-        a[w] = mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - M);
-        L += a[w] * sML[w][1][c];
-    }
-    const float inv = 1.0f / L;
+    float a[kCfWaves];
+    const float inv = share_weights(sML, c, a);
     const int vw = q / tl;
     float* dst = out + (((size_t)vw * B + b) * H + head) * kCfD * tl + (q - vw * tl);
 #pragma unroll
@@ -358,173 +367,100 @@ mha_cf32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int B, i
 //   O^T += V^T P^T, k-step t contracts keys {4 g + t}: B = P^T[key 4 g + t][query c] = s[t] itself,
 //     A = V[key 4 g + t][16 dt + c]; o[dt][i] = O^T[d = 16 dt + 4 g + i][query c].
 // Per-query softmax statistics reduce over the 4 registers and the 4 lane groups.
-template <int W>
-__global__ void __launch_bounds__(W * 64)
-mha16_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int N, int H, float scale,
-                 const float* __restrict__ bias) {
-    __shared__ float sO[W][16][64];
-    __shared__ float sML[W][2][16];
+//
+// mha16_kernel<W, Ops> is the one body: index maths, block order, tile shares, prefetch loop, key
+// mask, softmax, merge and store. Ops is the precision: it holds the input pointers and supplies the
+// query load, the tile type and its load, scores(tile) -> S^T and accumulate(tile, P^T, O^T).
 
-    // XCD-aware order: workgroups are dealt round-robin over the 8 XCDs, so consecutive linear ids
-    // would spread one (image, head)'s query blocks over every XCD's L2; remapped, XCD x runs the
-    // logical ids [x * total / 8, (x + 1) * total / 8), i.e. whole (image, head) K / V sets
-    const int nq = gridDim.x, total = nq * gridDim.y;
-    int lin = blockIdx.x + blockIdx.y * nq;
-    if ((total & 7) == 0) lin = (lin & 7) * (total >> 3) + (lin >> 3);
-    const int bh = lin / nq, qblk = lin - bh * nq;
-    const int b = bh / H, head = bh - b * H;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int c = lane & 15, g = lane >> 4;
-    const size_t tok = (size_t)3 * H * kD;
-    const float* base = qkv + (size_t)b * N * tok + (size_t)head * kD;
-    const float* kb = base + (size_t)H * kD;
-    const float* vb = base + (size_t)2 * H * kD;
+// What a lane addresses: (image, head) starts at element off0 of the [B, N, 3, H, 64] image (q there,
+// k at + H kD, v at + 2 H kD), token rows tok elements apart
+struct Lane16 {
+    size_t tok, off0;
+    int N, H, head, c, g;
+};
 
-    const int nt = (N + 15) / 16;
-    const int t_lo = wid * nt / W, t_hi = (wid + 1) * nt / W;
-    const int q = qblk * 16 + c;
+// exact fp32; bias != null: qkv holds x W^T without the projection's bias (see load_q)
+struct F32Ops {
+    const float* qkv;
+    const float* bias;
 
-    float qr[16];
-    {
-        const float qs = scale * kLog2e;
-        const floatx4* src = reinterpret_cast<const floatx4*>(base + (size_t)min(q, N - 1) * tok + 16 * g);
-        // the projection's bias (bias != null: qkv holds x W^T without it): q's part added here; k's part
-        // shifts every score of a query by the same b_k . q, which the softmax cancels, so it is
-        // dropped; v's part is added to the normalised output (the weights sum to 1)
-        const floatx4* bq = reinterpret_cast<const floatx4*>(bias + (size_t)head * kD + 16 * g);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const floatx4 t = bias ? src[i] + bq[i] : src[i];
-            qr[4 * i] = t.x * qs;
-            qr[4 * i + 1] = t.y * qs;
-            qr[4 * i + 2] = t.z * qs;
-            qr[4 * i + 3] = t.w * qs;
-        }
-    }
-    struct Tile16 {
+    struct Query {
+        float r[16];  // Q[query c][16 g .. 16 g + 15] * scale * log2 e
+    };
+    struct Tile {
         floatx4 k[4];  // K[key c][16 g .. 16 g + 15]
         float v[16];   // V[key 4 g + t][16 dt + c] at t * 4 + dt
     };
-    auto load_tile = [&](int tile, Tile16& T) {
-        const int k0 = tile * 16;
-        const floatx4* ks = reinterpret_cast<const floatx4*>(kb + (size_t)min(k0 + c, N - 1) * tok + 16 * g);
+
+    __device__ __forceinline__ void load_q(const Lane16& L, int q, float qs, Query& Q) const {
+        const floatx4* src =
+            reinterpret_cast<const floatx4*>(qkv + L.off0 + (size_t)min(q, L.N - 1) * L.tok + 16 * L.g);
+        // the projection's bias (bias != null: qkv holds x W^T without it): q's part added here; k's part
+        // shifts every score of a query by the same b_k . q, which the softmax cancels, so it is
+        // dropped; v's part is added to the normalised output (the weights sum to 1)
+        const floatx4* bq = reinterpret_cast<const floatx4*>(bias + (size_t)L.head * kD + 16 * L.g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const floatx4 t = bias ? src[i] + bq[i] : src[i];
+            Q.r[4 * i] = t.x * qs;
+            Q.r[4 * i + 1] = t.y * qs;
+            Q.r[4 * i + 2] = t.z * qs;
+            Q.r[4 * i + 3] = t.w * qs;
+        }
+    }
+    // v's part of the bias for this head's 64 output dims (null: none to add)
+    __device__ __forceinline__ const float* v_bias(const Lane16& L) const {
+        return bias ? bias + (size_t)(2 * L.H + L.head) * kD : nullptr;
+    }
+    __device__ __forceinline__ void load_tile(const Lane16& L, int k0, Tile& T) const {
+        const float* kb = qkv + L.off0 + (size_t)L.H * kD;
+        const float* vb = qkv + L.off0 + (size_t)2 * L.H * kD;
+        const floatx4* ks = reinterpret_cast<const floatx4*>(kb + (size_t)min(k0 + L.c, L.N - 1) * L.tok + 16 * L.g);
 #pragma unroll
         for (int i = 0; i < 4; ++i) T.k[i] = ks[i];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const float* vs = vb + (size_t)min(k0 + 4 * g + t, N - 1) * tok + c;
+            const float* vs = vb + (size_t)min(k0 + 4 * L.g + t, L.N - 1) * L.tok + L.c;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) T.v[t * 4 + dt] = vs[16 * dt];
         }
-    };
-
-    floatx4 o[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[dt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.f;
-    Tile16 cur, nxt;
-    if (t_lo < t_hi) load_tile(t_lo, cur);
-    for (int tile = t_lo; tile < t_hi; ++tile) {
-        const bool has_next = tile + 1 < t_hi;
-        if (has_next) load_tile(tile + 1, nxt);
+    }
+    static __device__ __forceinline__ floatx4 scores(const Tile& T, const Query& Q) {
         // two independent accumulation chains (dims 16 g + 0..7 / 8..15), summed once
         floatx4 s = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            s = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.k[i].x, qr[4 * i + 0], s, 0, 0, 0);
-            s2 = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.k[i + 2].x, qr[4 * i + 8], s2, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.k[i].y, qr[4 * i + 1], s, 0, 0, 0);
-            s2 = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.k[i + 2].y, qr[4 * i + 9], s2, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.k[i].z, qr[4 * i + 2], s, 0, 0, 0);
-            s2 = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.k[i + 2].z, qr[4 * i + 10], s2, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.k[i].w, qr[4 * i + 3], s, 0, 0, 0);
-            s2 = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.k[i + 2].w, qr[4 * i + 11], s2, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_16x16x4f32(T.k[i].x, Q.r[4 * i + 0], s, 0, 0, 0);
+            s2 = __builtin_amdgcn_mfma_f32_16x16x4f32(T.k[i + 2].x, Q.r[4 * i + 8], s2, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_16x16x4f32(T.k[i].y, Q.r[4 * i + 1], s, 0, 0, 0);
+            s2 = __builtin_amdgcn_mfma_f32_16x16x4f32(T.k[i + 2].y, Q.r[4 * i + 9], s2, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_16x16x4f32(T.k[i].z, Q.r[4 * i + 2], s, 0, 0, 0);
+            s2 = __builtin_amdgcn_mfma_f32_16x16x4f32(T.k[i + 2].z, Q.r[4 * i + 10], s2, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_16x16x4f32(T.k[i].w, Q.r[4 * i + 3], s, 0, 0, 0);
+            s2 = __builtin_amdgcn_mfma_f32_16x16x4f32(T.k[i + 2].w, Q.r[4 * i + 11], s2, 0, 0, 0);
         }
-        s += s2;
-        // keys past N (the last tile only) score -inf: their exp is exactly 0
-        const int kg = tile * 16 + 4 * g;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (kg + i >= N) s[i] = -INFINITY;
-        float bmax = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
-        bmax = halves_max(rows_max(bmax));
-        const float m_new = fmaxf(m_run, bmax);  // finite: every tile holds a key < N
-        if (__any(m_new > m_run)) {
-            const float corr = __builtin_amdgcn_exp2f(m_run - m_new);
-            l_run *= corr;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[dt] *= corr;
-            m_run = m_new;
-        }
-        float bsum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            s[i] = __builtin_amdgcn_exp2f(s[i] - m_run);
-            bsum += s[i];
-        }
-        l_run += halves_sum(rows_sum(bsum));
+        return s + s2;
+    }
+    static __device__ __forceinline__ void accumulate(const Tile& T, const floatx4& p, floatx4 (&o)[4]) {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.v[t * 4 + dt], s[t], o[dt], 0, 0, 0);
-        if (has_next) cur = nxt;
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(T.v[t * 4 + dt], p[t], o[dt], 0, 0, 0);
     }
+};
 
-    // merge the W key shares
-    if (g == 0) {
-        sML[wid][0][c] = m_run;
-        sML[wid][1][c] = l_run;
-    }
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sO[wid][dt * 4 + i][lane] = o[dt][i];
-    __syncthreads();
-    // 16 queries x 16 runs of 4 dims: run j holds d = 4 j .. 4 j + 3 = 16 dt + 4 g' + i (dt = j >> 2,
-    // g' = j & 3) of query qq, i.e. sO[w][4 dt + i][16 g' + qq]
-    if (tid >= 256) return;
-    const int qq = tid >> 4, j = tid & 15;
-    const int qo = qblk * 16 + qq;
-    if (qo >= N) return;
-    float mw[W], M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        mw[w] = sML[w][0][qq];
-        M = fmaxf(M, mw[w]);
-    }
-    float a[W], L = 0.f;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        a[w] = mw[w] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw[w] - M);
-        L += a[w] * sML[w][1][qq];
-    }
-    const float inv = 1.0f / L;
-    float acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < W; ++w) t += a[w] * sO[w][(j >> 2) * 4 + i][(j & 3) * 16 + qq];
-        acc[i] = t * inv;
-        if (bias) acc[i] += bias[(size_t)(2 * H + head) * kD + 4 * j + i];
-    }
-    float* dst = out + (((size_t)b * N + qo) * H + head) * kD + 4 * j;
-    *reinterpret_cast<floatx4*>(dst) = (floatx4){acc[0], acc[1], acc[2], acc[3]};
-}
-
-// ---------------------------------------------------------------------------------------------
-// Split-bf16 ("bf16x3") form of mha16_f32_kernel for the dense-layer mode of the C2 step (the
-// reference's attention matmuls run under TF32, src/main.py:15). The projection output (+ its bias)
-// is split once per call by split_qkv_kernel into hi / lo bf16 images (x = hi + lo, |x - hi - lo| <=
-// 2^-16 |x|), and every product is hi*hi + hi*lo + lo*hi with fp32 accumulation:
+// Split-bf16 ("bf16x3") precision, for the dense-layer mode of the C2 step (the reference's attention
+// matmuls run under TF32, src/main.py:15). The projection output (+ its bias) is split once per call
+// by split_qkv_kernel into hi / lo bf16 images (x = hi + lo, |x - hi - lo| <= 2^-16 |x|), and every
+// product is hi*hi + hi*lo + lo*hi with fp32 accumulation:
 //   S^T = K Q^T: two k-steps of v_mfma_f32_16x16x32_bf16 (lane group g holds dims 16 g + 8 s .. + 7 of
 //     its key row / query row in k-step s) x 3 terms, instead of 16 v_mfma_f32_16x16x4_f32;
 //   O^T += V^T P^T: per 16-dim block dt, v_mfma_f32_16x16x16_bf16 (A = V[key 4 g + j][16 dt + c],
 //     B = the lane's own 4 probabilities, split) x 3 terms, instead of 16 fp32 MFMAs.
-// Same operand / output maps, softmax and merge as mha16_f32_kernel; the biases live in the split
-// image (q's scaled by scale * log2 e in registers after re-joining hi + lo exactly).
-// (the split rule of mfma.h written as vector converts, here and in the kernel, as in linear.hip)
+// Same operand / output maps as F32Ops; the biases live in the split image (q's scaled by
+// scale * log2 e in registers after re-joining hi + lo exactly).
+// (the split rule of mfma.h written as vector converts, split_vec, as in linear.hip)
 __global__ void __launch_bounds__(256) split_qkv_kernel(const float4* __restrict__ x, const float* __restrict__ bias,
                                                         int cols4, int64_t n4, uint2* __restrict__ hi,
                                                         uint2* __restrict__ lo) {
@@ -537,155 +473,140 @@ __global__ void __launch_bounds__(256) split_qkv_kernel(const float4* __restrict
             v.z += b.z;
             v.w += b.w;
         }
-        const floatx4 f = {v.x, v.y, v.z, v.w};
-        const bf16x4 h = __builtin_convertvector(f, bf16x4);
-        const bf16x4 l = __builtin_convertvector(f - __builtin_convertvector(h, floatx4), bf16x4);
+        bf16x4 h, l;
+        split_vec((floatx4){v.x, v.y, v.z, v.w}, h, l);
         hi[i] = __builtin_bit_cast(uint2, h);
         lo[i] = __builtin_bit_cast(uint2, l);
     }
 }
 
-template <int W>
-__global__ void __launch_bounds__(W * 64)
-mha16_x3_kernel(const __bf16* __restrict__ qh_img, const __bf16* __restrict__ ql_img, float* __restrict__ out, int N,
-                int H, float scale) {
-    __shared__ float sO[W][16][64];
-    __shared__ float sML[W][2][16];
+struct X3Ops {
+    const __bf16* hi;
+    const __bf16* lo;
 
-    const int nq = gridDim.x, total = nq * gridDim.y;
-    int lin = blockIdx.x + blockIdx.y * nq;
-    if ((total & 7) == 0) lin = (lin & 7) * (total >> 3) + (lin >> 3);
-    const int bh = lin / nq, qblk = lin - bh * nq;
-    const int b = bh / H, head = bh - b * H;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int c = lane & 15, g = lane >> 4;
-    const size_t tok = (size_t)3 * H * kD;
-    const size_t off0 = (size_t)b * N * tok + (size_t)head * kD;
-    const __bf16* kh_b = qh_img + off0 + (size_t)H * kD;
-    const __bf16* kl_b = ql_img + off0 + (size_t)H * kD;
-    const __bf16* vh_b = qh_img + off0 + (size_t)2 * H * kD;
-    const __bf16* vl_b = ql_img + off0 + (size_t)2 * H * kD;
-
-    const int nt = (N + 15) / 16;
-    const int t_lo = wid * nt / W, t_hi = (wid + 1) * nt / W;
-    const int q = qblk * 16 + c;
+    struct Query {
+        bf16x8 h[2], l[2];  // Q[query c][16 g + 8 s .. + 7] * scale * log2 e, split
+    };
+    struct Tile {
+        bf16x8 kh[2], kl[2];    // K[key c][16 g + 8 s .. + 7]
+        __bf16 vh[16], vl[16];  // V[key 4 g + t][16 dt + c] at t * 4 + dt
+    };
 
     // this lane's query row, dims 16 g .. 16 g + 15: re-joined (exact), scaled, split again
-    bf16x8 qh[2], ql[2];
-    {
-        const float qs = scale * kLog2e;
-        const size_t qo = off0 + (size_t)min(q, N - 1) * tok + 16 * g;
+    __device__ __forceinline__ void load_q(const Lane16& L, int q, float qs, Query& Q) const {
+        const size_t qo = L.off0 + (size_t)min(q, L.N - 1) * L.tok + 16 * L.g;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-            const bf16x8 h = *reinterpret_cast<const bf16x8*>(qh_img + qo + 8 * s2);
-            const bf16x8 l = *reinterpret_cast<const bf16x8*>(ql_img + qo + 8 * s2);
-            typedef float floatx8 __attribute__((ext_vector_type(8)));
-            const floatx8 f = (__builtin_convertvector(h, floatx8) + __builtin_convertvector(l, floatx8)) * qs;
-            qh[s2] = __builtin_convertvector(f, bf16x8);
-            ql[s2] = __builtin_convertvector(f - __builtin_convertvector(qh[s2], floatx8), bf16x8);
+            const bf16x8 h = *reinterpret_cast<const bf16x8*>(hi + qo + 8 * s2);
+            const bf16x8 l = *reinterpret_cast<const bf16x8*>(lo + qo + 8 * s2);
+            split_vec((__builtin_convertvector(h, floatx8) + __builtin_convertvector(l, floatx8)) * qs, Q.h[s2],
+                      Q.l[s2]);
         }
     }
-    struct TileX3 {
-        bf16x8 kh[2], kl[2];      // K[key c][16 g + 8 s .. + 7]
-        __bf16 vh[16], vl[16];     // V[key 4 g + t][16 dt + c] at t * 4 + dt
-    };
-    auto load_tile = [&](int tile, TileX3& T) {
-        const int k0 = tile * 16;
-        const size_t ko = (size_t)min(k0 + c, N - 1) * tok + 16 * g;
+    __device__ __forceinline__ const float* v_bias(const Lane16&) const { return nullptr; }
+    __device__ __forceinline__ void load_tile(const Lane16& L, int k0, Tile& T) const {
+        const size_t kb = L.off0 + (size_t)L.H * kD, vb = L.off0 + (size_t)2 * L.H * kD;
+        const size_t ko = kb + (size_t)min(k0 + L.c, L.N - 1) * L.tok + 16 * L.g;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-            T.kh[s2] = *reinterpret_cast<const bf16x8*>(kh_b + ko + 8 * s2);
-            T.kl[s2] = *reinterpret_cast<const bf16x8*>(kl_b + ko + 8 * s2);
+            T.kh[s2] = *reinterpret_cast<const bf16x8*>(hi + ko + 8 * s2);
+            T.kl[s2] = *reinterpret_cast<const bf16x8*>(lo + ko + 8 * s2);
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const size_t vo = (size_t)min(k0 + 4 * g + t, N - 1) * tok + c;
+            const size_t vo = vb + (size_t)min(k0 + 4 * L.g + t, L.N - 1) * L.tok + L.c;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                T.vh[t * 4 + dt] = vh_b[vo + 16 * dt];
-                T.vl[t * 4 + dt] = vl_b[vo + 16 * dt];
+                T.vh[t * 4 + dt] = hi[vo + 16 * dt];
+                T.vl[t * 4 + dt] = lo[vo + 16 * dt];
             }
         }
-    };
-
-    floatx4 o[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[dt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.f;
-    TileX3 cur, nxt;
-    if (t_lo < t_hi) load_tile(t_lo, cur);
-    for (int tile = t_lo; tile < t_hi; ++tile) {
-        const bool has_next = tile + 1 < t_hi;
-        if (has_next) load_tile(tile + 1, nxt);
+    }
+    static __device__ __forceinline__ floatx4 scores(const Tile& T, const Query& Q) {
         floatx4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-            s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.kl[s2], qh[s2], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.kh[s2], ql[s2], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.kh[s2], qh[s2], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(T.kl[s2], Q.h[s2], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(T.kh[s2], Q.l[s2], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(T.kh[s2], Q.h[s2], s, 0, 0, 0);
         }
-        const int kg = tile * 16 + 4 * g;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (kg + i >= N) s[i] = -INFINITY;
-        float bmax = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
-        bmax = halves_max(rows_max(bmax));
-        const float m_new = fmaxf(m_run, bmax);
-        if (__any(m_new > m_run)) {
-            const float corr = __builtin_amdgcn_exp2f(m_run - m_new);
-            l_run *= corr;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[dt] *= corr;
-            m_run = m_new;
-        }
-        float bsum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            s[i] = __builtin_amdgcn_exp2f(s[i] - m_run);
-            bsum += s[i];
-        }
-        l_run += halves_sum(rows_sum(bsum));
-        const bf16x4 ph = __builtin_convertvector(s, bf16x4);
-        const bf16x4 pl = __builtin_convertvector(s - __builtin_convertvector(ph, floatx4), bf16x4);
+        return s;
+    }
+    static __device__ __forceinline__ void accumulate(const Tile& T, const floatx4& p, floatx4 (&o)[4]) {
+        bf16x4 ph, pl;
+        split_vec(p, ph, pl);
         const shortx4 phs = __builtin_bit_cast(shortx4, ph), pls = __builtin_bit_cast(shortx4, pl);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-            const bf16x4 vh4 = {cur.vh[dt], cur.vh[4 + dt], cur.vh[8 + dt], cur.vh[12 + dt]};
-            const bf16x4 vl4 = {cur.vl[dt], cur.vl[4 + dt], cur.vl[8 + dt], cur.vl[12 + dt]};
+            const bf16x4 vh4 = {T.vh[dt], T.vh[4 + dt], T.vh[8 + dt], T.vh[12 + dt]};
+            const bf16x4 vl4 = {T.vl[dt], T.vl[4 + dt], T.vl[8 + dt], T.vl[12 + dt]};
             const shortx4 vhs = __builtin_bit_cast(shortx4, vh4), vls = __builtin_bit_cast(shortx4, vl4);
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(vls, phs, o[dt], 0, 0, 0);
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(vhs, pls, o[dt], 0, 0, 0);
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(vhs, phs, o[dt], 0, 0, 0);
         }
+    }
+};
+
+template <int W, class Ops>
+__global__ void __launch_bounds__(W * 64)
+mha16_kernel(const Ops ops, float* __restrict__ out, int N, int H, float scale) {
+    __shared__ float sO[W][16][64];
+    __shared__ float sML[W][2][16];
+
+    const int nq = gridDim.x;
+    const int lin = xcd_block_order(blockIdx.x + blockIdx.y * nq, nq * gridDim.y);
+    const int bh = lin / nq, qblk = lin - bh * nq;
+    const int b = bh / H, head = bh - b * H;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const size_t tok = (size_t)3 * H * kD;
+    const Lane16 L = {tok, (size_t)b * N * tok + (size_t)head * kD, N, H, head, lane & 15, lane >> 4};
+
+    const int nt = (N + 15) / 16;
+    const int t_lo = wid * nt / W, t_hi = (wid + 1) * nt / W;
+
+    typename Ops::Query Q;
+    ops.load_q(L, qblk * 16 + L.c, scale * kLog2e, Q);
+
+    floatx4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+    typename Ops::Tile cur, nxt;
+    if (t_lo < t_hi) ops.load_tile(L, t_lo * 16, cur);
+    for (int tile = t_lo; tile < t_hi; ++tile) {
+        const bool has_next = tile + 1 < t_hi;
+        if (has_next) ops.load_tile(L, (tile + 1) * 16, nxt);
+        floatx4 s = Ops::scores(cur, Q);
+        // keys past N (the last tile only) score -inf: their exp is exactly 0
+        const int kg = tile * 16 + 4 * L.g;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (kg + i >= N) s[i] = -INFINITY;
+        softmax_step<RowsReduce>(s, o, m_run, l_run);  // the new maximum is finite: every tile holds a key < N
+        Ops::accumulate(cur, s, o);
         if (has_next) cur = nxt;
     }
 
-    if (g == 0) {
-        sML[wid][0][c] = m_run;
-        sML[wid][1][c] = l_run;
+    // merge the W key shares
+    if (L.g == 0) {
+        sML[wid][0][L.c] = m_run;
+        sML[wid][1][L.c] = l_run;
     }
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
         for (int i = 0; i < 4; ++i) sO[wid][dt * 4 + i][lane] = o[dt][i];
     __syncthreads();
+    // 16 queries x 16 runs of 4 dims: run j holds d = 4 j .. 4 j + 3 = 16 dt + 4 g' + i (dt = j >> 2,
+    // g' = j & 3) of query qq, i.e. sO[w][4 dt + i][16 g' + qq]
     if (tid >= 256) return;
     const int qq = tid >> 4, j = tid & 15;
     const int qo = qblk * 16 + qq;
     if (qo >= N) return;
-    float mw[W], M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        mw[w] = sML[w][0][qq];
-        M = fmaxf(M, mw[w]);
-    }
-    float a[W], L = 0.f;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        a[w] = mw[w] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw[w] - M);
-        L += a[w] * sML[w][1][qq];
-    }
-    const float inv = 1.0f / L;
+    float a[W];
+    const float inv = share_weights(sML, qq, a);
+    const float* bv = ops.v_bias(L);
     float acc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -693,54 +614,74 @@ mha16_x3_kernel(const __bf16* __restrict__ qh_img, const __bf16* __restrict__ ql
 #pragma unroll
         for (int w = 0; w < W; ++w) t += a[w] * sO[w][(j >> 2) * 4 + i][(j & 3) * 16 + qq];
         acc[i] = t * inv;
+        if (bv) acc[i] += bv[4 * j + i];
     }
     float* dst = out + (((size_t)b * N + qo) * H + head) * kD + 4 * j;
     *reinterpret_cast<floatx4*>(dst) = (floatx4){acc[0], acc[1], acc[2], acc[3]};
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side.
+
+// What every entry point requires: each pointer of `need` present, each of `aligned` on 16 bytes
+// (null passes), positive sizes, the kernel's head dim, and a grid y extent the device takes.
+static bool args_ok(std::initializer_list<const void*> need, std::initializer_list<const void*> aligned, int batch,
+                    int tokens, int heads, bool dim_ok) {
+    for (const void* p : need)
+        if (!p) return false;
+    for (const void* p : aligned)
+        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+    return batch > 0 && tokens > 0 && heads > 0 && dim_ok && (int64_t)batch * heads <= 65535;
+}
+
+// TSPLAT_MHA: "16" (default, 4 waves per 16-query block), "16x8" (8 waves), "32" (the
+// 32-query kernel); A/B knob.
+static int env_form() {
+    const char* env = getenv("TSPLAT_MHA");
+    return !env ? 0 : (!strcmp(env, "32") ? 2 : (!strcmp(env, "16x8") ? 1 : 0));
+}
+
+template <int W, class Ops>
+static int launch16(const Ops& ops, float* out, int batch, int tokens, int heads, float scale, hipStream_t stream) {
+    TSPLAT_PROF_BEGIN(tsplat::prof::kMha, stream);
+    hipLaunchKernelGGL((mha16_kernel<W, Ops>), dim3((tokens + 15) / 16, batch * heads), dim3(W * 64), 0, stream, ops,
+                       out, tokens, heads, scale);
+    TSPLAT_PROF_END(tsplat::prof::kMha, stream);
+    TSPLAT_CHECK_LAUNCH();
+    return TSPLAT_OK;
+}
+
 }  // namespace mha
 }  // namespace tsplat
 
+using namespace tsplat::mha;
+
 extern "C" int tsplat_mha_bias_f32_fwd(const float* qkv, const float* bias, float* out, int32_t batch,
-                                       int32_t tokens, int32_t heads, int32_t head_dim, float scale, void* stream_);
+                                       int32_t tokens, int32_t heads, int32_t head_dim, float scale, void* stream_) {
+    if (!args_ok({qkv, out}, {bias}, batch, tokens, heads, head_dim == kD)) return TSPLAT_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int form = bias ? 0 : env_form();  // the bias form is the default kernel's
+    if (form == 0) return launch16<4>(F32Ops{qkv, bias}, out, batch, tokens, heads, scale, stream);
+    if (form == 1) return launch16<8>(F32Ops{qkv, nullptr}, out, batch, tokens, heads, scale, stream);
+    TSPLAT_PROF_BEGIN(tsplat::prof::kMha, stream);
+    hipLaunchKernelGGL(mha_f32_kernel, dim3((tokens + kQW - 1) / kQW, batch * heads), dim3(kThreads), 0, stream, qkv,
+                       out, tokens, heads, scale);
+    TSPLAT_PROF_END(tsplat::prof::kMha, stream);
+    TSPLAT_CHECK_LAUNCH();
+    return TSPLAT_OK;
+}
 
 extern "C" int tsplat_mha_f32_fwd(const float* qkv, float* out, int32_t batch, int32_t tokens, int32_t heads,
                                   int32_t head_dim, float scale, void* stream_) {
     return tsplat_mha_bias_f32_fwd(qkv, nullptr, out, batch, tokens, heads, head_dim, scale, stream_);
 }
 
-extern "C" int tsplat_mha_bias_f32_fwd(const float* qkv, const float* bias, float* out, int32_t batch,
-                                       int32_t tokens, int32_t heads, int32_t head_dim, float scale, void* stream_) {
-    using namespace tsplat::mha;
-    if (!qkv || !out || batch <= 0 || tokens <= 0 || heads <= 0 || head_dim != kD) return TSPLAT_EINVAL;
-    if ((int64_t)batch * heads > 65535 || (reinterpret_cast<uintptr_t>(bias) & 15)) return TSPLAT_EINVAL;
-    hipStream_t stream = (hipStream_t)stream_;
-    // TSPLAT_MHA: "16" (default, 4 waves per 16-query block), "16x8" (8 waves), "32" (the
-    // 32-query kernel); A/B knob. The bias form is the default kernel's.
-    const char* env = getenv("TSPLAT_MHA");
-    const int form = !env || bias ? 0 : (!strcmp(env, "32") ? 2 : (!strcmp(env, "16x8") ? 1 : 0));
-    TSPLAT_PROF_BEGIN(tsplat::prof::kMha, stream);
-    if (form == 2)
-        hipLaunchKernelGGL(mha_f32_kernel, dim3((tokens + kQW - 1) / kQW, batch * heads), dim3(kThreads), 0, stream,
-                           qkv, out, tokens, heads, scale);
-    else if (form == 1)
-        hipLaunchKernelGGL(mha16_f32_kernel<8>, dim3((tokens + 15) / 16, batch * heads), dim3(512), 0, stream, qkv,
-                           out, tokens, heads, scale, nullptr);
-    else
-        hipLaunchKernelGGL(mha16_f32_kernel<4>, dim3((tokens + 15) / 16, batch * heads), dim3(256), 0, stream, qkv,
-                           out, tokens, heads, scale, bias);
-    TSPLAT_PROF_END(tsplat::prof::kMha, stream);
-    TSPLAT_CHECK_LAUNCH();
-    return TSPLAT_OK;
-}
-
 extern "C" int tsplat_qkv_attention_cf_fwd(const float* qkv, float* out, int32_t batch, int32_t heads,
                                            int32_t views, int32_t tokens_per_view, int32_t head_dim, float scale,
                                            void* stream_) {
-    using namespace tsplat::mha;
-    if (!qkv || !out || batch <= 0 || heads <= 0 || views <= 0 || tokens_per_view <= 0 || head_dim != kCfD)
+    if (!args_ok({qkv, out}, {}, batch, tokens_per_view, heads, head_dim == kCfD) || views <= 0 ||
+        (int64_t)views * tokens_per_view >= (1 << 30))
         return TSPLAT_EINVAL;
-    if ((int64_t)batch * heads > 65535 || (int64_t)views * tokens_per_view >= (1 << 30)) return TSPLAT_EINVAL;
     const int tokens = views * tokens_per_view;
     hipStream_t stream = (hipStream_t)stream_;
     TSPLAT_PROF_BEGIN(tsplat::prof::kMha, stream);
@@ -756,46 +697,28 @@ extern "C" size_t tsplat_mha_x3_workspace_bytes(int32_t batch, int32_t tokens, i
     return (size_t)2 * batch * tokens * 3 * heads * head_dim * sizeof(__bf16);
 }
 
-extern "C" int tsplat_mha_x3_fwd(const float* qkv, const float* bias, float* out, void* workspace, int32_t batch,
-                                 int32_t tokens, int32_t heads, int32_t head_dim, float scale, void* stream_) {
-    using namespace tsplat::mha;
-    if (!qkv || !out || !workspace || batch <= 0 || tokens <= 0 || heads <= 0 || head_dim != kD) return TSPLAT_EINVAL;
-    if ((int64_t)batch * heads > 65535 || (reinterpret_cast<uintptr_t>(bias) & 15) ||
-        (reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return TSPLAT_EINVAL;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int64_t n = (int64_t)batch * tokens * 3 * heads * kD;
-    __bf16* hi = (__bf16*)workspace;
-    __bf16* lo = hi + n;
-    const int64_t n4 = n / 4;
-    const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    TSPLAT_PROF_BEGIN(tsplat::prof::kMha, stream);
-    hipLaunchKernelGGL(split_qkv_kernel, dim3(blocks), dim3(256), 0, stream, (const float4*)qkv, bias,
-                       3 * heads * kD / 4, n4, (uint2*)hi, (uint2*)lo);
-    hipLaunchKernelGGL(mha16_x3_kernel<4>, dim3((tokens + 15) / 16, batch * heads), dim3(256), 0, stream, hi, lo, out,
-                       tokens, heads, scale);
-    TSPLAT_PROF_END(tsplat::prof::kMha, stream);
-    TSPLAT_CHECK_LAUNCH();
-    return TSPLAT_OK;
-}
-
 // The same attention on q / k / v already split into hi / lo bf16 images ([batch, tokens, 3 heads
 // kD] each, the qkv projection's bias included): written by the projection GEMM's epilogue
 // (tsplat_gemm_x3_fwd act 2), so the split pass and the fp32 qkv round trip are gone.
 extern "C" int tsplat_mha_x3_presplit_fwd(const void* qkv_hi, const void* qkv_lo, float* out, int32_t batch,
                                           int32_t tokens, int32_t heads, int32_t head_dim, float scale,
                                           void* stream_) {
-    using namespace tsplat::mha;
-    if (!qkv_hi || !qkv_lo || !out || batch <= 0 || tokens <= 0 || heads <= 0 || head_dim != kD) return TSPLAT_EINVAL;
-    if ((int64_t)batch * heads > 65535 || (reinterpret_cast<uintptr_t>(qkv_hi) & 15) ||
-        (reinterpret_cast<uintptr_t>(qkv_lo) & 15) ||
+    if (!args_ok({qkv_hi, qkv_lo, out}, {qkv_hi, qkv_lo}, batch, tokens, heads, head_dim == kD) ||
         (const char*)qkv_lo - (const char*)qkv_hi != (int64_t)batch * tokens * 3 * heads * kD * 2)
         return TSPLAT_EINVAL;  // the kernel takes lo at hi + n (one workspace-shaped image)
-    hipStream_t stream = (hipStream_t)stream_;
-    TSPLAT_PROF_BEGIN(tsplat::prof::kMha, stream);
-    hipLaunchKernelGGL(mha16_x3_kernel<4>, dim3((tokens + 15) / 16, batch * heads), dim3(256), 0, stream,
-                       (const __bf16*)qkv_hi, (const __bf16*)qkv_lo, out, tokens, heads, scale);
-    TSPLAT_PROF_END(tsplat::prof::kMha, stream);
-    TSPLAT_CHECK_LAUNCH();
-    return TSPLAT_OK;
+    return launch16<4>(X3Ops{(const __bf16*)qkv_hi, (const __bf16*)qkv_lo}, out, batch, tokens, heads, scale,
+                       (hipStream_t)stream_);
+}
+
+extern "C" int tsplat_mha_x3_fwd(const float* qkv, const float* bias, float* out, void* workspace, int32_t batch,
+                                 int32_t tokens, int32_t heads, int32_t head_dim, float scale, void* stream_) {
+    if (!args_ok({qkv, out, workspace}, {bias, qkv, workspace}, batch, tokens, heads, head_dim == kD))
+        return TSPLAT_EINVAL;
+    const int64_t n = (int64_t)batch * tokens * 3 * heads * kD;
+    __bf16* hi = (__bf16*)workspace;
+    const int64_t n4 = n / 4;
+    const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
+    hipLaunchKernelGGL(split_qkv_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const float4*)qkv, bias,
+                       3 * heads * kD / 4, n4, (uint2*)hi, (uint2*)(hi + n));
+    return launch16<4>(X3Ops{hi, hi + n}, out, batch, tokens, heads, scale, (hipStream_t)stream_);
 }

@@ -28,6 +28,7 @@
 #include "common.h"
 #include "mfma.h"
 #include "prof.h"
+#include "wave_reduce.h"
 #include "winattn_layout.h"
 
 namespace tsplat {
@@ -55,17 +56,6 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 // checks every built code object for such a read.
 __device__ __forceinline__ float max3_raw(float a, float b, float c) {
     return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
-}
-
-// max / sum of lanes l and l ^ 32 (the two half-waves), in VALU via v_permlane32_swap instead of
-// an LDS-routed ds_bpermute: swap(x, x) returns (x[row 0], x[row 1]) in every lane
-__device__ __forceinline__ float halves_max(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float halves_sum(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
 #ifndef TSPLAT_WA_STAMP
