@@ -632,6 +632,18 @@ int tsplat_conv1x1_bf16x3_scaled_fwd(const float* x, int32_t c_in, const float* 
                                      const float* bias, float* y, int32_t batch, int32_t height, int32_t width,
                                      int32_t c_out, int32_t channel_last, int32_t ksplit, int32_t zsplit,
                                      float* partials, int32_t* counters, void* stream);
+/* The same 1x1 / stride-1 case with one layout copy folded in (exactly one of the two per launch; the bits of
+ * tsplat_conv2d_bf16x3_fwd around that copy):
+ * px_stride > 0: x is channel-last rows, pixel q of image n at x + n * img_stride + q * px_stride floats (the
+ *   DINOv2 token tensor [batch, 1 + h w, c_in] from its second row: px_stride = c_in, img_stride = (1 + h w) c_in)
+ *   instead of NCHW. c_in a multiple of 8, x 16-byte aligned, both strides multiples of 4; else TSPLAT_EINVAL.
+ * shuffle = 2 or 4 (px_stride = img_stride = 0, x NCHW): y is the pixel shuffle of the result, channel
+ *   oc k k + ky k + kx of pixel (i, j) at y[n][oc][k i + ky][k j + kx], y [batch, c_out / k^2, k height, k width]
+ *   (a kernel = stride nn.ConvTranspose2d, reference src/depth_anything_v2/dpt.py:105-118, as one launch). */
+int tsplat_conv1x1_bf16x3_inplace_fwd(const float* x, int32_t c_in, int32_t px_stride, int64_t img_stride,
+                                      const void* w_packed, const float* bias, float* y, int32_t batch,
+                                      int32_t height, int32_t width, int32_t c_out, int32_t shuffle, int32_t ksplit,
+                                      int32_t zsplit, float* partials, int32_t* counters, void* stream);
 
 /* 3x3 / stride 1 / padding 1 convolution as Winograd F(2x2, 3x3) on exact-fp32 MFMA (replaces the
  * nn.Conv2d(c_in, c_out, 3, 1, 1) calls of the depth predictor's full-resolution heads and U-Net

@@ -10,6 +10,9 @@ runs bench.py's main in this process after setting the named constants (0 / 1). 
   query    depth_predictor_trans._NO_ZERO_QUERY the coarse layer without its zero query
   merge    uv_transformer._MERGE_PROJ           one GEMM for the fine layers' projections of the same rows
   cat      kernels._GEMM_CAT                    the MVT's mlp[0] reading [source | message] in place
+  rows     kernels._ROWS_IN                     the DPT projects' 1x1 reading the token rows in place
+  shuffle  kernels._SHUFFLE_OUT                 the DPT transposed convolutions' pixel shuffle in the 1x1's store
+  tail     encoder_trans._DEFER_DA_TAIL         Depth-Anything's depth tail in the depth predictor's fork
 """
 import importlib
 import runpy
@@ -25,6 +28,9 @@ NAMES = {
     "query": ("transplat_amd.model.encoder.matching.depth_predictor_trans", "_NO_ZERO_QUERY"),
     "merge": ("transplat_amd.model.utils.uv_transformer", "_MERGE_PROJ"),
     "cat": ("transplat_amd.kernels", "_GEMM_CAT"),
+    "rows": ("transplat_amd.kernels", "_ROWS_IN"),
+    "shuffle": ("transplat_amd.kernels", "_SHUFFLE_OUT"),
+    "tail": ("transplat_amd.model.encoder.encoder_trans", "_DEFER_DA_TAIL"),
 }
 
 if __name__ == "__main__":

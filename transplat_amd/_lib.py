@@ -113,6 +113,8 @@ SIGNATURES = {
     "tsplat_conv2d_f32_zsplit_fwd": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P] + [_I32] * 9 + [_P, _P, _P]),
     "tsplat_conv2d_bf16x3_fwd": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P] + [_I32] * 9 + [_P, _P, _P]),
     "tsplat_conv1x1_bf16x3_scaled_fwd": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P] + [_I32] * 7 + [_P, _P, _P]),
+    "tsplat_conv1x1_bf16x3_inplace_fwd": (ctypes.c_int, [_P, _I32, _I32, ctypes.c_int64, _P, _P, _P] + [_I32] * 7
+                                          + [_P, _P, _P]),
     "tsplat_resize_bilinear_nhwc_fwd": (ctypes.c_int, [_P, _P] + [_I32] * 6 + [_P]),
     "tsplat_resize_bilinear_nchw_fwd": (ctypes.c_int, [_P, _P] + [_I32] * 5 + [_P]),
     "tsplat_upsample_bilinear_act_fwd": (ctypes.c_int, [_P, _P, _P] + [_I32] * 6 + [_P]),

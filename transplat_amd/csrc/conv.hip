@@ -38,6 +38,9 @@ struct Args {
     const float* res;   // residual added to the output (y's layout) or null
     const float* scale; // conv_x3_kernel<.., SC = true>: [n, c1 + c2] factor of every input channel, or null
     int cl_out;         // conv_x3_kernel<.., SC = true>: y is [n, hout wout, cout] rows
+    int cl_px;          // conv_x3_kernel<.., CL = true>: x1 is channel-last rows, floats between pixels ...
+    long long cl_img;   // ... and between images (x1 points at image 0, pixel 0: a leading row is skipped there)
+    int shuf;           // kShuffle epilogue: k of the pixel shuffle (cout = oc k k, y is [n, oc, k hout, k wout])
     float* y;           // [n, cout, hout, wout] (NHWC: [n, hout, wout, cout])
     float* part;        // zsplit > 1: [tiles][zsplit][1024] partial tiles
     int* cnt;           // zsplit > 1: [tiles] arrival counters (zero between launches)
@@ -52,8 +55,13 @@ struct Args {
 // The tile's ksplit (and zsplit) partial sums -> bias (+ residual) -> y. Every kernel here holds one
 // 32 (cout) x 32 (pixel) tile per wave in the 32x32 MFMA accumulator layout (lane = pixel l & 31,
 // register r = cout 8 (r >> 2) + 4 (l >> 5) + (r & 3)).
-template <bool NHWC>
+// OUT: where element (cout, pixel) goes -- kNCHW, kNHWC, or kShuffle: channel (oc, ky, kx) of pixel
+// (y, x) at y[n][oc][k y + ky][k x + kx], k = p.shuf (the pixel shuffle behind a kernel = stride
+// transposed convolution run as a 1x1; same sums, only the address differs).
+enum { kNCHW = 0, kNHWC = 1, kShuffle = 2 };
+template <int OUT>
 __device__ __forceinline__ void tile_epilogue(const Args& p, const floatx16& acc, float* sred) {
+    constexpr bool NHWC = OUT == kNHWC;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, ksplit = blockDim.x >> 6;
     const int cot = blockIdx.y;
     const int hwo = p.hout * p.wout;
@@ -104,7 +112,13 @@ __device__ __forceinline__ void tile_epilogue(const Args& p, const floatx16& acc
     for (int idx = threadIdx.x; idx < 1024; idx += blockDim.x) {
         // NCHW: consecutive threads -> consecutive pixels; NHWC: -> consecutive output channels
         int r, l;
-        if (NHWC) {
+        if (OUT == kShuffle) {
+            // consecutive threads -> kx, then consecutive pixels: runs of k floats side by side in a row of y
+            const int kx = idx & (p.shuf - 1), pl = (idx / p.shuf) & 31;
+            const int col = idx / (32 * p.shuf) * p.shuf + kx;
+            r = ((col >> 3) << 2) | (col & 3);
+            l = ((col >> 2) & 1) * 32 + pl;
+        } else if (NHWC) {
             const int col = idx & 31, pl = idx >> 5;
             r = ((col >> 3) << 2) | (col & 3);
             l = ((col >> 2) & 1) * 32 + pl;
@@ -119,7 +133,12 @@ __device__ __forceinline__ void tile_epilogue(const Args& p, const floatx16& acc
         if (co >= p.cout || q >= p.npx) continue;
         if (p.bias) s += p.bias[co];
         size_t o;
-        if (NHWC) {
+        if (OUT == kShuffle) {
+            const int k = p.shuf, kk = k * k;
+            const int qn = q / hwo, qp = q - qn * hwo, qy = qp / p.wout, qx = qp - qy * p.wout;
+            const int oc = co / kk, t = co - oc * kk, ky = t / k, kx = t - ky * k;
+            o = (((size_t)qn * (p.cout / kk) + oc) * (k * p.hout) + k * qy + ky) * (k * p.wout) + k * qx + kx;
+        } else if (NHWC) {
             o = (size_t)q * p.cout + co;
         } else {
             const int qn = q / hwo, qp = q - qn * hwo;
@@ -259,8 +278,14 @@ __global__ void __launch_bounds__(1024) conv_f32_kernel(Args p) {
 // channels 16 g + 8 (l >> 5) + j; zero past cin / cout). Epilogue as the fp32 kernel's.
 // SC: the input is x * scale[n][channel] (one fp32 multiply as a value is loaded, before the hi / lo
 // split: the bits of a separate elementwise pass), and y may be channel-last rows (p.cl_out).
-template <int KS, int S, int UP, int NB, bool SC = false>
+// CL (1x1 / stride 1, one source): x1 is channel-last rows -- pixel q of image n at x1 + n cl_img + q cl_px,
+// e.g. the DINOv2 token tensor [n, 1 + hw, c] read past its class row -- so a lane's 8 channels are two
+// 16-byte loads of its pixel's row (c a multiple of 8, rows 16-byte aligned) instead of 8 loads a plane
+// apart: the operands, and so the bits, of the NCHW launch on a permuted copy.
+// SHUF (the same 1x1): the tile is stored pixel-shuffled (tile_epilogue<kShuffle>).
+template <int KS, int S, int UP, int NB, bool SC = false, bool CL = false, bool SHUF = false>
 __global__ void __launch_bounds__(1024) conv_x3_kernel(Args p) {
+    static_assert(!(CL || SHUF) || (KS == 1 && S == 1 && UP == 0 && !SC), "in-place layouts: the plain 1x1 only");
     extern __shared__ float sred[];  // [ksplit][16][64]
     constexpr int T = KS * KS, PAD = KS / 2;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, ksplit = blockDim.x >> 6;
@@ -286,7 +311,7 @@ __global__ void __launch_bounds__(1024) conv_x3_kernel(Args p) {
     const int units = ng * T;
     const int gw = blockIdx.z * ksplit + w, gstride = ksplit * p.zsplit;
     const int nu = units > gw ? (units - gw + gstride - 1) / gstride : 0;
-    const float* x1 = p.x1 + (size_t)nb * p.c1 * hwi;
+    const float* x1 = CL ? p.x1 + (size_t)nb * p.cl_img + (size_t)pix * p.cl_px : p.x1 + (size_t)nb * p.c1 * hwi;
     const float* x2 = p.x2 ? p.x2 + (size_t)nb * p.c2 * hwi : p.x1;
     const float* sc = SC && p.scale ? p.scale + (size_t)nb * ci : nullptr;
 
@@ -318,15 +343,26 @@ __global__ void __launch_bounds__(1024) conv_x3_kernel(Args p) {
                     o = off[tt];
                     tv = (vmask >> tt) & 1;
                 }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int ch = 16 * g + 8 * h + j;
-                const int cc = min(ch, ci - 1);
-                const float* src = cc < p.c1 ? x1 + (size_t)cc * hwi : x2 + (size_t)(cc - p.c1) * hwi;
-                float v = src[o];
-                if (SC && sc) v *= sc[cc];
+            if constexpr (CL) {
+                // ci is a multiple of 8: the lane's 8 channels are all inside or all past the end
+                const int ch = 16 * g + 8 * h;
+                const float4* row = reinterpret_cast<const float4*>(x1 + min(ch, ci - 8));
+                const float4 v0 = row[0], v1 = row[1];
+                const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
                 const unsigned mb = (ok && tv && ch < ci) ? ~0u : 0u;
-                xv[k][j] = __uint_as_float(__float_as_uint(v) & mb);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) xv[k][j] = __uint_as_float(__float_as_uint(v[j]) & mb);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int ch = 16 * g + 8 * h + j;
+                    const int cc = min(ch, ci - 1);
+                    const float* src = cc < p.c1 ? x1 + (size_t)cc * hwi : x2 + (size_t)(cc - p.c1) * hwi;
+                    float v = src[o];
+                    if (SC && sc) v *= sc[cc];
+                    const unsigned mb = (ok && tv && ch < ci) ? ~0u : 0u;
+                    xv[k][j] = __uint_as_float(__float_as_uint(v) & mb);
+                }
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -345,11 +381,11 @@ __global__ void __launch_bounds__(1024) conv_x3_kernel(Args p) {
     }
     if constexpr (SC) {
         if (p.cl_out) {
-            tile_epilogue<true>(p, acc, sred);
+            tile_epilogue<kNHWC>(p, acc, sred);
             return;
         }
     }
-    tile_epilogue<false>(p, acc, sred);
+    tile_epilogue<SHUF ? kShuffle : kNCHW>(p, acc, sred);
 }
 
 }  // namespace conv
@@ -482,13 +518,22 @@ extern "C" int tsplat_conv2d_f32_nhwc_fwd(const float* x, int32_t c_in, const fl
     return TSPLAT_OK;
 }
 
-// scaled: the 1x1 / stride-1 form with the per-(sample, channel) input factor and the channel-last
-// output option (tsplat_conv1x1_bf16x3_scaled_fwd); otherwise scale / cl_out are unused
+// The 1x1 / stride-1 forms beside the plain launch: scaled = the per-(sample, channel) input factor and the
+// channel-last output option (tsplat_conv1x1_bf16x3_scaled_fwd); cl_px > 0 = channel-last input rows; shuf > 0 =
+// the pixel-shuffled store (tsplat_conv1x1_bf16x3_inplace_fwd, one of the two per launch)
+struct X3Form {
+    bool scaled = false;
+    const float* scale = nullptr;
+    int32_t cl_out = 0;
+    int32_t cl_px = 0;
+    int64_t cl_img = 0;
+    int32_t shuf = 0;
+};
+
 static int conv_x3_launch(const float* x1, int32_t c1, const float* x2, int32_t c2, const void* w_packed,
                           const float* bias, float* y, int32_t batch, int32_t height, int32_t width, int32_t c_out,
                           int32_t ksize, int32_t stride, int32_t upsample, int32_t ksplit, int32_t zsplit,
-                          float* partials, int32_t* counters, bool scaled, const float* scale, int32_t cl_out,
-                          void* stream_) {
+                          float* partials, int32_t* counters, const X3Form& form, void* stream_) {
     using namespace tsplat::conv;
     if (!x1 || !w_packed || !y || batch <= 0 || height <= 0 || width <= 0 || c_out <= 0) return TSPLAT_EINVAL;
     if (zsplit < 1 || zsplit > 64 || (zsplit > 1 && (!partials || !counters))) return TSPLAT_EINVAL;
@@ -506,8 +551,11 @@ static int conv_x3_launch(const float* x1, int32_t c1, const float* x2, int32_t 
     p.wp = (const float*)w_packed;
     p.bias = bias;
     p.y = y;
-    p.scale = scale;
-    p.cl_out = cl_out;
+    p.scale = form.scale;
+    p.cl_out = form.cl_out;
+    p.cl_px = form.cl_px;
+    p.cl_img = form.cl_img;
+    p.shuf = form.shuf;
     p.c1 = c1;
     p.c2 = c2;
     p.cout = c_out;
@@ -541,17 +589,23 @@ static int conv_x3_launch(const float* x1, int32_t c1, const float* x2, int32_t 
         else if (nb == 4) hipLaunchKernelGGL((conv_x3_kernel<KS, S, UP, 4>), grid, block, lds, stream, p); \
         else hipLaunchKernelGGL((conv_x3_kernel<KS, S, UP, 2>), grid, block, lds, stream, p);             \
     } while (0)
-    if (scaled) {
-        if (nb == 1) hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 1, true>), grid, block, lds, stream, p);
-        else if (nb == 3) hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 3, true>), grid, block, lds, stream, p);
-        else if (nb == 4) hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 4, true>), grid, block, lds, stream, p);
-        else hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 2, true>), grid, block, lds, stream, p);
-    } else if (ksize == 3 && stride == 1 && !upsample) TSPLAT_X3_LAUNCH(3, 1, 0);
+#define TSPLAT_X3_1X1(...)                                                                                     \
+    do {                                                                                                       \
+        if (nb == 1) hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 1, __VA_ARGS__>), grid, block, lds, stream, p);     \
+        else if (nb == 3) hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 3, __VA_ARGS__>), grid, block, lds, stream, p); \
+        else if (nb == 4) hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 4, __VA_ARGS__>), grid, block, lds, stream, p); \
+        else hipLaunchKernelGGL((conv_x3_kernel<1, 1, 0, 2, __VA_ARGS__>), grid, block, lds, stream, p);             \
+    } while (0)
+    if (form.scaled) TSPLAT_X3_1X1(true);
+    else if (form.cl_px > 0) TSPLAT_X3_1X1(false, true, false);
+    else if (form.shuf > 0) TSPLAT_X3_1X1(false, false, true);
+    else if (ksize == 3 && stride == 1 && !upsample) TSPLAT_X3_LAUNCH(3, 1, 0);
     else if (ksize == 3 && stride == 2) TSPLAT_X3_LAUNCH(3, 2, 0);
     else if (ksize == 3) TSPLAT_X3_LAUNCH(3, 1, 1);
     else if (stride == 1) TSPLAT_X3_LAUNCH(1, 1, 0);
     else TSPLAT_X3_LAUNCH(1, 2, 0);
 #undef TSPLAT_X3_LAUNCH
+#undef TSPLAT_X3_1X1
     TSPLAT_PROF_END(tsplat::prof::kConv, stream);
     TSPLAT_CHECK_LAUNCH();
     return TSPLAT_OK;
@@ -563,7 +617,7 @@ extern "C" int tsplat_conv2d_bf16x3_fwd(const float* x1, int32_t c1, const float
                                         int32_t upsample, int32_t ksplit, int32_t zsplit, float* partials,
                                         int32_t* counters, void* stream_) {
     return conv_x3_launch(x1, c1, x2, c2, w_packed, bias, y, batch, height, width, c_out, ksize, stride, upsample,
-                          ksplit, zsplit, partials, counters, false, nullptr, 0, stream_);
+                          ksplit, zsplit, partials, counters, X3Form{}, stream_);
 }
 
 extern "C" int tsplat_conv1x1_bf16x3_scaled_fwd(const float* x, int32_t c_in, const float* scale, const void* w_packed,
@@ -571,6 +625,35 @@ extern "C" int tsplat_conv1x1_bf16x3_scaled_fwd(const float* x, int32_t c_in, co
                                                 int32_t width, int32_t c_out, int32_t channel_last, int32_t ksplit,
                                                 int32_t zsplit, float* partials, int32_t* counters, void* stream_) {
     if (channel_last != 0 && channel_last != 1) return TSPLAT_EINVAL;
+    X3Form form;
+    form.scaled = true;
+    form.scale = scale;
+    form.cl_out = channel_last;
     return conv_x3_launch(x, c_in, nullptr, 0, w_packed, bias, y, batch, height, width, c_out, 1, 1, 0, ksplit, zsplit,
-                          partials, counters, true, scale, channel_last, stream_);
+                          partials, counters, form, stream_);
+}
+
+extern "C" int tsplat_conv1x1_bf16x3_inplace_fwd(const float* x, int32_t c_in, int32_t px_stride, int64_t img_stride,
+                                                 const void* w_packed, const float* bias, float* y, int32_t batch,
+                                                 int32_t height, int32_t width, int32_t c_out, int32_t shuffle,
+                                                 int32_t ksplit, int32_t zsplit, float* partials, int32_t* counters,
+                                                 void* stream_) {
+    X3Form form;
+    if ((px_stride > 0) == (shuffle > 0)) return TSPLAT_EINVAL;  // one in-place layout per launch
+    if (px_stride > 0) {
+        // two 16-byte loads per lane and unit: whole 8-channel runs, every row 16-byte aligned
+        if (c_in <= 0 || c_in % 8 || px_stride < c_in || px_stride % 4 || img_stride % 4 ||
+            img_stride < (int64_t)height * width * px_stride || reinterpret_cast<uintptr_t>(x) % 16)
+            return TSPLAT_EINVAL;
+        if ((int64_t)batch * img_stride >= (1ll << 31)) return TSPLAT_EINVAL;
+        form.cl_px = px_stride;
+        form.cl_img = img_stride;
+    } else {
+        if (px_stride != 0 || img_stride != 0 || !(shuffle == 2 || shuffle == 4) || c_out <= 0 ||
+            c_out % (shuffle * shuffle))
+            return TSPLAT_EINVAL;
+        form.shuf = shuffle;
+    }
+    return conv_x3_launch(x, c_in, nullptr, 0, w_packed, bias, y, batch, height, width, c_out, 1, 1, 0, ksplit, zsplit,
+                          partials, counters, form, stream_);
 }

@@ -1124,6 +1124,53 @@ def conv1x1_scaled(x, scale, weight, bias=None, channel_last: bool = False):
     return y
 
 
+# The DPT head's layout copies folded into the 1x1s beside them (bf16x3 mode, tsplat_conv1x1_bf16x3_inplace_fwd,
+# the same bits); False = the copy and the plain launch (A/B scripts set them):
+# the projects' 1x1 reads the DINOv2 token rows instead of a permuted NCHW copy of them
+_ROWS_IN = True
+# the kernel = stride transposed convolutions' 1x1 stores pixel-shuffled instead of F.pixel_shuffle's copy
+_SHUFFLE_OUT = True
+
+
+def _conv1x1_inplace(x, ci, px_stride, img_stride, weight, bias, n, h, w, shuffle, y):
+    """tsplat_conv1x1_bf16x3_inplace_fwd on conv2d_direct's launch plan for the same 1x1 (so its bits)."""
+    lib = _lib.load()
+    co = weight.shape[0]
+    tiles = ((n * h * w + 31) // 32) * ((co + 31) // 32)
+    ksplit, z = _conv_x3_shape(tiles, (ci + 15) // 16)
+    part = cnt = None
+    if z > 1:
+        part = torch.empty(tiles * z * 1024, dtype=torch.float32, device=y.device)
+        cnt = _zsplit_counters(y.device, tiles)
+    pb = _f32(bias) if bias is not None else None
+    rc = lib.tsplat_conv1x1_bf16x3_inplace_fwd(_lib.ptr(x), ci, px_stride, img_stride,
+                                               _lib.ptr(conv_pack_weight_x3(weight)), _lib.ptr(pb), _lib.ptr(y), n, h, w,
+                                               co, shuffle, ksplit, z, _lib.ptr(part), _lib.ptr(cnt),
+                                               _lib.stream_ptr(y.device))
+    _lib.check(rc, "tsplat_conv1x1_bf16x3_inplace_fwd")
+    return y
+
+
+def conv1x1_rows(mod, rows, h: int, w: int):
+    """mod(x.contiguous()), x = rows.permute(0, 2, 1).reshape(n, c, h, w), for a 1x1 nn.Conv2d `mod` on channel-last
+    rows [n, h w, c] of any row and image stride (the DINOv2 tokens past the class row): where conv2d_forward is
+    installed on `mod` and would give that copy to the split-bf16 direct kernel, the kernel reads the rows in place
+    (bit-identical); rows it cannot read as 16-byte runs (c not a multiple of 8, misaligned) are copied as before."""
+    n, hw, c = rows.shape
+    x = rows.permute(0, 2, 1).reshape(n, c, h, w)
+    if not (_ROWS_IN and split_mode() and rows.is_cuda and getattr(mod.forward, "func", None) is conv2d_forward
+            and mod.weight.dim() == 4 and hw == h * w and c % 8 == 0 and rows.stride(2) == 1
+            and rows.stride(1) % 4 == 0 and rows.stride(0) % 4 == 0 and rows.stride(1) >= c
+            and rows.stride(0) >= hw * rows.stride(1) and n * rows.stride(0) < 2 ** 31 and rows.data_ptr() % 16 == 0):
+        return mod(x.contiguous())
+    call = conv_module_call(mod, (x,))._replace(contiguous=True)  # the call on the copy
+    if not (call.k == 1 and call.stride == 1 and conv_route(call, SITE_FORWARD) == "direct"
+            and conv_x3_wins(call.npx, call.ci, call.co, 1)):
+        return mod(x.contiguous())
+    y = torch.empty((n, call.co, h, w), dtype=torch.float32, device=rows.device)
+    return _conv1x1_inplace(rows, c, rows.stride(1), rows.stride(0), mod.weight, mod.bias, n, h, w, 0, y)
+
+
 def conv2d_direct(x1, weight, bias=None, stride: int = 1, x2=None, upsample: bool = False):
     """conv2d(cat([x1, x2], 1) (nearest-upsampled 2x if upsample), weight, bias, stride,
     padding = k // 2) in one MFMA launch, NCHW fp32: exact fp32 (tsplat_conv2d_f32_zsplit_fwd), or
@@ -1221,10 +1268,15 @@ def conv_unfold_gemm(x, weight, bias, stride: int, padding: int):
 def conv_transpose_direct(x, weight, bias, s: int):
     """conv_transpose2d(x, weight [ci, co, s, s], bias, stride s) -- the DPT's resize_layers
     (kernel = stride, no overlap, reference dpt.py:105-118): a 1x1 convolution to co * s^2 channels
-    on the direct exact-fp32 kernel (bias in its epilogue) + pixel_shuffle (a copy)."""
+    on the direct kernel (bias in its epilogue) + pixel_shuffle: a copy, or in the bf16x3 mode at s = 2 or 4
+    the 1x1's own store (_SHUFFLE_OUT, the same bits)."""
     ci, co = weight.shape[:2]
     w1 = _derived(weight, "convT", lambda t: t.permute(1, 2, 3, 0).reshape(co * s * s, ci, 1, 1).contiguous())
     b1 = _derived(bias, "convT_b", lambda t: t.repeat_interleave(s * s).contiguous()) if bias is not None else None
+    n, _, h, w = x.shape
+    if _SHUFFLE_OUT and split_mode() and s in (2, 4) and x.is_cuda and x.dim() == 4 and x.numel() < 2 ** 31:
+        y = torch.empty((n, co, s * h, s * w), dtype=torch.float32, device=x.device)
+        return _conv1x1_inplace(_f32(x), ci, 0, 0, w1, b1, n, h, w, s, y)
     return F.pixel_shuffle(conv2d_direct(x, w1, b1, 1), s)
 
 

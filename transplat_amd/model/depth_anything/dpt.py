@@ -26,7 +26,10 @@ from .dinov2 import DINOv2
 # slower, 444.7 vs 487.6 views/s same box (profiles/r6/ab_c2_dpt_hoist.txt).
 # bf16x3 dense mode (kernels.dense_precision): the head runs on NCHW maps instead, so its 3x3
 # convolutions take the bf16x3 Winograd kernel with the ResidualConvUnit glue fused (ReLU on load,
-# bias, + x, + the fusion block's skip: two launches per unit) and the 1x1s the direct kernel.
+# bias, + x, + the fusion block's skip: two launches per unit) and the 1x1s the direct kernel. The projects'
+# 1x1 reads the token rows where they lie and the transposed convolutions' 1x1 stores pixel-shuffled
+# (kernels.conv1x1_rows, conv_transpose_direct): no layout copy is left in reassemble. The depth
+# after output_conv1 (depth_tail) can be left to the caller, who needs it a whole matching stage later.
 
 
 def _nchw3() -> bool:
@@ -173,16 +176,18 @@ class DPTHead(nn.Module):
     def reassemble(self, i, x, patch_h, patch_w):
         """Branch i of the head up to layer{i+1}_rn (reference dpt.py:121-140): tokens [B, N, C] ->
         project (1x1) -> resize (convT / identity / strided conv) -> 3x3 layer_rn."""
-        x = x.permute(0, 2, 1).reshape((x.shape[0], x.shape[-1], patch_h, patch_w))
-        if _nchw3():  # NCHW maps for the bf16x3 kernels (the permuted view is channels-last)
-            x = self.resize_layers[i](self.projects[i](x.contiguous())).contiguous()
+        if _nchw3():  # NCHW maps for the bf16x3 kernels: the 1x1 reads the token rows, no permuted copy first
+            x = self.resize_layers[i](kernels.conv1x1_rows(self.projects[i], x, patch_h, patch_w)).contiguous()
             return getattr(self.scratch, f"layer{i + 1}_rn")(x).contiguous()
+        x = x.permute(0, 2, 1).reshape((x.shape[0], x.shape[-1], patch_h, patch_w))
         x = self.resize_layers[i](self.projects[i](x))
         return getattr(self.scratch, f"layer{i + 1}_rn")(x)
 
-    def forward(self, out_features, patch_h, patch_w, raw_tail: bool = False):
+    def forward(self, out_features, patch_h, patch_w, raw_tail: bool = False, defer_tail: bool = False):
         """`raw_tail` (not in the reference): the depth may come back WITHOUT output_conv2's last
-        ReLU (the bf16x3 NCHW route only); the caller applies ReLU either way."""
+        ReLU (the bf16x3 NCHW route only); the caller applies ReLU either way. `defer_tail`: output_conv1's
+        map comes back in the depth's place, for the caller to give to depth_tail later (nothing between
+        output_conv1 and the depth's first reader needs the depth)."""
         self.prepare(out_features[0][0].is_cuda)
         layer_1_rn, layer_2_rn, layer_3_rn, layer_4_rn = [self.reassemble(i, x[0], patch_h, patch_w)
                                                           for i, x in enumerate(out_features)]
@@ -194,20 +199,26 @@ class DPTHead(nn.Module):
         final_out = s.output_conv1(path_1)
         # nothing below writes final_out in place (_resize allocates its result): no copy needed
         out_feature = final_out.detach()
+        if defer_tail:
+            return final_out, out_feature
+        return self.depth_tail(final_out, patch_h, patch_w, raw_tail), out_feature
+
+    def depth_tail(self, final_out, patch_h, patch_w, raw_tail: bool = False):
+        """The head after output_conv1 (reference dpt.py:150-153): resize to the image, output_conv2."""
         final_out = _resize(final_out, {"size": (int(patch_h * 14), int(patch_w * 14))}, True)
-        oc = s.output_conv2
+        oc = self.scratch.output_conv2
         if (_nchw3() and final_out.is_contiguous()
                 and kernels.conv_route(kernels.conv_module_call(oc[0], (final_out,)), kernels.SITE_FORWARD) == "wino"):
             h = kernels.conv3x3_wino(final_out, oc[0].weight, oc[0].bias, act="relu")
             if raw_tail and isinstance(oc[3], nn.ReLU) and isinstance(oc[4], nn.Identity):
-                return oc[2](h), out_feature  # the ReLUs are the caller's
-            return oc[4](oc[3](oc[2](h))), out_feature
+                return oc[2](h)  # the ReLUs are the caller's
+            return oc[4](oc[3](oc[2](h)))
         if (final_out.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
                 and final_out.is_cuda and final_out.is_contiguous(memory_format=torch.channels_last)):
             # conv -> ReLU as conv + (bias, ReLU) epilogue; the 1-channel tail stays on the modules
             h = kernels.conv_nhwc_epilogue(oc[0], final_out, "relu")
-            return oc[4](oc[3](oc[2](h))), out_feature
-        return oc(final_out), out_feature
+            return oc[4](oc[3](oc[2](h)))
+        return oc(final_out)
 
 
 class DepthAnythingV2(nn.Module):
@@ -220,11 +231,13 @@ class DepthAnythingV2(nn.Module):
         self.depth_head = DPTHead(self.pretrained.embed_dim, features, use_bn, out_channels=out_channels,
                                   use_clstoken=use_clstoken)
 
-    def forward(self, x, patches=None, raw_depth: bool = False):
+    def forward(self, x, patches=None, raw_depth: bool = False, defer_tail: bool = False):
         """x: the images [B, 3, H, W]. Not in the reference: `patches` = (patch matrix of
         kernels.da_patches, B, patch_h, patch_w) in place of x (x is then ignored); `raw_depth`: the
         depth comes back as the [B, 1, H, W] map with its trailing ReLUs possibly still to apply
-        (kernels.depth_norm applies ReLU on load; it is idempotent)."""
+        (kernels.depth_norm applies ReLU on load; it is idempotent); `defer_tail` (with raw_depth): in the
+        depth's place comes the pair (fn, final_out), fn(final_out) being that depth (DPTHead.depth_tail
+        on output_conv1's map), for a caller that runs it later."""
         if patches is not None:
             pm, n_img, patch_h, patch_w = patches
             tokens = self.pretrained.prepare_tokens_patches(pm, n_img, patch_h, patch_w)
@@ -241,7 +254,11 @@ class DepthAnythingV2(nn.Module):
             features = self.pretrained.get_intermediate_layers(x, self.intermediate_layer_idx[self.encoder],
                                                                return_class_token=True, tokens=tokens)
         with stage(None, "da_dpt"):
-            depth, out_features = head(features, patch_h, patch_w, raw_tail=raw_depth)
+            depth, out_features = head(features, patch_h, patch_w, raw_tail=raw_depth, defer_tail=defer_tail)
+        if defer_tail:
+            if not raw_depth:
+                raise ValueError("defer_tail returns the raw depth's tail: raw_depth must be set")
+            return (lambda final_out: head.depth_tail(final_out, patch_h, patch_w, True), depth), out_features
         if raw_depth:
             return depth, out_features
         return F.relu(depth).squeeze(1), out_features

@@ -27,6 +27,11 @@ from .common.gaussian_adapter import GaussianAdapter, GaussianAdapterCfg
 from .encoder import Encoder
 from .matching.depth_predictor_trans import DepthPredictorTrans
 
+# Depth-Anything's depth tail (resize, output_conv2, depth_norm: five launches that only produce da_depth) runs
+# in the depth predictor's side-stream fork beside the matching stage instead of in front of the join (bf16x3
+# mode, streams on); False = the head finishes before the join (A/B scripts set it)
+_DEFER_DA_TAIL = True
+
 _DA_CONFIGS = {
     "vits": {"encoder": "vits", "features": 64, "out_channels": [48, 96, 192, 384]},
     "vitb": {"encoder": "vitb", "features": 128, "out_channels": [96, 192, 384, 768]},
@@ -162,21 +167,37 @@ class EncoderTrans(Encoder[EncoderTransCfg]):
                 dino = self.da_model.pretrained
                 # the depth tail as two launches (kernels.depth_norm) from the head's last 1x1 map
                 tail = kernels.split_mode() and images.is_cuda and images.dtype == torch.float32
+                # the depth's first reader is the refine U-Net, a whole matching stage later: the head stops at
+                # output_conv1 and the depth predictor runs the rest in its side-stream fork (_DEFER_DA_TAIL)
+                defer = _DEFER_DA_TAIL and tail and streams.enabled(images.device)
                 if kernels.split_mode() and dino.patches_ok(images):
                     # normalise + reorder + resize + unfold in one launch, straight into the patch
                     # projection's GEMM operand
                     g = 252 // dino.patch_size
                     pm = kernels.da_patches(images, self.img_mean, self.img_std, (g, g), dino.patch_size)
-                    da_depth, out_feature = self.da_model(None, patches=(pm, b * v, g, g), raw_depth=tail)
+                    da_depth, out_feature = self.da_model(None, patches=(pm, b * v, g, g), raw_depth=tail,
+                                                          defer_tail=defer)
                 else:
                     da_images = self.normalize_images(images)
                     da_images = torch.cat((da_images[:, :, 2:3], da_images[:, :, 0:2]), dim=2)
                     da_images = da_images.reshape(b * v, 3, h, w)
                     da_images = kernels.interpolate_bilinear_ac(da_images, (252, 252))
-                    da_depth, out_feature = self.da_model(da_images, raw_depth=tail)
-                if tail:  # ReLU, resize to (h, w), per-view min / max, (d - min) / (max - min)
+                    da_depth, out_feature = self.da_model(da_images, raw_depth=tail, defer_tail=defer)
+
+                def normalized(da_depth):  # ReLU, resize to (h, w), per-view min / max, (d - min) / (max - min)
                     da_depth = kernels.depth_norm(da_depth.float().reshape(b * v, *da_depth.shape[-2:]), (h, w))
-                    return da_depth.view(b, v, 1, h, w), out_feature.float()
+                    return da_depth.view(b, v, 1, h, w)
+
+                if defer:
+                    head_tail, final_out = da_depth
+
+                    def da_tail(final_out):
+                        with torch.no_grad(), self._dense():
+                            return normalized(head_tail(final_out))
+
+                    return (da_tail, final_out), out_feature.float()
+                if tail:
+                    return normalized(da_depth), out_feature.float()
                 da_depth = kernels.interpolate_bilinear_ac(da_depth[None].float().contiguous(), (h, w))
                 da_depth = da_depth.view(b, v, 1, h, w).flatten(2)
                 # per-view min / max in two aminmax stages (rows of w, then the h row results): the
@@ -217,11 +238,12 @@ class EncoderTrans(Encoder[EncoderTransCfg]):
         bb = streams.fork(device, backbone, context["image"], context["intrinsics"], context["extrinsics"],
                           context["near"], context["far"])
         da_depth, out_feature = depth_anything(context["image"])
+        da_tail, da_depth = (da_depth, None) if isinstance(da_depth, tuple) else (None, da_depth)
         trans_features, cnn_features, (dp_cams, adapter_cams) = streams.join(bb)
         with bench("encoder_4_depth_predictor"), self._dense():
             begun = self.depth_predictor.begin(trans_features, context["intrinsics"], context["extrinsics"],
                                                context["near"], context["far"], cnn_features=cnn_features,
-                                               benchmarker=benchmarker, cams=dp_cams)
+                                               benchmarker=benchmarker, cams=dp_cams, da_tail=da_tail)
         dino_feature = out_feature.view(b, v, *out_feature.shape[1:])
 
         extra_info = {"images": rearrange(context["image"], "b v c h w -> (v b) c h w"), "scene_names": scene_names}

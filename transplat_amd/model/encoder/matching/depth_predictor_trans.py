@@ -247,10 +247,18 @@ class DepthPredictorTrans(nn.Module):
         proj_feat_in_fullres = _conv_upsample_gelu(self.upsampler, torch.cat((feat01, cnn_features), dim=1))
         return proj_feat_in_fullres, self.proj_feature(proj_feat_in_fullres)
 
-    def begin(self, features, intrinsics, extrinsics, near, far, cnn_features=None, benchmarker=None, cams=None):
+    def _projection_da(self, feat01, cnn_features, da_fn, da_in):
+        # the fork's branch with Depth-Anything's deferred depth tail da_fn(da_in) [b, v, 1, h, w] behind the
+        # projection (in front of it measured the same: 5.754 against 5.751 ms per step);
+        # da_in is a fork argument so that record_stream sees it
+        return (*self._projection(feat01, cnn_features), da_fn(da_in))
+
+    def begin(self, features, intrinsics, extrinsics, near, far, cnn_features=None, benchmarker=None, cams=None,
+              da_tail=None):
         """The part of forward that reads only the backbone's outputs and the cameras -- 4a's feature
         lists, the full-resolution projection (forked beside the cost volume) and, for two views,
-        the coarse correlation layer; forward(begun=...) continues from it."""
+        the coarse correlation layer; forward(begun=...) continues from it. da_tail = (fn, tensor): the
+        caller's da_depth is fn(tensor), computed in the projection's fork; forward then takes it from there."""
         b, v, c, h, w = features.shape
 
         # the reference's stage tags (depth_predictor_trans.py:320-456) as roctx ranges
@@ -263,7 +271,10 @@ class DepthPredictorTrans(nn.Module):
             feat01 = feat_comb_lists[0]
             # the full-resolution feature projection runs on a side stream beside the cost volume
             # (matching, refine U-Net, depth head: a chain of 64^2 launches), transplat_amd/streams.py
-            proj = streams.fork(features.device, self._projection, feat01, cnn_features)
+            if da_tail is not None:
+                proj = streams.fork(features.device, self._projection_da, feat01, cnn_features, *da_tail)
+            else:
+                proj = streams.fork(features.device, self._projection, feat01, cnn_features)
         coarse = None
         if v == 2:
             with stage(None, "dp_coarse"):  # diagnostic sub-stage mark
@@ -300,7 +311,9 @@ class DepthPredictorTrans(nn.Module):
         with stage(benchmarker, "encoder_4d_coarse_depth"):
             coarse_disps, pdf_max, fullres_disps = self._coarse_depth(raw_correlation, disp_candi_curr)
         with stage(benchmarker, "encoder_4e_depth_refine_unet"):
-            proj_feat_in_fullres, proj_feature = streams.join(proj)
+            proj_feat_in_fullres, proj_feature, *deferred = streams.join(proj)
+            if deferred:  # begin(da_tail=...): Depth-Anything's depth, computed in the fork
+                da_depth = rearrange(deferred[0], "b v ... -> (v b) ...")
             refine_out = run_sequential(self.refine_unet, torch.cat(
                 (extra_info["images"], da_depth, proj_feature, fullres_disps, pdf_max), dim=1))
         with stage(benchmarker, "encoder_4f_gaussian_head"):

@@ -38,6 +38,7 @@ _HIP = {
     "tsplat_conv3x3_few_bf16x3_fwd": ("direct convs (HIP)", "bf16x3"),
     "tsplat_conv2d_bf16x3_fwd": ("direct convs (HIP)", "bf16x3"),
     "tsplat_conv1x1_bf16x3_scaled_fwd": ("direct convs (HIP)", "bf16x3"),
+    "tsplat_conv1x1_bf16x3_inplace_fwd": ("direct convs (HIP)", "bf16x3"),
     "tsplat_conv2d_f32_fwd": ("direct convs (HIP)", "exact fp32"),
     "tsplat_conv2d_f32_zsplit_fwd": ("direct convs (HIP)", "exact fp32"),
     "tsplat_conv2d_f32_nhwc_fwd": ("direct convs (HIP)", "exact fp32"),
